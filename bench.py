@@ -5,8 +5,13 @@ One step = one full map update of a local volume (set_pose → OGM → block all
 obtainFrontiers / waves A,B,C / commit), i.e. the GPU work of VOLMAPNODE::publishMap (src/volumetric_mapper.cpp:138-224).
 Inputs are resident in HBM when a timed region starts.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c5|c2|c3|c4|...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c5|c2|c3|c4|...] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step (--dump-outputs) and prints the
+line: headline keys + config.  --full adds everything else this program measures: the per-step latency pass, the instrumented
+replay behind the roofline objects and kernels_ms_per_step, the other workloads, the CPU baselines, the CostMap publish and the
+library-defaults run, and writes profiles/bench_last_full.json.
 
 Workloads (all synthetic; PRESETS below holds grid / voxel / cutoff / fast_mode of each):
   c5 (default, headline)  BASELINE config 5's sensor-less hash world on a 512^3 grid at 0.05 m, cutoff 2 m: FULL observation,
@@ -22,13 +27,17 @@ With N > 1 every rank owns one 512^3 tile of a larger volume around the same rob
 BASELINE config 5 itself): one-voxel halo exchange + refinement over RCCL after every update until no tile changed
 (gie/tiling.py exchange_converged_device).  Per-GPU work is fixed: scaling is "weak".
 
-Rank 0 prints ONE JSON line, kept below 8 KB (build_line): headline keys, ONE roofline object, cpu_baseline, per-workload
-step times.  Everything else (per-kernel roofline trees, notes, regions) goes to profiles/bench_last_full.json.
+Rank 0 prints ONE JSON line, kept below 8 KB (build_line): headline keys and, with --full, ONE roofline object, cpu_baseline,
+per-workload step times.  Everything else (per-kernel roofline trees, notes, regions) goes to profiles/bench_last_full.json.
 
-Timing: W warm-up steps, then regions of EXACTLY K steps, each bracketed by barrier + synchronize on both sides (MAX over
-ranks); regions repeat until >= 0.5 s has been timed and `value` / `ms_per_step` come from the median region.  Per-step
-latencies (median, p95) come from a further pass with one event pair per step on the mapper's stream, kernel durations from
-a replay of the first region on a fresh mapper with HIP events on every kernel's dispatch.
+Timing: W warm-up steps, then ONE region of EXACTLY K steps, bracketed by barrier + synchronize on both sides (MAX over ranks):
+`ms_per_step` = region / K.  --min-timed-s S repeats the region until S seconds have been timed and takes the median region.
+With --full, per-step latencies (median, p95) come from a further pass with one event pair per step on the mapper's stream,
+kernel durations from a replay of the first region on a fresh mapper with HIP events on every kernel's dispatch.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes the local map its last timed step left (what gie_read_local hands a
+caller: edt, type, dist_sq, coc) to DIR/<name>.npy as float32 / float64; a volume above DUMP_SAMPLE voxels is sampled at a fixed,
+seeded set of voxels (DIR/sample_index.npy: their [Z][Y][X] flat indices).  The inputs are seeded: same arguments, same inputs.
 """
 import argparse
 import json
@@ -180,37 +189,46 @@ def make_frames(scenes, voxel, nframes, seed, sensor):
 
 
 class HashWorldFeed:
-    """BASELINE config 5: label planes of the hash world, built on the device between timed regions."""
+    """BASELINE config 5: label planes of the hash world, built on the device between timed regions.  A plane depends on the
+    frame only through the pivot and the frame's parity (scenes.hash_world_labels): frames that share both share one plane, so the
+    out-and-back drive needs at most C5_TURN + 1 planes however many steps a region holds."""
 
     kind = "labels"
 
     def __init__(self, torch, scenes, dev, voxel, size, tile_off):
         self.torch, self.scenes, self.dev, self.voxel, self.size, self.tile_off = torch, scenes, dev, voxel, size, tile_off
-        self.first, self.planes = 0, []
+        self.planes, self.ptrs = {}, {}
 
     def pose(self, i):
         return c5_pose(self.scenes, i, self.voxel)
 
+    def _key(self, i):
+        pos, _ = self.pose(i)
+        return self.scenes.local_pivot(pos, self.voxel, self.size, self.tile_off), i % 2
+
     def prepare(self, first, count):
         torch = self.torch
-        while len(self.planes) < count:
-            self.planes.append(torch.empty(self.size[2], self.size[1], self.size[0], dtype=torch.int8, device=self.dev))
-        for j in range(count):
-            pos, _ = self.pose(first + j)
-            pvt = self.scenes.local_pivot(pos, self.voxel, self.size, self.tile_off)
+        keys = {i: self._key(i) for i in range(first, first + count)}
+        need = set(keys.values())
+        self.planes = {k: v for k, v in self.planes.items() if k in need}      # (the mapper is idle here: nothing reads a dropped plane)
+        for k in sorted(need):
+            if k in self.planes:
+                continue
+            pvt, parity = k
             lab = self.scenes.hash_world_labels(
-                pvt, self.size, first + j, seed=C5["seed"], p_occ=C5["p_occ"], toggle_frac=C5["toggle_frac"],
+                pvt, self.size, parity, seed=C5["seed"], p_occ=C5["p_occ"], toggle_frac=C5["toggle_frac"],
                 arange=lambda n: torch.arange(n, dtype=torch.int64, device=self.dev),
                 where=lambda c, a, b: torch.where(c, torch.tensor(a, dtype=torch.int8, device=self.dev), torch.tensor(b, dtype=torch.int8, device=self.dev)))
-            self.planes[j].copy_(lab)
+            self.planes[k] = torch.empty(self.size[2], self.size[1], self.size[0], dtype=torch.int8, device=self.dev)
+            self.planes[k].copy_(lab)
             del lab
-        self.first = first
+        self.ptrs = {i: self.planes[k].data_ptr() for i, k in keys.items()}
         torch.cuda.synchronize()
 
     def step_input(self, m, i):
         pos, q = self.pose(i)
         m.set_pose(pos, q)
-        m.ogm_labels_dev(self.planes[i - self.first].data_ptr(), borrow=True)      # (the planes stay resident and untouched: gie_fuse reads them in place)
+        m.ogm_labels_dev(self.ptrs[i], borrow=True)      # (the planes stay resident and untouched: gie_fuse reads them in place)
 
     def describe(self):
         return ("sensor-less hash world (BASELINE config 5): occupied iff hash(x,y,z) < %.0f %%, full observation, %.0f %% of the "
@@ -456,8 +474,9 @@ class Runner:
 
 def run_workload(torch, gie, scenes, tiling, dist, workload, size, voxel, cutoff_dist, W, K, rank, world, dev, local_rank, backend,
                  min_timed_s=0.5, max_regions=MAX_REGIONS, with_latency=True, rms=False, group=None, transport_note=None, fast_mode=False,
-                 default_knobs=False):
-    """Timed regions + latency pass + instrumented replay for one workload.  Returns a dict (rank 0) or None."""
+                 default_knobs=False, full=True, dump_dir=None):
+    """Timed regions (+ with full: latency pass + instrumented replay) for one workload.  Returns a dict (rank 0) or None.
+    dump_dir: rank 0 writes the outputs of the last timed step there (dump_outputs) before anything else runs on the mapper."""
     n_vox = size[0] * size[1] * size[2]
     tile_off = tiling.tile_offset_voxels(rank, world, size) if world > 1 else (0, 0, 0)
     cfg = gie.make_config(voxel, size, cutoff_dist=cutoff_dist, fast_mode=fast_mode, device_id=local_rank, retain_radius_blocks=DRIVE["retain"],
@@ -477,13 +496,16 @@ def run_workload(torch, gie, scenes, tiling, dist, workload, size, voxel, cutoff
             break
     st1 = r.m.stats()
     timed_updates = K * len(regions)
-    lat = r.latency_pass(first, K) if with_latency else []
-    first += K if with_latency else 0
+    if dump_dir and rank == 0:
+        dump_outputs(r.m, dump_dir)
+    lat = r.latency_pass(first, K) if with_latency and full else []
+    first += K if with_latency and full else 0
     res = None
     accuracy = None
+    ray_cells = None
     if rank == 0 and rms:
         accuracy = accuracy_check(r.m, voxel)
-    if rank == 0:
+    if rank == 0 and full:
         ty = r.m.read_local(edt=False, dist_sq=False, coc=False)["type"]
         kn = ty != 0
         n_known = int(kn.sum())
@@ -500,7 +522,6 @@ def run_workload(torch, gie, scenes, tiling, dist, workload, size, voxel, cutoff
                  "edt_pass_y": planes * Ys * Xs, "edt_pass_x": planes * Ys * Xs, "edt_pass_z": int(kt.sum()) * 512,
                  "ogm_classify": n_vox}
         known = n_known / float(n_vox)
-        ray_cells = None
         del ty, kn, kt, face
         res = {"known": known, "units": units}
     blocks = st1["blocks_total"]
@@ -521,6 +542,44 @@ def run_workload(torch, gie, scenes, tiling, dist, workload, size, voxel, cutoff
     r.close()
     if rank != 0:
         return None
+    med = percentile(regions, 0.5)
+    ms_per_step = 1e3 * med / K
+    hz = K / med
+    value = world * n_vox * hz / 1e6
+    visits = {k: (st1["total_visits_" + k] - st0["total_visits_" + k]) / float(timed_updates) for k in "abc"}
+    tgrid = tiling.tile_grid(world)
+    out = {
+        "value": round(value, 2), "ms_per_step": round(ms_per_step, 4), "hz": round(hz, 3),
+        "timed_regions": len(regions), "region_ms": [round(1e3 * x, 3) for x in regions], "timed_s": round(sum(regions), 3),
+        "config": {"workload": "%dx%dx%d @ %.2f m, %s, full map update, cutoff %.0f m, fast_mode %s"
+                               % (size[0], size[1], size[2], voxel, feed.describe(), cutoff_dist, "on" if fast_mode else "off"),
+                   "preset": workload, "baseline_config": BASELINE_CONFIG.get(workload),
+                   "grid": list(size), "voxel_m": voxel, "cutoff_m": cutoff_dist, "fast_mode": bool(fast_mode),
+                   "drive": ({"mode": DRIVE["mode"], "turn_frames": C5_TURN if DRIVE["mode"] == "turn" else None, "delta_vox": C5["delta_vox"],
+                              "retain_radius_blocks": DRIVE["retain"]} if workload == "c5" else
+                             {"mode": "turn", "turn_frames": LIDAR_TURN, "delta_vox": PRESETS[workload]["delta"], "retain_radius_blocks": DRIVE["retain"]}),
+                   "tiles": ("%dx%dx%d tiles of %dx%dx%d, one per GPU" % (tgrid + tuple(size))) if world > 1 else "single volume",
+                   "known_voxel_fraction": round(res["known"], 4) if res else None,
+                   "wave_visits_per_step": [round(visits[k], 1) for k in "abc"],
+                   "wave_levels_last_step": [st1["levels_a"], st1["levels_b"], st1["levels_c"]],
+                   "blocks": blocks},
+        "steps": K, "warmup": W,
+    }
+    if res is None:                                 # (a plain run reads no map back)
+        del out["config"]["known_voxel_fraction"]
+    if world > 1:       # the halo exchange this run timed (VERDICT r4 "next" #3 / #10)
+        out["config"].update({
+            "exchange": "RCCL" if backend == "nccl" else "gloo, host staging", "rccl_ranks": world if backend == "nccl" else 0,
+            "halo_mode": halo_mode, "halo_max_rounds": r.halo_rounds, "rounds_per_update": round(rounds_per_step, 3),
+            "updates_unconverged": (round_stats or {}).get("updates_unconverged"), "exchange_notes": notes})
+        if lat:
+            # what follows the tile's own sweep in a step (face export, transfers, import, merge end, refinement rounds), median over the
+            # latency pass; nothing of it overlaps the tile's own work (obtainFrontiers reads the ghosts): overlap_frac 0
+            out["config"].update({"exchange_ms_per_step": round(percentile(getattr(r, "exchange_ms", []) or [0.0], 0.5), 4), "overlap_frac": 0.0})
+    if accuracy is not None:
+        out["accuracy"] = accuracy
+    if not full:
+        return out
     # kernel durations: the first region replayed on a fresh mapper with start / stop events on every kernel's dispatch
     # (rank 0's tile, no halo exchange: the exchange kernels are not roofline candidates)
     feed2 = feed            # (same frames: a lidar / depth feed keeps the scans it has generated)
@@ -541,11 +600,6 @@ def run_workload(torch, gie, scenes, tiling, dist, workload, size, voxel, cutoff
     sv1 = r2.m.stats()
     r2.close()
 
-    med = percentile(regions, 0.5)
-    ms_per_step = 1e3 * med / K
-    hz = K / med
-    value = world * n_vox * hz / 1e6
-    visits = {k: (st1["total_visits_" + k] - st0["total_visits_" + k]) / float(timed_updates) for k in "abc"}
     visits_instr = sum(sv1["total_visits_" + k] - sv0["total_visits_" + k] for k in "abc") / float(K)
     units = res["units"]
     alg = dict(ALG_BYTES)
@@ -645,43 +699,41 @@ def run_workload(torch, gie, scenes, tiling, dist, workload, size, voxel, cutoff
     update = group_roof(list(sweeps), ms_per_step) or {}
     update["note"] = "every stage of the map update: bytes of all kernels of a step / the uninstrumented step time"
 
-    tgrid = tiling.tile_grid(world)
-    out = {
-        "value": round(value, 2), "ms_per_step": round(ms_per_step, 4), "hz": round(hz, 3),
-        "timed_regions": len(regions), "region_ms": [round(1e3 * x, 3) for x in regions], "timed_s": round(sum(regions), 3),
+    out.update({
         "step_ms": ({"median": round(percentile(lat, 0.5), 4), "p95": round(percentile(lat, 0.95), 4), "min": round(min(lat), 4),
                      "max": round(max(lat), 4), "n": len(lat), "how": "one event pair per step on the mapper's stream, separate pass"} if lat else None),
-        "config": {"workload": "%dx%dx%d @ %.2f m, %s, full map update, cutoff %.0f m, fast_mode %s"
-                               % (size[0], size[1], size[2], voxel, feed2.describe(), cutoff_dist, "on" if fast_mode else "off"),
-                   "preset": workload, "baseline_config": BASELINE_CONFIG.get(workload),
-                   "grid": list(size), "voxel_m": voxel, "cutoff_m": cutoff_dist, "fast_mode": bool(fast_mode),
-                   "drive": ({"mode": DRIVE["mode"], "turn_frames": C5_TURN if DRIVE["mode"] == "turn" else None, "delta_vox": C5["delta_vox"],
-                              "retain_radius_blocks": DRIVE["retain"]} if workload == "c5" else
-                             {"mode": "turn", "turn_frames": LIDAR_TURN, "delta_vox": PRESETS[workload]["delta"], "retain_radius_blocks": DRIVE["retain"]}),
-                   "tiles": ("%dx%dx%d tiles of %dx%dx%d, one per GPU" % (tgrid + tuple(size))) if world > 1 else "single volume",
-                   "known_voxel_fraction": round(res["known"], 4),
-                   "wave_visits_per_step": [round(visits[k], 1) for k in "abc"],
-                   "wave_levels_last_step": [st1["levels_a"], st1["levels_b"], st1["levels_c"]],
-                   "blocks": blocks},
-        "steps": K, "warmup": W,
         "kernels_ms_per_step": {k: round(v[0] / K, 4) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0])},
         "ms_per_step_instrumented": round(1e3 * dt_instr / K, 4),
         "roofline": roofline, "roofline_wavefront_sweep": wavefront, "roofline_update": update,
         "roofline_sweeps": {k: {kk: vv for kk, vv in v.items() if kk != "kernel"} for k, v in sweeps.items()},
-    }
-    if world > 1:       # the halo exchange this run timed (VERDICT r4 "next" #3 / #10)
-        out["config"].update({
-            "exchange": "RCCL" if backend == "nccl" else "gloo, host staging", "rccl_ranks": world if backend == "nccl" else 0,
-            "halo_mode": halo_mode, "halo_max_rounds": r.halo_rounds, "rounds_per_update": round(rounds_per_step, 3),
-            "updates_unconverged": (round_stats or {}).get("updates_unconverged"), "exchange_notes": notes,
-            # what follows the tile's own sweep in a step (face export, transfers, import, merge end, refinement rounds), median over the
-            # latency pass; nothing of it overlaps the tile's own work (obtainFrontiers reads the ghosts): overlap_frac 0
-            "exchange_ms_per_step": round(percentile(getattr(r, "exchange_ms", []) or [0.0], 0.5), 4), "overlap_frac": 0.0})
+    })
     if model_errors:
         out["roofline_model_errors"] = sorted(model_errors)
-    if accuracy is not None:
-        out["accuracy"] = accuracy
     return out
+
+
+DUMP_SAMPLE = 1 << 20        # voxels --dump-outputs writes at most: 48 B each over the five files (48 MB)
+DUMP_SEED = 12345
+
+
+def dump_sample_index(n, k=DUMP_SAMPLE, seed=DUMP_SEED):
+    """The voxels --dump-outputs writes: all n of them, or a fixed, seeded, sorted choice of k flat [Z][Y][X] indices."""
+    if n <= k:
+        return None
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def dump_outputs(m, out_dir):
+    """What gie_read_local hands a caller after the last timed step (EDT, voxel type, squared distance, closest obstacle), as
+    out_dir/<name>.npy in float32 / float64 (every value exact): all voxels, or the DUMP_SAMPLE of dump_sample_index."""
+    loc = m.read_local()
+    idx = dump_sample_index(m.n)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a, dt in (("edt", loc["edt"].reshape(-1), np.float32), ("type", loc["type"].reshape(-1), np.float32),
+                        ("dist_sq", loc["dist_sq"].reshape(-1), np.float64), ("coc", loc["coc"].reshape(-1, 3), np.float64)):
+        np.save(os.path.join(out_dir, name + ".npy"), (a if idx is None else a[idx]).astype(dt))
+    if idx is not None:
+        np.save(os.path.join(out_dir, "sample_index.npy"), idx.astype(np.float64))
 
 
 def accuracy_check(m, voxel):
@@ -919,14 +971,16 @@ def build_line(main_res, extras, cpu, n_gpus, metric="edt_map_update_throughput"
     line = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data")}
     line["hz"] = main_res["hz"]
     line["config"] = {k: _short(v) for k, v in cfgm.items() if k not in ("drive", "exchange_notes", "wave_levels_last_step")}
-    line["roofline"] = compact_roofline(main_res["roofline"])
-    ws, up = main_res.get("roofline_wavefront_sweep") or {}, main_res.get("roofline_update") or {}
-    line["roofline_wavefront_sweep"] = {k: ws.get(k) for k in ("ms_per_step", "frac", "frac_basis", "frac_algorithmic") if k in ws}
-    line["roofline_update"] = {k: up.get(k) for k in ("ms_per_step", "frac", "frac_basis", "frac_algorithmic") if k in up}
+    if "roofline" in main_res:                  # (the instrumented replay of --full)
+        line["roofline"] = compact_roofline(main_res["roofline"])
+        ws, up = main_res.get("roofline_wavefront_sweep") or {}, main_res.get("roofline_update") or {}
+        line["roofline_wavefront_sweep"] = {k: ws.get(k) for k in ("ms_per_step", "frac", "frac_basis", "frac_algorithmic") if k in ws}
+        line["roofline_update"] = {k: up.get(k) for k in ("ms_per_step", "frac", "frac_basis", "frac_algorithmic") if k in up}
     if main_res.get("step_ms"):
         line["step_ms"] = {k: main_res["step_ms"][k] for k in ("median", "p95")}
     line["timed_regions"], line["timed_s"] = main_res["timed_regions"], main_res["timed_s"]
-    line["kernels_ms_per_step"] = main_res["kernels_ms_per_step"]
+    if "kernels_ms_per_step" in main_res:
+        line["kernels_ms_per_step"] = main_res["kernels_ms_per_step"]
     if main_res.get("roofline_model_errors"):
         line["roofline_model_errors"] = main_res["roofline_model_errors"]
     if cpu is not None:
@@ -951,7 +1005,8 @@ def build_line(main_res, extras, cpu, n_gpus, metric="edt_map_update_throughput"
         line["accuracy"] = {k: _short(v) for k, v in main_res["accuracy"].items()}
     if costmap is not None:          # row a17 (CostMap.msg payload, 8 B/voxel), off the timed region: never part of `value`
         line["costmap_publish"] = costmap
-    line["detail"] = full_file
+    if full_file:
+        line["detail"] = full_file
     # the limit holds whatever a run produces: drop the least important blocks first
     for k in ("roofline_ogm", "costmap_publish", "kernels_ms_per_step", "mvoxels_per_s_by_workload", "baseline_config_by_workload", "accuracy", "roofline_update", "step_ms"):
         if len(json.dumps(line)) <= LINE_LIMIT:
@@ -1003,7 +1058,14 @@ def run_bench():
     ap.add_argument("--voxel", type=float, default=None, help="voxel width in m (default: the preset's)")
     ap.add_argument("--cutoff", type=float, default=None, help="wave cutoff distance in m (default: the preset's)")
     ap.add_argument("--workload", "--sensor", dest="workload", choices=WORKLOADS, default="c5")
-    ap.add_argument("--min-timed-s", type=float, default=0.5, help="repeat the K-step region until this much has been timed")
+    ap.add_argument("--min-timed-s", type=float, default=0.0,
+                    help="repeat the K-step region until this much has been timed, up to %d regions (default: one region, K timed steps)" % MAX_REGIONS)
+    ap.add_argument("--full", action="store_true",
+                    help="also the latency pass, the instrumented replay (roofline, kernels_ms_per_step), the other workloads, the CPU baselines, "
+                         "the CostMap publish, the library-defaults run and the side file %s" % FULL_FILE)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the local map of the last timed step to DIR/<name>.npy (float32 / float64; a seeded sample of %d voxels "
+                         "of a larger volume)" % DUMP_SAMPLE)
     ap.add_argument("--drive", choices=["turn", "line"], default="turn", help="c5 robot: 24 frames out and 24 back (default), or a straight line forever")
     ap.add_argument("--retain", type=int, default=0, help="gie_config.retain_radius_blocks: erase and recycle blocks more than R blocks outside the volume (0: never, the reference's rule)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -1011,7 +1073,7 @@ def run_bench():
                     help="accuracy profiler (the reference's Gnd_truth_checker, gt_checker.h:30-80): RMSE of the local EDT after the last "
                          "timed update against the exact distance to the nearest occupied voxel of the volume")
     ap.add_argument("--no-extras", "--no-secondary", dest="no_extras", action="store_true",
-                    help="skip the runs reported beside the headline (lidar workloads, BASELINE configs 2 / 3 / 4)")
+                    help="--full: skip the runs reported beside the headline (lidar workloads, BASELINE configs 2 / 3 / 4)")
     ap.add_argument("--extras", default=None, help="comma list of workloads to run beside the headline (default: %s)" % ",".join(DEFAULT_EXTRAS))
     args = ap.parse_args()
     DRIVE["mode"], DRIVE["retain"] = args.drive, max(0, args.retain)
@@ -1068,8 +1130,11 @@ def run_bench():
                             kw.pop("world", 1), dev, local_rank, backend, fast_mode=p["fast"], **kw), (size, voxel, cutoff)
 
     main_res, (size, voxel, cutoff) = run(args.workload, dist=dist, rank=rank, world=world, min_timed_s=args.min_timed_s, rms=args.rms, group=group,
-                                          transport_note=transport_note)
-    if rank == 0:
+                                          transport_note=transport_note, full=args.full, dump_dir=args.dump_outputs)
+    if rank == 0 and not args.full:
+        line, _ = build_line(main_res, {}, None, world, full_file=None)
+        print(json.dumps(line), flush=True)
+    elif rank == 0:
         extras = {}
         if world == 1 and not args.no_extras:
             names = [w for w in (args.extras.split(",") if args.extras else DEFAULT_EXTRAS) if w and w != args.workload]

@@ -164,6 +164,54 @@ def test_bench_line_stays_below_8_kb_and_round_trips():
     assert len(json.dumps(l8)) < 8192
 
 
+def test_plain_line_is_the_headline():
+    """A plain run (no --full) times the headline only: its line carries the contract's keys and nothing of the instrumented
+    replay, the other workloads or the side file."""
+    import json
+    main_res = _canned_result("c5", 2.3298, big=False)
+    for k in ("step_ms", "kernels_ms_per_step", "ms_per_step_instrumented", "roofline", "roofline_wavefront_sweep", "roofline_update", "roofline_sweeps"):
+        del main_res[k]
+    del main_res["config"]["known_voxel_fraction"]
+    line, _ = bench.build_line(main_res, {}, None, 1, full_file=None)
+    back = json.loads(json.dumps(line))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert k in back, k
+    assert back["ms_per_step"] == 2.3298 and back["higher_is_better"] is True and back["unit"] == "Mvoxels/s"
+    for k in ("roofline", "kernels_ms_per_step", "cpu_baseline", "ms_per_step_by_workload", "detail"):
+        assert k not in back, k
+
+
+def test_hash_world_planes_depend_on_pivot_and_parity_only(monkeypatch):
+    """HashWorldFeed keeps one label plane per (pivot, frame parity): each frame's plane must be the one its own frame index gives,
+    and a long region of the out-and-back drive must need no more than C5_TURN + 1 planes."""
+    import torch
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    size, voxel = (24, 16, 8), 0.05
+    feed = bench.HashWorldFeed(torch, scenes, torch.device("cpu"), voxel, size, (0, 0, 0))
+    first, count = 5, 4 * bench.C5_TURN + 3
+    feed.prepare(first, count)
+    assert len(feed.planes) <= bench.C5_TURN + 1
+    by_ptr = {t.data_ptr(): t for t in feed.planes.values()}
+    for i in range(first, first + count):
+        pos, _ = bench.c5_pose(scenes, i, voxel)
+        want = scenes.hash_world_labels(scenes.local_pivot(pos, voxel, size), size, i, seed=bench.C5["seed"], p_occ=bench.C5["p_occ"],
+                                        toggle_frac=bench.C5["toggle_frac"])
+        assert np.array_equal(by_ptr[feed.ptrs[i]].numpy(), want.astype(np.int8)), i
+    feed.prepare(0, 2)                       # a later region drops the planes it does not need
+    assert len(feed.planes) == 2
+
+
+def test_dump_sample_is_fixed_and_small():
+    """--dump-outputs: a volume above DUMP_SAMPLE voxels is written at a fixed, seeded, sorted sample; all files <= 64 MB."""
+    n = 512 ** 3
+    idx = bench.dump_sample_index(n)
+    assert idx.shape == (bench.DUMP_SAMPLE,) and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < n
+    assert np.array_equal(idx, bench.dump_sample_index(n))
+    assert bench.dump_sample_index(bench.DUMP_SAMPLE) is None
+    # edt f32 + type f32 + dist_sq f64 + coc 3 x f64 + sample_index f64 per voxel
+    assert bench.DUMP_SAMPLE * (4 + 4 + 8 + 24 + 8) <= 64 * 2 ** 20
+
+
 def test_presets_are_the_baseline_configs():
     """BASELINE.json configs 2-5 as bench presets, with the reference's parameters (cfg/cow_lady_params.yaml:15-27,
     cfg/ugv_laser3D_params.yaml:17-28, cfg/uav_laser3D_params.yaml:16-28 + launch/uav_raycast.launch:4-8)."""

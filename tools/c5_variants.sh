@@ -10,7 +10,7 @@ i=0
 for v in "$@"; do
   i=$((i+1))
   echo "== variant $i: $v"
-  env $v timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extras --min-timed-s 0.2 > $OUT/v$i.json 2> $OUT/v$i.err || tail -3 $OUT/v$i.err
+  env $v timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extras --min-timed-s 0.2 > $OUT/v$i.json 2> $OUT/v$i.err || tail -3 $OUT/v$i.err
   python - "$OUT/v$i.json" <<'PY'
 import json, sys
 try:

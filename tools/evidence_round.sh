@@ -14,6 +14,6 @@ done
 rm -rf $O/cu
 python tools/soak_fullsize.py --c5 --frames 8 > $O/soak_fullsize_c5_8_updates.log 2>&1
 python tools/soak_fullsize.py --frames 9 --pattern rpp > $O/soak_fullsize_9_updates_rpp.log 2>&1
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
 cp profiles/bench_last_full.json $O/bench_driver_cmd_full.json
 ls -la $O

@@ -7,5 +7,5 @@ sys.path.insert(0, ROOT)
 os.chdir(ROOT)
 import bench  # noqa: E402
 bench.PLACE_TRIES = int(sys.argv[1])
-sys.argv = ["bench.py", "--steps", "20", "--warmup", "5", "--no-extras", "--no-cpu-baseline"]
+sys.argv = ["bench.py", "--full", "--steps", "20", "--warmup", "5", "--no-extras", "--no-cpu-baseline"]
 bench.main()
