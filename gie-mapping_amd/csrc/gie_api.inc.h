@@ -23,6 +23,29 @@ static thread_local std::string g_gie_err;
 static void gie_set_err(const std::string &s) { g_gie_err = s; }
 extern "C" const char *gie_last_error(void) { return g_gie_err.c_str(); }
 
+/* ---- THE PAIR PLANE'S HOST STATE (gie_ops.h "deferred records", "lazy pairs", "Mark + commit"): what a fused merge has left to the
+ * pair plane that the reference stores in the global map.  The gie_pp_* transitions below (and gie_catchup_everything) are the only
+ * writers of these fields and of the gie_ctx fields they steer: c.track, c.fused, c.prev_valid, c.prev_shift, c.skip2_ok, c.oldskip,
+ * c.catchup_fast, c.coc_defer, c.qdefer, c.lazy_ok, c.bcoc_lazy, c.pp_pvt / pp_upvt, c.ts_pvt.  Invariants: coc_pending implies
+ * owed != NONE (only a fused merge defers); c.qdefer == coc_pending, except inside gie_fuse from the rotation of the tile planes to its
+ * end, where it is 0; c.prev_valid / c.skip2_ok only if owed was FRESH at that gie_fuse; after gie_batch_edt, c.bcoc != c.bcoc_lazy. */
+enum gie_owed {
+    GIE_OWED_NONE,      /* nothing is owed: the last merge ran in the reference's order (its commit stored every pair), or none ran */
+    GIE_OWED_FRESH,     /* the last merge ran fused: its volume's stored pairs are written as their voxels leave; types and block table are its */
+    GIE_OWED_STALE      /* ... but a gie_fuse without a merge, or a table roll for ghosts, replaced them: the flush goes by hash and marks */
+};
+struct gie_pivots { int pvt[3], upvt[3], tb0[3]; };   /* pivot, wave-range pivot and block-table origin of a merge */
+struct gie_pair_state {
+    gie_owed owed = GIE_OWED_NONE;        /* whose pairs the pair plane holds */
+    gie_pivots last = {};                 /* the last fused merge's: the owed pairs were written at these pivots */
+    int flushed_ct = -1;                  /* map tick (c.map_ct) of the pose the owed pairs were last written for ahead of gie_fuse (gie_pp_before_import) */
+    int coc_pending = 0;                  /* voxels of the current tskip tiles have their records in the pair plane only */
+    int lazy_pending = 0;                 /* tiles may be flagged in tlazy: their pairs are gie_pair_of_bcoc(c.bcoc_lazy) at c.pp_pvt / c.pp_upvt */
+    uint32_t *bcoc_alt = nullptr;         /* the other batch-obstacle plane (allocated by gie_create): pass Z writes the one the lazy pairs are not derived from */
+    int tsp_pvt[3] = {};                  /* the pivot tskip_prev's tiles refer to (c.ts_pvt: tskip's) */
+    int fuse_fresh = 0;                   /* gie_fuse has run and no merge has consumed it yet (a merge needs the frame clear of its own map update) */
+    int track_want = 0;                   /* gie_stream_enable: taken over by the next gie_fuse (an update runs in ONE order of kernels from its fuse to its merge) */
+};
 struct gie_mapper {
     gie_config cfg;
     gie_ctx c;
@@ -30,15 +53,12 @@ struct gie_mapper {
     int ncell;
     int has_pose, has_ogm, merge_open;
     int bar_fault_left;     /* map updates whose wavefront launch gets the barrier fault (gie_debug_fault_barrier) */
-    int fuse_fresh;                       /* gie_fuse has run and no merge has consumed it yet (a merge needs the frame clear of its own map update) */
+    gie_pair_state pp;                    /* the pair plane's host state (above) */
     int pool_base;                        /* GIE_DEBUG_POOL_BASE (tests): the slots below it are never handed out */
     int evictions;                        /* map updates with block erasure since the hash table was last rebuilt */
     long long tomb_bound;                 /* upper bound of the tombstones those erasures left in the table */
     int retain_box_valid, retain_box_lo[3], retain_box_hi[3];   /* block box +- retain of the last update that erased */
-    int deferred;                         /* the last merge ran fused: the stored pairs of its volume's voxels are still to be written when they leave (gie_commit_pair) */
     int32_t *blk_tab2; int tab_valid, tab_tb0[3];   /* the other block table (the tables of consecutive fuses alternate) and where the current one was built */
-    int flush_tab_ok;                     /* ... and _glb_type / the block table are still that update's (no gie_fuse since) */
-    int commit_pvt[3], commit_upvt[3], commit_tb0[3];   /* pivots / block-table origin of that merge */
     int edt_partial;                      /* the last batch EDT skipped tiles nobody reads (gie_read_batch_edt completes it) */
     int ogm_unlabelled;                   /* ray-cast scan whose _inst_type labels have not been written (gie_read_ogm does it) */
     float msg_origin[3];
@@ -54,13 +74,7 @@ struct gie_mapper {
     int32_t h_cnt[GIE_CNT_NUM];
     int32_t next_off[3], next_whole[3];
     float us[4];
-    int track_want;                       /* gie_stream_enable: taken over by the next gie_fuse (an update runs in ONE order of kernels from its fuse to its merge) */
     const int8_t *labels_pending;         /* the last scan is a label plane left in place (c.scan_labels until gie_fuse): materialised into `_inst_type` if anything else wants it */
-    int coc_pending;                      /* voxels of the current tskip tiles have their records in the pair plane only (gie_ops.h "deferred records") */
-    int lazy_pending;                     /* tiles may be flagged in tlazy: their pairs are not in the pair plane (gie_ops.h "lazy pairs") */
-    uint32_t *bcoc_alt;                   /* the other batch-obstacle plane (pass Z never writes the one the lazy pairs are derived from) */
-    int tsp_pvt[3];                       /* the pivot tskip_prev's tiles refer to */
-    int flushed_ct;                       /* map tick (c.map_ct) of the pose the owed pairs were last written for ahead of gie_fuse (gie_owed_pairs_before_import) */
     /* CostMap publishing without a stall (gie_costmap_publish / gie_costmap_acquire): device staging + two pinned host buffers */
     gie_seendist *d_cm; void *h_cm[2]; size_t cm_bytes; int cm_slot, cm_pending;
     long long *d_round_stats;             /* exchange rounds without the host: rounds enqueued / run, updates / updates left unconverged (k_round_note) */
@@ -149,6 +163,7 @@ static int gie_pow2_ge(long long v) { int p = 1; while ((long long)p < v) p <<= 
 
 #define GIE_MAX_POOL_BLOCKS (1 << 26)          /* slots are 32-bit, voxel addresses (slot * 512 + index) 64-bit: what bounds a pool is the device's memory
                                                 * (38 B per voxel: 15 M blocks in 288 GB); this is where the hash table's 32-bit index arithmetic ends */
+static void gie_pp_init(gie_mapper *m); static void gie_pp_pose(gie_mapper *m);     /* (pair-plane transitions, below) */
 extern "C" gie_mapper *gie_create(const gie_config *cfg)
 {
     if (!cfg || cfg->voxel_width <= 0.f || cfg->local_size[0] < 1 || cfg->local_size[1] < 1 || cfg->local_size[2] < 1) {
@@ -167,7 +182,7 @@ extern "C" gie_mapper *gie_create(const gie_config *cfg)
     }
     gie_mapper *m = new gie_mapper();
     m->cfg = *cfg;
-    m->has_pose = m->has_ogm = 0; m->merge_open = 0; m->bar_fault_left = 0; m->c.bar_fault = 0; m->edt_partial = 0; m->ogm_unlabelled = 0; m->evictions = 0; m->tomb_bound = 0; m->retain_box_valid = 0; m->deferred = 0; m->flush_tab_ok = 0; m->fuse_fresh = 0; m->flushed_ct = -1; m->coc_pending = 0; m->labels_pending = nullptr; m->track_want = 0;
+    m->has_pose = m->has_ogm = 0; m->merge_open = 0; m->bar_fault_left = 0; m->c.bar_fault = 0; m->edt_partial = 0; m->ogm_unlabelled = 0; m->evictions = 0; m->tomb_bound = 0; m->retain_box_valid = 0; m->labels_pending = nullptr;
     m->d_cm = nullptr; m->h_cm[0] = m->h_cm[1] = nullptr; m->cm_bytes = 0; m->cm_slot = 0; m->cm_pending = 0;
     for (int i = 0; i < 3; i++) { m->next_off[i] = 0; m->next_whole[i] = cfg->local_size[i]; }
     m->d_sensor = nullptr; m->sensor_cap = 0; m->d_pts_g = nullptr; m->pts_cap = 0;
@@ -198,7 +213,7 @@ extern "C" gie_mapper *gie_create(const gie_config *cfg)
     c.cy1 = gie_dalloc<uint16_t>(m, N);
     c.cxy2 = gie_dalloc<uint32_t>(m, N);
     c.bcoc = gie_dalloc<uint32_t>(m, N);
-    m->bcoc_alt = gie_dalloc<uint32_t>(m, N);
+    m->pp.bcoc_alt = gie_dalloc<uint32_t>(m, N);
     c.pair = gie_dalloc<uint64_t>(m, N);      /* zero-initialised: SURVEY App. B #3 */
     c.wl = gie_dalloc<uint32_t>(m, N);
     for (int i = 0; i < 3; i++) c.tfd[i] = (cfg->local_size[i] + 7) / 8;
@@ -212,9 +227,7 @@ extern "C" gie_mapper *gie_create(const gie_config *cfg)
     c.tskip = gie_dalloc<uint8_t>(m, 2 * ntile);
     c.tskip_prev = c.tskip ? c.tskip + ntile : nullptr;
     c.tlazy = gie_dalloc<uint8_t>(m, ntile);
-    c.bcoc_lazy = c.bcoc; c.lazy_ok = 0; m->lazy_pending = 0;
-    c.coc_defer = 0; c.qdefer = 0; c.scan_labels = nullptr;
-    for (int i = 0; i < 3; i++) { c.ts_pvt[i] = 0; m->tsp_pvt[i] = 0; c.pp_pvt[i] = c.pp_upvt[i] = 0; }
+    c.scan_labels = nullptr;
     c.ucol = gie_dalloc<uint8_t>(m, (((size_t)X * Y * ((Z + 7) / 8)) + 3) & ~(size_t)3);
     c.zocc = gie_dalloc<uint8_t>(m, (size_t)c.Z);
     c.zneed = gie_dalloc<uint64_t>(m, (size_t)c.tfd[0] * c.tfd[1]);
@@ -262,7 +275,6 @@ extern "C" gie_mapper *gie_create(const gie_config *cfg)
     c.wb_flag[1] = c.wb_flag[0] ? c.wb_flag[0] + mb : nullptr;
     c.g_wl = gie_dalloc<int32_t>(m, GV, false);
     c.g_dirty = gie_dalloc<int32_t>(m, (size_t)mb);
-    c.track = 0;
     long long qab = 16ll * bdr; if (qab < 65536) qab = 65536; if (qab > (16 << 20)) qab = 16 << 20;
     long long qc = (long long)c.N; if (qc < 4096) qc = 4096; if (qc > (16 << 20)) qc = 16 << 20;
     c.qcap_ab = (int)qab; c.qcap_c = (int)qc;
@@ -292,6 +304,7 @@ extern "C" gie_mapper *gie_create(const gie_config *cfg)
         }
     }
     gie_place_calibrate(m, N, GV);
+    gie_pp_init(m);
     be_memset(&m->be, c.hkeys, 0xff, (size_t)hcap * sizeof(uint64_t));
     be_memset(&m->be, c.lprop, 0xff, (size_t)bdr * sizeof(uint64_t));
     be_memset(&m->be, c.cand[0], 0xff, N * sizeof(uint64_t));
@@ -347,8 +360,7 @@ extern "C" int gie_set_pose(gie_mapper *m, const float pos[3], const float q[4])
     }
     c.wr_inside = 1;
     for (int i = 0; i < 3; i++) if (c.pvt[i] - c.upvt[i] < 0 || c.pvt[i] - c.upvt[i] + sz[i] > c.wr[i]) c.wr_inside = 0;
-    c.lazy_ok = c.wr_inside;                              /* "lazy pairs": not for one tile of several (its faces lie inside the whole volume: the refinement rounds read them) */
-    for (int i = 0; i < 3; i++) if (m->next_off[i] != 0 || m->next_whole[i] != sz[i]) c.lazy_ok = 0;
+    gie_pp_pose(m);
     c.tab_prev = nullptr;                                 /* the block table belongs to the pose before: the next gie_fuse builds this one's (from it) */
     const uint32_t f = (uint32_t)c.map_ct & 0x3ffffu;
     if (f == 0) {                                         /* stamp wrap: clear the stamp planes once */
@@ -560,8 +572,7 @@ extern "C" int gie_set_ext_boxes(gie_mapper *m, const float *ll, const float *ur
 static void gie_table_roll(gie_mapper *m)
 {
     gie_ctx &c = m->c;
-    static const int no_prev = GIE_SWITCH("GIE_NO_TAB_PREV", 0);      /* (debugging: every block through the hash) */
-    if (m->tab_valid && !no_prev) {
+    if (m->tab_valid) {
         c.tab_prev = c.blk_tab;
         for (int i = 0; i < 3; i++) c.tab_prev_d[i] = c.tb0[i] - m->tab_tb0[i];
         int32_t *t = c.blk_tab; c.blk_tab = m->blk_tab2; m->blk_tab2 = t;
@@ -570,19 +581,39 @@ static void gie_table_roll(gie_mapper *m)
     m->tab_valid = 1;
 }
 
-/* the stored pairs the last (fused) merge left out, for the voxels of ITS volume that the volume of the current pose no longer
- * holds (gie_pair_flush_voxel): the functor + how many voxels it covers.  rehash: types and block table on the device are no longer
- * that merge's — blocks are found through the hash and a record that has been flushed before (no mark) is left alone. */
-static int gie_flush_op(gie_mapper *m, op_pair_flush *out, int rehash)
+/* ---- the pair plane's transitions (gie_pair_state above) */
+static void gie_cp3(int d[3], const int s[3]) { d[0] = s[0]; d[1] = s[1]; d[2] = s[2]; }
+/* Mark and commit as one sweep (gie_ops.h "Mark + commit") unless the changed-block flags are on;
+ * GIE_FUSED=0 keeps the reference's order Mark -> obtainFrontiers -> waves -> commit (tests run both) */
+static int gie_fused_mode(const gie_mapper *m) { static const int env = GIE_SWITCH("GIE_FUSED", 1); return (env && !m->c.track) ? 1 : 0; }
+static int gie_pp_set_fused(gie_mapper *m) { return m->c.fused = gie_fused_mode(m); }
+extern "C" int gie_stream_enable(gie_mapper *m, int on)
+{
+    if (!m) { gie_set_err("gie_stream_enable: null handle"); return GIE_ERR_INVALID; }
+    m->pp.track_want = on ? 1 : 0; return GIE_OK;       /* (from the next gie_fuse on: include/gie.h) */
+}
+/* gie_create, once the planes are placed (gie_place_calibrate may replace c.bcoc); no tile is flagged lazy yet */
+static void gie_pp_init(gie_mapper *m) { m->c.bcoc_lazy = m->c.bcoc; }
+/* gie_set_pose: this pose's sweep may leave pairs out if the volume lies inside the wave range and is not one tile of several (its
+ * faces lie inside the whole volume: the refinement rounds read them) */
+static void gie_pp_pose(gie_mapper *m)
+{
+    m->c.lazy_ok = m->c.wr_inside;
+    for (int i = 0; i < 3; i++) if (m->next_off[i] != 0 || m->next_whole[i] != m->cfg.local_size[i]) m->c.lazy_ok = 0;
+}
+/* types or block table of the last fused merge are replaced (a gie_fuse, a table roll for ghosts) */
+static void gie_pp_replaced(gie_mapper *m) { if (m->pp.owed == GIE_OWED_FRESH) m->pp.owed = GIE_OWED_STALE; }
+/* the stored pairs the last fused merge owes to the voxels of ITS volume that the volume of the current pose no longer holds
+ * (gie_pair_flush_voxel): the functor + how many voxels it covers */
+static int gie_flush_op(const gie_mapper *m, op_pair_flush *out)
 {
     const gie_ctx &c = m->c;
-    op_pair_flush op;
-    op.b.rehash = rehash;
-    const int sz[3] = { c.X, c.Y, c.Z };
-    int w[3];
+    op_pair_flush &op = *out;
+    op.b.rehash = m->pp.owed == GIE_OWED_STALE;
+    gie_cp3(op.b.opvt, m->pp.last.pvt); gie_cp3(op.b.oupvt, m->pp.last.upvt); gie_cp3(op.b.otb0, m->pp.last.tb0);
+    const int sz[3] = { c.X, c.Y, c.Z }; int w[3];
     for (int i = 0; i < 3; i++) {
-        op.b.opvt[i] = m->commit_pvt[i]; op.b.oupvt[i] = m->commit_upvt[i]; op.b.otb0[i] = m->commit_tb0[i];
-        const long long s = (long long)m->commit_pvt[i] - c.pvt[i];          /* old local + s = new local */
+        const long long s = (long long)m->pp.last.pvt[i] - c.pvt[i];         /* old local + s = new local */
         long long lo = -s > 0 ? -s : 0, hi = sz[i] - s < sz[i] ? sz[i] - s : sz[i];
         if (hi < lo) hi = lo;
         if (lo > sz[i]) { lo = sz[i]; hi = sz[i]; }
@@ -590,111 +621,175 @@ static int gie_flush_op(gie_mapper *m, op_pair_flush *out, int rehash)
     }
     if (w[0] == 0 || w[1] == 0 || w[2] == 0) { for (int i = 0; i < 3; i++) { op.b.lo[i] = op.b.hi[i] = 0; w[i] = 0; } }   /* nothing stays */
     op.b.n0 = (c.X - w[0]) * c.Y * c.Z; op.b.n1 = w[0] * (c.Y - w[1]) * c.Z; op.b.n2 = w[0] * w[1] * (c.Z - w[2]);
-    *out = op;
     return op.b.n0 + op.b.n1 + op.b.n2;
 }
-
-static int gie_fused_mode(const gie_mapper *m);
-
-static int gie_fused_mode(const gie_mapper *m);
+/* every record still left to the pair plane, now: before something reads or writes stored records of voxels inside the volume out of
+ * turn — the reference's order of kernels, ghosts imported ahead of a pose's gie_fuse */
+static void gie_catchup_everything(gie_mapper *m)
+{
+    if (!m->pp.coc_pending) return;
+    gie_ctx &c = m->c;
+    gie_catchup p; p.flags = c.tskip; p.all = 1;
+    gie_cp3(p.fpvt, c.ts_pvt); gie_cp3(p.ppvt, c.pp_pvt); gie_cp3(p.pupvt, c.pp_upvt);
+    be_coc_catchup(&m->be, c, p);
+    m->pp.coc_pending = c.qdefer = 0;
+}
+/* gie_fuse, first: this update's order of kernels is settled, and the pairs owed to voxels no longer in the volume are written before
+ * that merge's types, pairs and table are overwritten and blocks erased; fuses without a merge in between each flush what
+ * has left that LAST merge's volume by now (a record flushed before has lost its mark).  Returns the voxels the frame clear is to flush. */
+static int gie_pp_fuse_begin(gie_mapper *m, op_pair_flush *op)
+{
+    m->c.track = m->pp.track_want; m->pp.fuse_fresh = 1;
+    if (m->pp.owed == GIE_OWED_NONE) return 0;
+    const int n = gie_flush_op(m, op);
+    if (m->c.retain == 0) return n;
+    be_lin(&m->be, m->c, *op, n);                     /* (before blocks are erased) */
+    return 0;
+}
+/* gie_fuse, before the frame clear: this update's tile planes become the _prev ones; they describe the update before (at prev_shift,
+ * tskip_prev flagged at its pose) if that was the last fused merge and nothing has replaced its types since */
+static void gie_pp_fuse_rotate(gie_mapper *m)
+{
+    gie_ctx &c = m->c;
+    std::swap(c.tmax, c.tmax_prev); std::swap(c.tskip, c.tskip_prev);
+    c.prev_valid = c.skip2_ok = m->pp.owed == GIE_OWED_FRESH;
+    for (int i = 0; i < 3; i++) { c.prev_shift[i] = c.pvt[i] - m->pp.last.pvt[i]; if (c.ts_pvt[i] != m->pp.last.pvt[i]) c.skip2_ok = 0; }
+    gie_cp3(m->pp.tsp_pvt, c.ts_pvt); gie_cp3(c.ts_pvt, c.pvt);
+    c.qdefer = 0;                     /* (until the flags are final: no query can come in between) */
+}
+/* gie_fuse, behind the fusion (the types are known): the tiles whose stored records this update's Mark need not read (gie_tile_oldskip:
+ * the previous update's bounds and this pose; not for ray-cast scans, which never clear a tile), the records the previous update left
+ * to its pair plane for tiles that are not among them any more, and the pairs of the lazy tiles the coming sweep will not flag again
+ * (the next Mark reads old pairs by local index).  A merge in the reference's order after all catches up the rest (gie_pp_mark_begin). */
+static void gie_pp_fuse_end(gie_mapper *m)
+{
+    gie_ctx &c = m->c; gie_pair_state &s = m->pp;
+    c.oldskip = (gie_fused_mode(m) && c.prev_valid && !c.pntcld_mode) ? 1 : 0;
+    /* usually tskip_prev is the update before's, at its pose: the launch that flags this update's tiles finds the ones to catch up on
+     * the way; otherwise the flags' own plane is walked — after a fuse WITHOUT a merge (whose sweep never ran) every flagged tile */
+    c.catchup_fast = (s.coc_pending && c.oldskip && c.skip2_ok) ? 1 : 0;
+    if (c.oldskip) be_tile_oldskip(&m->be, c, s.last.upvt);
+    if (s.coc_pending && !c.catchup_fast) {
+        gie_catchup p; p.flags = c.tskip_prev; p.all = s.owed == GIE_OWED_STALE;
+        gie_cp3(p.fpvt, s.tsp_pvt); gie_cp3(p.ppvt, s.last.pvt); gie_cp3(p.pupvt, s.last.upvt);
+        be_coc_catchup(&m->be, c, p);
+    }
+    s.coc_pending = s.coc_pending && c.oldskip;      /* what stays deferred lies in this update's tskip tiles */
+    if (s.lazy_pending) {
+        s.lazy_pending = (gie_fused_mode(m) && c.oldskip && c.lazy_ok) ? 1 : 0;     /* (what the sweep's short way goes by: tskip 2, records deferred) */
+        be_pair_materialise(&m->be, c, s.lazy_pending);
+    }
+    c.qdefer = s.coc_pending;
+    gie_cp3(c.pp_pvt, s.last.pvt); gie_cp3(c.pp_upvt, s.last.upvt);
+    gie_pp_replaced(m);
+}
+/* gie_merge_begin, before Mark: the fused sweep leaves tskip tiles' records to the pair plane (a tile of several too: gie_deferred_coc);
+ * the reference's order reads every stored record, so what is owed is written first.  Lazy pairs are THIS update's from this Mark on. */
+static void gie_pp_mark_begin(gie_mapper *m)
+{
+    gie_ctx &c = m->c;
+    m->pp.fuse_fresh = 0;
+    gie_pp_set_fused(m);
+    c.coc_defer = (c.fused && c.oldskip) ? 1 : 0;
+    if (!c.fused) gie_catchup_everything(m);
+    c.bcoc_lazy = c.bcoc; gie_cp3(c.pp_pvt, c.pvt); gie_cp3(c.pp_upvt, c.upvt);
+    if (c.coc_defer && c.lazy_ok) m->pp.lazy_pending = 1;
+}
+/* ... after Mark: the pair plane is THIS update's — what the fused sweep left to it, or nothing (the reference's order: its commit
+ * stores every pair, also the ones an earlier fused update left out) */
+static void gie_pp_mark_end(gie_mapper *m)
+{
+    gie_ctx &c = m->c;
+    m->pp.owed = c.fused ? GIE_OWED_FRESH : GIE_OWED_NONE;
+    if (c.fused) { gie_cp3(m->pp.last.pvt, c.pvt); gie_cp3(m->pp.last.upvt, c.upvt); gie_cp3(m->pp.last.tb0, c.tb0); }
+    m->pp.coc_pending = c.qdefer = c.coc_defer;
+}
+/* gie_batch_edt: pass Z writes the batch-obstacle plane the lazy pairs are not derived from */
+static void gie_pp_edt_plane(gie_mapper *m) { if (m->c.bcoc == m->c.bcoc_lazy) std::swap(m->c.bcoc, m->pp.bcoc_alt); }
+/* ahead of a ghost import (possibly before this pose's gie_fuse: ADVICE r4): every record left to the pair plane is stored (a ghost
+ * may land on a voxel of a tskip tile), and the pairs owed to the voxels that have left the last fused merge's volume are written as
+ * gie_fuse would — ghosts land just outside the NEW volume, on exactly those voxels, and a later flush would overwrite them */
+static void gie_pp_before_import(gie_mapper *m)
+{
+    gie_ctx &c = m->c; gie_pair_state &s = m->pp;
+    gie_catchup_everything(m);
+    if (s.owed == GIE_OWED_NONE || s.flushed_ct == c.map_ct || (s.last.pvt[0] == c.pvt[0] && s.last.pvt[1] == c.pvt[1] && s.last.pvt[2] == c.pvt[2])) return;
+    op_pair_flush op; const int n = gie_flush_op(m, &op);
+    be_lin(&m->be, c, op, n);
+    s.flushed_ct = c.map_ct; s.owed = GIE_OWED_STALE;        /* (gie_fuse's own flush goes by the marks) */
+}
 
 /* ---- stages */
+/* block-pool lifecycle (gie_config.retain_radius_blocks): erase what lies too far behind, before anything is allocated; every
+ * GIE_REHASH_PERIOD-th map update the hash table is rebuilt from the live slots, which drops the tombstones */
+static void gie_retain_blocks(gie_mapper *m)
+{
+    gie_ctx &c = m->c;
+    if (c.retain == 0) return;
+    be_lin(&m->be, c, op_evict(), c.max_blocks);
+    /* how many hash cells this erasure can have turned into tombstones: every live block lay inside the retention box of the update before
+     * (what was farther was erased then, blocks are only allocated inside the volume's box), so at most the block coordinates of that box
+     * that are not in this update's.  The host never reads the device's count; the bound decides when the table is rebuilt — a robot that
+     * jumps to new ground every update would otherwise use up the EMPTY cells (lookups end at one) long before the period is over */
+    long long vol_prev = m->retain_box_valid ? 1 : 0, vol_both = m->retain_box_valid ? 1 : 0;
+    for (int i = 0; i < 3; i++) {
+        const long long lo = (long long)c.vb_lo[i] - c.retain, hi = (long long)c.vb_hi[i] + c.retain;
+        if (m->retain_box_valid) {
+            vol_prev *= (long long)m->retain_box_hi[i] - m->retain_box_lo[i] + 1;
+            const long long a = lo > m->retain_box_lo[i] ? lo : m->retain_box_lo[i], b = hi < m->retain_box_hi[i] ? hi : m->retain_box_hi[i];
+            vol_both *= b >= a ? b - a + 1 : 0;
+        }
+        m->retain_box_lo[i] = (int)lo; m->retain_box_hi[i] = (int)hi;
+    }
+    m->retain_box_valid = 1;
+    const long long gone = vol_prev - vol_both;
+    m->tomb_bound += gone > c.max_blocks ? c.max_blocks : gone;
+    if (++m->evictions >= GIE_REHASH_PERIOD || m->tomb_bound > ((long long)c.hmask + 1) / 4) {
+        m->evictions = 0; m->tomb_bound = 0;
+        be_memset(&m->be, c.hkeys, 0xff, ((size_t)c.hmask + 1) * sizeof(uint64_t));
+        be_lin(&m->be, c, op_rehash(), c.max_blocks);
+    }
+}
+
+/* everything that has to be zero for this map update, in one launch with the pair flush (nflush voxels; it touches none of these arrays).
+ * tknown_prev tells which tiles still hold stale _glb_type; the ray-touch flags were consumed by the OGM stage, cleared for the next scan */
+static void gie_frame_clear(gie_mapper *m, const op_pair_flush &flush, int nflush)
+{
+    gie_ctx &c = m->c;
+    const size_t ntile = (size_t)c.tfd[0] * c.tfd[1] * c.tfd[2];
+    std::swap(c.tknown, c.tknown_prev);
+    gie_clear_list l; l.n = 0;
+    auto add = [&l](void *p, size_t bytes) { l.p[l.n] = p; l.bytes[l.n] = (uint32_t)bytes; l.n++; };
+    add(c.tflag, 5 * ntile);                                   /* tflag | tunk | tsum | tray | tact */
+    add(c.tknown, ntile);
+    add(c.zocc, (size_t)c.Z);
+    add(c.zredo, (size_t)((c.X + 15) / 16) * c.Y * sizeof(uint32_t));
+    add(c.tmax, ntile * sizeof(int32_t));
+    add(c.tbmax, ntile * sizeof(int32_t));
+    add(c.tskip, ntile);
+    add(c.cnt, GIE_CNT_ERR * sizeof(int32_t));                 /* per-frame counters (the sticky error flag survives) */
+    add(c.cnt + GIE_CNT_ERR + 1, (GIE_CNT_FRAME_END - GIE_CNT_ERR - 1) * sizeof(int32_t));
+    add(c.cnt + GIE_CNT_BAR_B, (GIE_CNT_AUX_END - GIE_CNT_BAR_B) * sizeof(int32_t));
+    add(c.lvl_next, 6 * GIE_MAX_LEVELS * sizeof(int32_t));    /* waves C, B and A */
+    add(c.wc_flag[0], 2 * ntile * sizeof(int32_t));          /* (zero again after every complete wave C; a wave cut short may leave flags) */
+    if (!c.fast_mode) add(c.wb_flag[0], 2 * (size_t)c.max_blocks * sizeof(int32_t));      /* (likewise for wave B) */
+    if (nflush > 0) be_flush_clear(&m->be, c, flush, nflush, l); else be_clear(&m->be, l);
+}
 extern "C" int gie_fuse(gie_mapper *m)
 {
     int rc = gie_need_pose(m, "gie_fuse"); if (rc) return rc;
     if (!m->has_ogm) { gie_set_err("gie_fuse: no scan has been fed since the last fuse (call gie_ogm_* first)"); return GIE_ERR_INVALID; }
     m->has_ogm = 0;
     m->ogm_unlabelled = 0;                /* fuse consumes the scan */
-    m->c.track = m->track_want;           /* the order of kernels of this update — fused sweep or the reference's, with the changed-block flags — is settled here */
-    const int unmerged = m->deferred && !m->flush_tab_ok;   /* types and block table are no longer those of the last fused merge: a gie_fuse
-                                                              without a merge came in between (the staged ABI allows it) */
-    m->fuse_fresh = 1;
     be_time(&m->be, 2);
-    /* allocHashTB (glb_hash_map.cu:58-113): flag missing blocks, rank them with an exclusive
-     * scan, insert + initialise, then resolve the frame's block table */
+    /* allocHashTB (glb_hash_map.cu:58-113): flag missing blocks, rank them with a scan, insert + initialise, resolve the frame's block table,
+     * and list the tiles fuse has to look at (a block overlaps them, or they hold old types); kernels walk lists or sweep (gie_use_lists) */
     be_prof(&m->be, GIE_K_ALLOC, 0);
-    const int was_fused = m->deferred && !unmerged;    /* the map update before this one ran fused, and it was the one before */
-    int nflush = 0;
-    op_pair_flush flush_op;
-    if (m->deferred) {
-        /* the stored pairs the last (fused) merge left out, for the voxels that are not in this volume any more; before
-         * anything of that update — types, pairs, block table — is overwritten, and before blocks are erased.
-         * `deferred` stays set until the next merge: when fuses follow each other without one, every one of them
-         * flushes what has left the volume of that LAST MERGE by now — the local pair plane is still that merge's — finding
-         * the blocks through the hash (types and block table are the un-merged fuse's by then); a record flushed before has
-         * lost its mark and is left alone. */
-        const gie_ctx &c = m->c;
-        op_pair_flush op;
-        nflush = gie_flush_op(m, &op, unmerged);
-        flush_op = op;
-        if (m->c.retain > 0) { be_lin(&m->be, c, op, nflush); nflush = 0; }      /* before blocks are erased; otherwise it shares the frame clear's launch below */
-    }
-    if (m->c.retain > 0) {
-        /* block-pool lifecycle (gie_config.retain_radius_blocks): erase what lies too far behind, before anything is allocated;
-         * every GIE_REHASH_PERIOD-th map update the hash table is rebuilt from the live slots, which drops the tombstones */
-        be_lin(&m->be, m->c, op_evict(), m->c.max_blocks);
-        {   /* how many hash cells this erasure can have turned into tombstones: every live block lay inside the retention box of
-             * the update before (what was farther was erased then, and blocks are only allocated inside the volume's box), so at
-             * most the block coordinates of that box that are not in this update's.  The host never reads the device's count;
-             * the bound decides when the table is rebuilt — a robot that jumps to new ground every update would otherwise use
-             * up the table's EMPTY cells (lookups end at one) long before the period is over */
-            long long vol_prev = m->retain_box_valid ? 1 : 0, vol_both = m->retain_box_valid ? 1 : 0;
-            for (int i = 0; i < 3; i++) {
-                const long long lo = (long long)m->c.vb_lo[i] - m->c.retain, hi = (long long)m->c.vb_hi[i] + m->c.retain;
-                if (m->retain_box_valid) {
-                    vol_prev *= (long long)m->retain_box_hi[i] - m->retain_box_lo[i] + 1;
-                    const long long a = lo > m->retain_box_lo[i] ? lo : m->retain_box_lo[i], b = hi < m->retain_box_hi[i] ? hi : m->retain_box_hi[i];
-                    vol_both *= b >= a ? b - a + 1 : 0;
-                }
-                m->retain_box_lo[i] = (int)lo; m->retain_box_hi[i] = (int)hi;
-            }
-            m->retain_box_valid = 1;
-            long long gone = vol_prev - vol_both;
-            if (gone > m->c.max_blocks) gone = m->c.max_blocks;
-            m->tomb_bound += gone;
-        }
-        if (++m->evictions >= GIE_REHASH_PERIOD || m->tomb_bound > ((long long)m->c.hmask + 1) / 4) {
-            m->evictions = 0; m->tomb_bound = 0;
-            be_memset(&m->be, m->c.hkeys, 0xff, ((size_t)m->c.hmask + 1) * sizeof(uint64_t));
-            be_lin(&m->be, m->c, op_rehash(), m->c.max_blocks);
-        }
-    }
-    {   /* everything that has to be zero for this map update, in one launch.  Per-tile summaries:
-         * last frame's "known" flags (tknown_prev) tell which tiles still hold stale _glb_type; the
-         * ray-touch flags were consumed by the OGM stage and are cleared for the next scan. */
-        gie_ctx &c = m->c;
-        const size_t ntile = (size_t)c.tfd[0] * c.tfd[1] * c.tfd[2];
-        uint8_t *t = c.tknown; c.tknown = c.tknown_prev; c.tknown_prev = t;
-        {   /* the bounds of what the previous map update committed per tile (gie_tile_oldskip): valid when that update ran fused */
-            int32_t *tm = c.tmax; c.tmax = c.tmax_prev; c.tmax_prev = tm;
-            c.prev_valid = was_fused;
-            for (int i = 0; i < 3; i++) c.prev_shift[i] = c.pvt[i] - m->commit_pvt[i];
-            uint8_t *ts = c.tskip; c.tskip = c.tskip_prev; c.tskip_prev = ts;          /* (cleared below; flagged again behind the occupancy fusion) */
-            c.skip2_ok = was_fused;       /* (... and tskip_prev is that update's: flagged at its pose, which is the merge's) */
-            for (int i = 0; i < 3; i++) { if (c.ts_pvt[i] != m->commit_pvt[i]) c.skip2_ok = 0; m->tsp_pvt[i] = c.ts_pvt[i]; c.ts_pvt[i] = c.pvt[i]; }
-            c.qdefer = 0;                 /* (until the flags are final: host-side state, no query can come in between) */
-        }
-        gie_clear_list l; l.n = 0;
-        auto add = [&l](void *p, size_t bytes) { l.p[l.n] = p; l.bytes[l.n] = (uint32_t)bytes; l.n++; };
-        add(c.tflag, 5 * ntile);                                   /* tflag | tunk | tsum | tray | tact */
-        add(c.tknown, ntile);
-        add(c.zocc, (size_t)c.Z);
-        add(c.zredo, (size_t)((c.X + 15) / 16) * c.Y * sizeof(uint32_t));
-        add(c.tmax, ntile * sizeof(int32_t));
-        add(c.tbmax, ntile * sizeof(int32_t));
-        add(c.tskip, ntile);
-        add(c.cnt, GIE_CNT_ERR * sizeof(int32_t));                 /* per-frame counters (the sticky error flag survives) */
-        add(c.cnt + GIE_CNT_ERR + 1, (GIE_CNT_FRAME_END - GIE_CNT_ERR - 1) * sizeof(int32_t));
-        add(c.cnt + GIE_CNT_BAR_B, (GIE_CNT_AUX_END - GIE_CNT_BAR_B) * sizeof(int32_t));
-        add(c.lvl_next, 6 * GIE_MAX_LEVELS * sizeof(int32_t));    /* waves C, B and A */
-        add(c.wc_flag[0], 2 * ntile * sizeof(int32_t));          /* (zero again after every complete wave C; a wave cut short may leave flags) */
-        if (!c.fast_mode) add(c.wb_flag[0], 2 * (size_t)c.max_blocks * sizeof(int32_t));      /* (likewise for wave B) */
-        /* (the pair flush touches none of these arrays and none of the pointers swapped above: one launch for both) */
-        if (nflush > 0) be_flush_clear(&m->be, c, flush_op, nflush, l); else be_clear(&m->be, l);
-    }
-    /* + the tiles fuse has to look at (an existing block overlaps them, or they still hold types from
-     * earlier frames), listed in the block-initialisation launch; fuse, Mark, commit and pass Z walk their list or
-     * sweep the volume — each kernel decides from the length of its list (gie_use_lists) */
+    op_pair_flush flush;
+    const int nflush = gie_pp_fuse_begin(m, &flush);
+    gie_retain_blocks(m);
+    gie_pp_fuse_rotate(m);
+    gie_frame_clear(m, flush, nflush);
     gie_table_roll(m);
     be_block_alloc(&m->be, m->c, m->ncell, m->d_rank, 0, (int)((size_t)m->c.tfd[0] * m->c.tfd[1] * m->c.tfd[2]));
     m->c.tab_prev = m->c.blk_tab; m->c.tab_prev_d[0] = m->c.tab_prev_d[1] = m->c.tab_prev_d[2] = 0;     /* (a second allocation pass of this update — ghost layers — looks into this table first) */
@@ -703,72 +798,18 @@ extern "C" int gie_fuse(gie_mapper *m)
     be_fuse(&m->be, m->c, m->c.tl_front);
     be_prof(&m->be, GIE_K_FUSE, 1);
     m->labels_pending = nullptr; m->c.scan_labels = nullptr;      /* (a label plane left in place has been read) */
-    {   /* the tiles whose stored records this update's Mark need not read (gie_tile_oldskip: the previous update's bounds and this
-         * pose — and an obstacle somewhere in the volume, known now that the types are fused), then the records the previous update
-         * left to its pair plane for the tiles that are not among them any more (gie_ops.h "deferred records").  If the merge ends
-         * up running in the reference's order after all (gie_stream_enable in between), gie_merge_begin catches up the rest. */
-        gie_ctx &c = m->c;
-        static const int use_bound = GIE_SWITCH("GIE_MARKC_BOUND", 1);     /* 0: always read the stored records (measurements) */
-        /* (not for ray-cast scans: a scan observes well under 1 % of the volume, no tile is ever cleared — the launch would be 5 us of
-         * a 0.2 - 0.4 ms update for nothing) */
-        c.oldskip = (gie_fused_mode(m) && c.prev_valid && use_bound && !c.pntcld_mode) ? 1 : 0;
-        be_prof(&m->be, GIE_K_ALLOC, 0);
-        /* the usual case: tskip_prev is the update before's and lies at its pose (prev_shift) — the launch that flags this update's
-         * tiles finds the ones to bring up to date on the way; otherwise (a fuse without a merge since; no bound to go by) the
-         * tiles of the flags' own plane are enumerated (be_coc_catchup) */
-        c.catchup_fast = (m->coc_pending && c.oldskip && c.skip2_ok) ? 1 : 0;
-        if (c.oldskip) be_tile_oldskip(&m->be, c, m->commit_upvt);
-        if (m->coc_pending && !c.catchup_fast) {
-            gie_catchup p;
-            /* (after a fuse WITHOUT a merge the flags are that fuse's, whose sweep never ran: also its tiles flagged 1 — "the sweep stores
-             * them" — still hold voxels the merge before left to its pair plane: every flagged tile is caught up; round 6) */
-            p.flags = c.tskip_prev; p.all = unmerged ? 1 : 0;
-            for (int i = 0; i < 3; i++) { p.fpvt[i] = m->tsp_pvt[i]; p.ppvt[i] = m->commit_pvt[i]; p.pupvt[i] = m->commit_upvt[i]; }
-            be_coc_catchup(&m->be, c, p);
-        }
-        if (m->coc_pending) m->coc_pending = c.oldskip;       /* what stays deferred lies in this update's tskip tiles (none without the bound) */
-        /* "lazy pairs": the flagged tiles this update's sweep will not leave flagged again get their pairs into the plane now — the batch
-         * obstacles they are derived from are still there, and the next Mark reads old pairs by local index */
-        if (m->lazy_pending) {
-            const int stay = (gie_fused_mode(m) && c.oldskip && c.lazy_ok) ? 1 : 0;      /* (what the sweep's short way will go by: tskip 2, records deferred) */
-            be_pair_materialise(&m->be, c, stay);
-            m->lazy_pending = stay;
-        }
-        be_prof(&m->be, GIE_K_ALLOC, 1);
-        c.qdefer = m->coc_pending;
-        for (int i = 0; i < 3; i++) { c.pp_pvt[i] = m->commit_pvt[i]; c.pp_upvt[i] = m->commit_upvt[i]; }
-    }
+    be_prof(&m->be, GIE_K_ALLOC, 0);
+    gie_pp_fuse_end(m);
+    be_prof(&m->be, GIE_K_ALLOC, 1);
     be_time(&m->be, 3);
-    m->flush_tab_ok = 0;
     return GIE_OK;
-}
-
-/* Mark and commit as one sweep (gie_ops.h "Mark + commit") unless the changed-block flags are on;
- * GIE_FUSED=0 keeps the reference's order Mark -> obtainFrontiers -> waves -> commit (tests run both) */
-static int gie_fused_mode(const gie_mapper *m)
-{
-    static const int env = GIE_SWITCH("GIE_FUSED", 1);
-    return (env && !m->c.track) ? 1 : 0;
-}
-
-/* every record still left to the pair plane, now (gie_ops.h "deferred records"): before something reads or writes stored records of
- * voxels inside the volume out of turn — the reference's order of kernels, ghosts imported ahead of a pose's gie_fuse */
-static void gie_catchup_everything(gie_mapper *m)
-{
-    if (!m->coc_pending) return;
-    gie_ctx &c = m->c;
-    gie_catchup p;
-    p.flags = c.tskip; p.all = 1;
-    for (int i = 0; i < 3; i++) { p.fpvt[i] = c.ts_pvt[i]; p.ppvt[i] = c.pp_pvt[i]; p.pupvt[i] = c.pp_upvt[i]; }
-    be_coc_catchup(&m->be, c, p);
-    m->coc_pending = 0; c.qdefer = 0;
 }
 
 extern "C" int gie_batch_edt(gie_mapper *m)
 {
     int rc = gie_need_pose(m, "gie_batch_edt"); if (rc) return rc;
     be_time(&m->be, 4);
-    if (m->c.bcoc == m->c.bcoc_lazy) { uint32_t *t = m->c.bcoc; m->c.bcoc = m->bcoc_alt; m->bcoc_alt = t; }      /* ("lazy pairs": pass Z writes the OTHER plane) */
+    gie_pp_edt_plane(m);
     be_prof(&m->be, GIE_K_EDT_ZFACES, 0);
     be_edt_prep(&m->be, m->c);          /* plane list + reader masks (the tile skip flags are gie_fuse's since round 5) */
     be_prof(&m->be, GIE_K_EDT_ZFACES, 1);
@@ -786,33 +827,16 @@ extern "C" int gie_merge_begin(gie_mapper *m)
     int rc = gie_need_pose(m, "gie_merge"); if (rc) return rc;
     /* the seed counters, the barrier words of the waves and the per-round arrays are zeroed by gie_fuse's frame clear: a second
      * merge of the same map update would append to what the first one left */
-    if (!m->fuse_fresh) { gie_set_err("gie_merge: no gie_fuse since the last merge (one merge per map update)"); return GIE_ERR_INVALID; }
-    m->fuse_fresh = 0;
+    if (!m->pp.fuse_fresh) { gie_set_err("gie_merge: no gie_fuse since the last merge (one merge per map update)"); return GIE_ERR_INVALID; }
     be_time(&m->be, 6);
-    m->c.fused = gie_fused_mode(m);
-    const int kmark = m->c.fused ? GIE_K_MARKC : GIE_K_MARK;
+    const int kmark = gie_fused_mode(m) ? GIE_K_MARKC : GIE_K_MARK;
     be_prof(&m->be, kmark, 0);
-    /* (the tiles whose stored records need not be read — tskip — were flagged by gie_fuse) */
-    {   /* deferred records (gie_ops.h): a tskip tile's voxels are not stored by the fused sweep.  The reference's order of kernels reads
-         * every stored record: what is still owed to the tskip tiles is written first, while the pair plane is the previous update's. */
-        gie_ctx &c = m->c;
-        c.coc_defer = (c.fused && c.oldskip) ? 1 : 0;      /* (also for one tile of several: the face layers are exported through gie_deferred_coc) */
-        if (!c.fused) gie_catchup_everything(m);
-    }
-    /* "lazy pairs": from this Mark on the flagged tiles' pairs are the ones of THIS update's batch obstacles at THIS update's pivots */
-    m->c.bcoc_lazy = m->c.bcoc;
-    for (int i = 0; i < 3; i++) { m->c.pp_pvt[i] = m->c.pvt[i]; m->c.pp_upvt[i] = m->c.upvt[i]; }
-    if (m->c.fused && m->c.coc_defer && m->c.lazy_ok) m->lazy_pending = 1;
+    gie_pp_mark_begin(m);
     if (m->c.fused) be_markc(&m->be, m->c, m->c.tl_known);
     else be_vox_list<false>(&m->be, m->c, op_mark(), m->c.tl_known, GIE_CNT_TL_KNOWN, 0);
     be_prof(&m->be, kmark, 1);
     m->merge_open = 1;
-    if (m->c.fused) { m->deferred = 1; m->flush_tab_ok = 1; for (int i = 0; i < 3; i++) { m->commit_pvt[i] = m->c.pvt[i]; m->commit_upvt[i] = m->c.upvt[i]; m->commit_tb0[i] = m->c.tb0[i]; } }
-    else m->deferred = 0;     /* the reference's order: its commit sweep stores every pair, also the ones an earlier fused update left out (gie_commit_finish) */
-    /* from here on the pair plane is THIS update's: what the sweep left to it (coc_defer), or nothing (it stored every record it passed) */
-    m->coc_pending = m->c.coc_defer;
-    m->c.qdefer = m->coc_pending;
-    for (int i = 0; i < 3; i++) { m->c.pp_pvt[i] = m->c.pvt[i]; m->c.pp_upvt[i] = m->c.upvt[i]; }
+    gie_pp_mark_end(m);
     return GIE_OK;
 }
 /* second half: obtainFrontiers, waves A / B / C, commit */
@@ -1072,12 +1096,6 @@ static int gie_stream_chunk_blocks()
     return (v >= 1 && v <= GIE_STREAM_CHUNK) ? v : GIE_STREAM_CHUNK;
 }
 
-extern "C" int gie_stream_enable(gie_mapper *m, int on)
-{
-    if (!m) { gie_set_err("gie_stream_enable: null handle"); return GIE_ERR_INVALID; }
-    m->track_want = on ? 1 : 0;           /* (from the next gie_fuse on: include/gie.h) */
-    return GIE_OK;
-}
 extern "C" int gie_stream_changed(gie_mapper *m, int32_t *keys, gie_voxel *blocks, int max_blocks, int32_t *n_changed)
 {
     if (!m || max_blocks < 0) { gie_set_err("gie_stream_changed: bad arguments"); return GIE_ERR_INVALID; }
@@ -1142,34 +1160,18 @@ extern "C" int gie_get_pivot(gie_mapper *m, int32_t pvt[3])
 /* The halo entry points read and write the global map through the frame's block table (gie_gvox_tab) and the ABI only asks them
  * for a pose — so they may run between gie_set_pose and that pose's gie_fuse, when the table on the device is still the previous
  * pose's (the ghost-block pass then left a table the next gie_fuse misread; and an export read the cells of the new
- * origin out of the old table).  Before any of them touches the map:
- *  - the stored pairs the last fused merge still owes to the voxels that have left its volume are written (as gie_fuse would):
- *    ghosts land just outside the NEW volume, on exactly those voxels, and a flush after the import would overwrite them;
- *    gie_fuse's own flush then goes by the marks (rehash form);
- *  - the block table is rebuilt at this pose's origin (the allocation pass of gie_fuse, nothing flagged but what a scan of this
- *    pose has observed so far). */
-static void gie_owed_pairs_before_import(gie_mapper *m)
-{
-    gie_ctx &c = m->c;
-    gie_catchup_everything(m);            /* (the records of tskip tiles too: a ghost may land on one of their voxels) */
-    if (!m->deferred || m->flushed_ct == c.map_ct) return;
-    if (m->commit_pvt[0] == c.pvt[0] && m->commit_pvt[1] == c.pvt[1] && m->commit_pvt[2] == c.pvt[2]) return;
-    op_pair_flush op;
-    const int n = gie_flush_op(m, &op, m->flush_tab_ok ? 0 : 1);
-    be_lin(&m->be, c, op, n);
-    m->flushed_ct = c.map_ct;
-    m->flush_tab_ok = 0;
-}
+ * origin out of the old table).  Before any of them touches the map, the pair plane's debts are paid (gie_pp_before_import) and
+ * the block table is rebuilt at this pose's origin (the allocation pass of gie_fuse, nothing flagged but what a scan of this pose has
+ * observed so far). */
 static int gie_table_is_this_poses(const gie_mapper *m)
 { return m->tab_valid && m->tab_tb0[0] == m->c.tb0[0] && m->tab_tb0[1] == m->c.tb0[1] && m->tab_tb0[2] == m->c.tb0[2]; }
 /* ghost voxels need their blocks: the allocation pass of gie_fuse again, over every cell of the block table */
 static void gie_ghost_block_alloc(gie_mapper *m)
 {
-    gie_ctx &c = m->c;
-    gie_owed_pairs_before_import(m);
-    if (!gie_table_is_this_poses(m)) { gie_table_roll(m); m->flush_tab_ok = 0; }      /* (the table of the last fused merge is the OTHER one now) */
-    be_block_alloc(&m->be, c, m->ncell, m->d_rank, 1);
-    c.tab_prev = c.blk_tab; c.tab_prev_d[0] = c.tab_prev_d[1] = c.tab_prev_d[2] = 0;
+    gie_pp_before_import(m);
+    if (!gie_table_is_this_poses(m)) { gie_table_roll(m); gie_pp_replaced(m); }      /* (the table of the last fused merge is the OTHER one now) */
+    be_block_alloc(&m->be, m->c, m->ncell, m->d_rank, 1);
+    m->c.tab_prev = m->c.blk_tab; m->c.tab_prev_d[0] = m->c.tab_prev_d[1] = m->c.tab_prev_d[2] = 0;
 }
 static void gie_table_for_pose(gie_mapper *m)
 {
@@ -1334,7 +1336,7 @@ extern "C" int gie_refine(gie_mapper *m, int32_t *seeded)
     }
     const int nb = 2 * (c.X * c.Y + c.Y * c.Z + c.X * c.Z);
     be_lin(&m->be, c, op_refine(), nb);
-    c.fused = gie_fused_mode(m);
+    gie_pp_set_fused(m);
     be_waves(&m->be, c, 0, 0, 0);                        /* (its own clear above) */
     if (!c.fused) be_vox_list<true>(&m->be, c, op_commit(), c.tl_known, GIE_CNT_TL_KNOWN, 0);   /* fused: wave C has committed what it merged */
     if (!seeded) return GIE_OK;          /* enqueue only: a fixed number of exchange rounds needs no answer */

@@ -118,14 +118,12 @@ typedef struct gie_ctx {
     const int8_t *scan_labels; /* non-null: the scan is a label plane the caller (or the library's staging buffer) still holds — gie_ogm_labels_dev
                              * has only flagged its blocks — and gie_fuse reads the labels from there: `_inst_type` is neither written nor reset */
     int wr_inside;          /* every voxel of the local volume lies inside the wave range (always, unless a tile offset pushes the volume out of it) */
+    /* (oldskip, ts_pvt above and the scalars from here to prev_shift: the pair plane's state, set by gie_api.inc.h's gie_pp_* transitions only) */
     int skip2_ok;           /* tskip_prev describes the tiles of the update right before this one, at the pose prev_shift refers to: a tile may be flagged 2 */
     int catchup_fast;       /* gie_tile_oldskip also says which tiles of this update need their deferred records stored (tskip_prev is the update before's, at prev_shift) */
     int coc_defer;          /* Mark + commit leaves the stored obstacle of skip tiles' voxels unwritten this update (gie_ops.h "deferred records") */
-    /* LAZY PAIRS (round 6, gie_ops.h "lazy pairs"): in a tile the sweep's short way handles (tskip 2, records deferred, volume inside the wave
-     * range) the pair of a voxel is a function of its batch obstacle, and the sweep does not store it: the tile is flagged, readers derive */
-    uint8_t *tlazy;         /* per tile: the pairs of the tile's voxels are NOT in the pair plane: they are gie_pair_of_bcoc(bcoc_lazy[id]) at pivots pp_pvt / pp_upvt.
-                             * ONE plane, never swapped or cleared with the frame: it says what the pair plane holds NOW (set by the sweep, taken away by whoever
-                             * writes the tile's pairs) */
+    uint8_t *tlazy;         /* LAZY PAIRS (gie_ops.h): per tile, its voxels' pairs are NOT in the pair plane but gie_pair_of_bcoc(bcoc_lazy[id]) at pivots pp_pvt / pp_upvt.
+                             * ONE plane, never swapped or cleared with the frame: what the pair plane holds NOW (set by the sweep, cleared by whoever writes the pairs) */
     const uint32_t *bcoc_lazy; /* the batch-obstacle plane the flags refer to (the one of the last merge; `bcoc` alternates between two planes) */
     int lazy_ok;            /* this update's sweep may leave pairs out: the volume lies inside the wave range and is not one tile of several */
     int qdefer;             /* readers of single global voxels (gie_query_global*): a voxel of a tskip tile has its record in the pair plane ... */
