@@ -352,25 +352,45 @@ template <int CP, int TX, int WAVES> static void gie_launch_edt_z(be_state *b, c
     int grid = wgs * b->cu_total; if (grid > (ntiles + 1) / 2) grid = (ntiles + 1) / 2;     /* tiles are taken in pairs */
     GIE_LAUNCH(b, (k_edt_z<CP, TX, WAVES>), dim3(grid), dim3(64 * WAVES), lds, c, ntx, ntiles, full);
 }
-template <int CP> static void gie_launch_edt_xz(be_state *b, const gie_ctx &c, bool zpass, int full)
+/* pass X (zpass false): `zs_fused` = the fused streaming form of pass Z may take the volume (be_zs_mode), when it does the launch
+ * returns at once; redo: only the rows of the slabs that form gave up (k_edt_x_redo) */
+template <int CP> static void gie_launch_edt_xz(be_state *b, const gie_ctx &c, bool zpass, int full, int zs_fused = 0, bool redo = false)
 {
-    if (!zpass) {
-        GIE_LAUNCH(b, k_edt_x<CP>, dim3((c.Y + GIE_EDTX_WAVES - 1) / GIE_EDTX_WAVES, c.Z), dim3(64 * GIE_EDTX_WAVES), 0, c);
+    if (redo) {
+        GIE_LAUNCH(b, k_edt_x_redo<CP>, dim3(b->cu_total * 8), dim3(64 * GIE_EDTX_WAVES), 0, c);
+    } else if (!zpass) {
+        GIE_LAUNCH(b, k_edt_x<CP>, dim3((c.Y + GIE_EDTX_WAVES - 1) / GIE_EDTX_WAVES, c.Z), dim3(64 * GIE_EDTX_WAVES), 0, c, zs_fused, full);
     } else {
         gie_launch_edt_z<CP, 16, 8>(b, c, full);      /* 2 workgroups per CU overlap load / envelope / store phases */
     }
 }
-static void gie_launch_edt_dim(be_state *b, const gie_ctx &c, int L, bool zpass, int full)
+static void gie_launch_edt_dim(be_state *b, const gie_ctx &c, int L, bool zpass, int full, int zs_fused = 0, bool redo = false)
 {
-    if (L <= 64) gie_launch_edt_xz<1>(b, c, zpass, full);
-    else if (L <= 128) gie_launch_edt_xz<2>(b, c, zpass, full);
-    else if (L <= 256) gie_launch_edt_xz<4>(b, c, zpass, full);
-    else if (L <= 512) gie_launch_edt_xz<8>(b, c, zpass, full);
-    else gie_launch_edt_xz<16>(b, c, zpass, full);
+    if (L <= 64) gie_launch_edt_xz<1>(b, c, zpass, full, zs_fused, redo);
+    else if (L <= 128) gie_launch_edt_xz<2>(b, c, zpass, full, zs_fused, redo);
+    else if (L <= 256) gie_launch_edt_xz<4>(b, c, zpass, full, zs_fused, redo);
+    else if (L <= 512) gie_launch_edt_xz<8>(b, c, zpass, full, zs_fused, redo);
+    else gie_launch_edt_xz<16>(b, c, zpass, full, zs_fused, redo);
 }
-/* pass Z again over the whole volume (the passes before it are complete either way) */
+/* the host half of "pass Z's streaming form takes the volume" (gie_zs_takes): 0 = never, 1 = it reads pass X's planes, 2 = the
+ * fused form, which reads pass Y's (X even; pass X is skipped when it takes the volume; GIE_ZS_FUSED=0 keeps the first for A/B runs) */
+static int be_zs_mode(const gie_ctx &c)
+{
+    if (c.Z < 64 || c.Z > 1024) return 0;          /* (short columns: the column kernel) */
+    static const int on = GIE_SWITCH("GIE_ZSTREAM", 1);
+    static const int fused = GIE_SWITCH("GIE_ZS_FUSED", 1);
+    return on ? ((fused && (c.X & 1) == 0) ? 2 : 1) : 0;     /* (the fused form loads its rows two columns to a dword) */
+}
+/* pass Z: the streaming form (if it takes the volume), pass X on the rows of the slabs it gave up (fused form: pass X did not
+ * run), the column kernel (the rest, or the repair of those slabs) */
 static int be_edt_z_stream(be_state *b, const gie_ctx &c, int full);
-static void be_edt_z(be_state *b, const gie_ctx &c, int full) { (void)be_edt_z_stream(b, c, full); gie_launch_edt_dim(b, c, c.Z, true, full); }
+static void be_edt_z_rest(be_state *b, const gie_ctx &c, int full, int zs)
+{
+    if (zs == 2) gie_launch_edt_dim(b, c, c.X, false, full, 0, true);
+    gie_launch_edt_dim(b, c, c.Z, true, full);
+}
+/* pass Z again over the whole volume (pass Y is complete, pass X where the streaming form does not take the volume) */
+static void be_edt_z(be_state *b, const gie_ctx &c, int full) { be_edt_z_rest(b, c, full, be_edt_z_stream(b, c, full) ? be_zs_mode(c) : 0); }
 /* EDT_OCC::batchEDTUpdate, local_edt.cu:7-28 */
 /* adaptive sweep (k_voxa): the kernel walks the list or sweeps the volume, whichever the list's
  * length calls for; staged = the functor's load1/load2/finish form; always_list = never sweep */
@@ -468,9 +488,8 @@ static void be_edt_z_direct(be_state *b, const gie_ctx &c)
 /* returns 1 when launched: the launch also carries the list form of the pass (k_edt_z_direct's body) when `full` is 0 */
 static int be_edt_z_stream(be_state *b, const gie_ctx &c, int full)
 {
-    if (c.Z < 64 || c.Z > 1024) return 0;          /* (short columns: the column kernel) */
-    static const int on = GIE_SWITCH("GIE_ZSTREAM", 1);
-    if (!on) return 0;
+    const int zs = be_zs_mode(c);
+    if (!zs) return 0;
     const int nxr = (c.X + 63) / 64;
     /* z segments so that the launch has about eight waves per SIMD to overlap its rows' round trips (a segment re-reads 16 planes) */
     static const int target = GIE_SWITCH("GIE_ZSTREAM_WAVES", 8);
@@ -485,7 +504,8 @@ static int be_edt_z_stream(be_state *b, const gie_ctx &c, int full)
     const long long cap = (long long)b->cu_total * 8 * 4;
     if (grid > cap) grid = cap;
     if (!full && grid < (long long)b->cu_total * 16) grid = (long long)b->cu_total * 16;      /* (the list form's grid: be_edt_z_direct) */
-    GIE_LAUNCH(b, k_edt_z_stream, dim3((unsigned)grid), dim3(256), 0, c, full, nseg, seg_len);
+    if (zs == 2) GIE_LAUNCH(b, k_edt_z_stream<true>, dim3((unsigned)grid), dim3(256), 0, c, full, nseg, seg_len, zs);
+    else GIE_LAUNCH(b, k_edt_z_stream<false>, dim3((unsigned)grid), dim3(256), 0, c, full, nseg, seg_len, zs);
     return 1;
 }
 /* tskip for this update; with c.catchup_fast the tiles whose deferred records have to be stored are listed and stored (pupvt: the
@@ -546,12 +566,14 @@ static void be_edt(be_state *b, const gie_ctx &c, int full)
     else if (c.Y <= 512) GIE_LAUNCH(b, (k_edt_y<16, 16>), gy, dim3(GIE_EDTY_COLS, 16), 0, c);
     else GIE_LAUNCH(b, (k_edt_y<32, 16>), gy, dim3(GIE_EDTY_COLS, 16), 0, c);
     be_prof(b, 6, 1);
-    be_prof(b, 7, 0); gie_launch_edt_dim(b, c, c.X, false, 1); be_prof(b, 7, 1);   /* GIE_K_EDT_X */
-    be_prof(b, 8, 0);                                                              /* GIE_K_EDT_Z */
+    const int zs = be_zs_mode(c);
+    be_prof(b, 7, 0); gie_launch_edt_dim(b, c, c.X, false, full, zs == 2 ? zs : 0); be_prof(b, 7, 1);   /* GIE_K_EDT_X */
+    be_prof(b, 8, 0);                                                                                  /* GIE_K_EDT_Z */
     /* dense fields: the streaming form does the whole pass and flags what it could not finish for the column kernel; few known
      * tiles: the list form — in the same launch */
-    if (!be_edt_z_stream(b, c, full) && !full) be_edt_z_direct(b, c);
-    gie_launch_edt_dim(b, c, c.Z, true, full);
+    const int zl = be_edt_z_stream(b, c, full);
+    if (!zl && !full) be_edt_z_direct(b, c);
+    be_edt_z_rest(b, c, full, zl ? zs : 0);
     be_prof(b, 8, 1);
 
 }

@@ -884,8 +884,15 @@ __device__ __forceinline__ int gie_row_compact_push(uint2 *ce, int base, const b
 #ifndef GIE_EDTX_WAVES
 #define GIE_EDTX_WAVES 4
 #endif
+/* pass Z's streaming form takes the volume (k_edt_z_stream below): `zs` = the host half (be_zs_mode: Z in [64, 1024], the switch),
+ * the rest is this update's, on the device — the list form is not called for and the planes with obstacles are many (k_edt_prep
+ * has counted both before pass X runs) */
+GIE_HD int gie_zs_takes(const gie_ctx &c, const int zs, const int full)
+{
+    return zs && !(full == 0 && gie_z_use_lists(c, c.cnt[GIE_CNT_TL_KNOWN])) && *c.zcount > GIE_BAND_MAXK;
+}
 template <int CP>
-__global__ __launch_bounds__(64 * GIE_EDTX_WAVES) void k_edt_x(const gie_ctx c)
+__device__ __forceinline__ void gie_edt_x_row(const gie_ctx &c, const int y, const int z)
 {
     constexpr int LP = 64 * CP;
     __shared__ __attribute__((aligned(16))) uint2 s_ce[GIE_EDTX_WAVES][LP];
@@ -895,10 +902,6 @@ __global__ __launch_bounds__(64 * GIE_EDTX_WAVES) void k_edt_x(const gie_ctx c)
     constexpr bool OVL = LP >= 2 * (GIE_BAND_MAXK + GIE_BAND_PAD) && LP / 2 >= GIE_BAND_MAXK;
     __shared__ __attribute__((aligned(16))) int2 s_mb[OVL ? 1 : GIE_EDTX_WAVES][OVL ? 1 : GIE_BAND_MAXK + GIE_BAND_PAD];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    /* grid = (rows of a plane / waves, planes): no division by a run-time size — most waves
-     * belong to a plane without obstacle and leave after one flag read, and an integer division
-     * was a quarter of all the instructions of the launch */
-    const int z = blockIdx.y, y = blockIdx.x * GIE_EDTX_WAVES + wave;
     if (!c.zocc[z]) return;                                     /* empty plane: pass Z does not read its cxy2 */
     if (y >= c.Y) return;
     const int X = c.X;
@@ -988,6 +991,42 @@ __global__ __launch_bounds__(64 * GIE_EDTX_WAVES) void k_edt_x(const gie_ctx c)
     } else {
 #pragma unroll
         for (int m = 0; m < CP; m++) if (u0 + m < X) out[u0 + m] = o[m];
+    }
+}
+/* zs: pass Z's fused streaming form may take the volume (be_zs_mode) — when it does (it reads pass Y's planes itself) this pass
+ * has nothing to do, and every workgroup leaves after the test (0.017 ms for the headline's 64 K workgroups: workgroups of 16 waves
+ * were measured no cheaper, and a grid-stride walk over the rows needs 123 VGPRs at CP = 8 against 44, so the grid stays this one) */
+template <int CP>
+__global__ __launch_bounds__(64 * GIE_EDTX_WAVES) void k_edt_x(const gie_ctx c, const int zs, const int full)
+{
+    if (zs && gie_zs_takes(c, zs, full)) return;
+    /* grid = (rows of a plane / waves, planes): no division by a run-time size — most waves
+     * belong to a plane without obstacle and leave after one flag read, and an integer division
+     * was a quarter of all the instructions of the launch */
+    gie_edt_x_row<CP>(c, blockIdx.x * GIE_EDTX_WAVES + (int)(threadIdx.x >> 6), blockIdx.y);
+}
+/* After the fused streaming form: pass X on the rows (y, every plane with obstacles) of the y values whose slabs it gave up
+ * (c.zredo) — the column kernel behind it reads them.  A grid-stride walk over (y, 8 planes with obstacles): nothing to do on
+ * most updates. */
+template <int CP>
+__global__ __launch_bounds__(64 * GIE_EDTX_WAVES) void k_edt_x_redo(const gie_ctx c)
+{
+    if (c.cnt[GIE_CNT_ZFAIL] == 0) return;
+    const int K = *c.zcount, Y = c.Y, lane = threadIdx.x & 63;
+    const int nw = (int)gridDim.x * GIE_EDTX_WAVES, w0 = (int)blockIdx.x * GIE_EDTX_WAVES + (int)(threadIdx.x >> 6);
+    const int ntx = (c.X + 15) >> 4, nkc = (K + 7) >> 3;
+#pragma unroll 1
+    for (int u = w0; u < Y * nkc; u += nw) {
+        const int uu = __builtin_amdgcn_readfirstlane(u);   /* (wave-uniform said outright: the row's addresses stay scalar) */
+        const int y = uu / nkc, k0 = (uu % nkc) * 8;
+        bool f = false;
+        for (int i = lane; i < ntx; i += 64) f |= c.zredo[(size_t)y * ntx + i] != 0u;
+        if (!__any(f)) continue;                            /* wave-uniform */
+#pragma unroll 1
+        for (int k = k0; k < min(k0 + 8, K); k++) {
+            gie_wave_sync();                                /* (the wave's site list is reused row after row) */
+            gie_edt_x_row<CP>(c, y, c.zlist[k]);
+        }
     }
 }
 
@@ -1266,6 +1305,68 @@ __device__ __forceinline__ uint32_t gie_zs_key(const uint32_t v, const bool plan
     const bool ok = plane_ok && max(ux, uy) <= 16u && a < (uint32_t)((GIE_ZS_R + 1) * (GIE_ZS_R + 1));
     return ok ? ((a << 24) | ((uint32_t)j << 18) | (ux << 13) | (uy << 8)) : (GIE_ZS_NONE | ((uint32_t)j << 18));
 }
+/* The FUSED form reads pass Y's planes (cy1) instead of pass X's: the only in-plane site the key above can hold lies within 8
+ * columns (an offset of 9 costs 81), so the key is the minimum over |dx| <= 8 of dx² + (y - cy1[x + dx])², ties to the smaller
+ * x — pass X's rule.  A wave's row of a plane is 64 + 16 columns (x0 - 8 .. x0 + 71), staged in LDS as column values
+ *     dy² (<= 64) << 24 | y offset + 8 << 8      or GIE_ZS_NONE (no site in the column, beyond 8 rows, outside the volume)
+ * y is the wave's, so a value is one per column; a lane adds (dx² << 24 | (23 + dx) << 13) for each of its 17 columns and takes
+ * the minimum: distance², then dx (the smaller x), then the column's y offset.  23 + dx = 31 - (x offset + 8): one xor turns the
+ * minimum into gie_zs_key's key. */
+#define GIE_ZS_XW (64 + 2 * GIE_ZS_R)
+#define GIE_ZS_ROWS 8                                     /* planes staged at a time */
+#ifndef GIE_ZS_CHAINS
+#define GIE_ZS_CHAINS 4                                   /* planes whose row reads are in flight together */
+#endif
+#ifndef GIE_ZS_FUSED_WGS
+#define GIE_ZS_FUSED_WGS 7                                /* workgroups per compute unit the fused form is built for (registers) */
+#endif
+__device__ __forceinline__ uint32_t gie_zs_col(const uint32_t cy, const bool ok, const int y8)
+{
+    const uint32_t uy = (uint32_t)(y8 - (int)cy);
+    const int dy = (int)uy - 8;
+    return (ok && uy <= 16u) ? (((uint32_t)__mul24(dy, dy) << 24) | (uy << 8)) : GIE_ZS_NONE;      /* (cy = 0xffff: uy wraps) */
+}
+typedef __attribute__((address_space(3))) uint32_t gie_lds_u32;     /* (LDS said outright: through a generic pointer the rows were read with 16-byte flat loads at 4-byte offsets) */
+__device__ __forceinline__ uint32_t gie_zs_fused_key(const gie_lds_u32 *row, const int j)
+{
+    uint32_t m = 0xffffffffu;
+#pragma unroll
+    for (int k = 0; k <= 2 * GIE_ZS_R; k++) m = min(m, row[k] + (((uint32_t)((k - GIE_ZS_R) * (k - GIE_ZS_R)) << 24) | ((uint32_t)(15 + k) << 13)));
+    return m < GIE_ZS_LIMIT ? ((m ^ (31u << 13)) | ((uint32_t)j << 18)) : (GIE_ZS_NONE | ((uint32_t)j << 18));
+}
+/* NP planes from zfirst on (clamped to the volume; pm bit j: plane zfirst + j holds obstacles) -> window places JB .. JB + NP - 1.
+ * Lane l < 40 loads the columns x0 - 8 + 2l and the one after as one dword (X even: be_zs_mode) */
+template <int NP, int JB, int AUX>
+__device__ __forceinline__ void gie_zs_fused_keys(uint32_t (&wk)[GIE_ZS_W], uint32_t (*srow)[GIE_ZS_XW], const __amdgpu_buffer_rsrc_t rs, const unsigned vo,
+                                                  const unsigned ps2, const int zfirst, const int Z, const unsigned long long pm, const bool ok0, const bool ok1, const int y8, const int lane)
+{
+    static_assert(NP % GIE_ZS_ROWS == 0, "whole batches of rows");
+    uint32_t v[NP];
+#pragma unroll
+    for (int j = 0; j < NP; j++) {
+        const unsigned so = (unsigned)min(max(__builtin_amdgcn_readfirstlane(zfirst) + j, 0), Z - 1) * ps2;     /* (wave-uniform: an SGPR, no waterfall) */
+        v[j] = __builtin_amdgcn_raw_buffer_load_b32(rs, vo, so, AUX);
+    }
+#pragma unroll
+    for (int j0 = 0; j0 < NP; j0 += GIE_ZS_ROWS) {
+#pragma unroll
+        for (int j = j0; j < j0 + GIE_ZS_ROWS; j++) {
+            const bool po = (pm >> j) & 1ull;
+            if (lane < GIE_ZS_XW / 2)
+                *reinterpret_cast<uint2 *>(&srow[j - j0][2 * lane]) = make_uint2(gie_zs_col(v[j] & 0xffffu, po && ok0, y8), gie_zs_col(v[j] >> 16, po && ok1, y8));
+        }
+        gie_wave_sync();
+        gie_lds_u32 *rp[GIE_ZS_CHAINS];
+#pragma unroll
+        for (int q = 0; q < GIE_ZS_CHAINS; q++) rp[q] = (gie_lds_u32 *)&srow[0][lane];
+#pragma unroll
+        for (int j = j0; j < j0 + GIE_ZS_ROWS; j++) {
+            wk[JB + j] = gie_zs_fused_key(rp[j % GIE_ZS_CHAINS] + (j - j0) * GIE_ZS_XW, JB + j);
+            asm volatile("" : "+v"(rp[j % GIE_ZS_CHAINS]) : "v"(wk[JB + j]));      /* (GIE_ZS_CHAINS planes at a time: with every row's reads hoisted first the kernel spilled) */
+        }
+        gie_wave_sync();                                  /* (the rows are rewritten next) */
+    }
+}
 /* One trip of a slab again, for the few positions whose closest obstacle lies beyond the register window (BASELINE config 5's hash
  * world: about thirty of 134 M voxels per update have none within 8 planes — and sending their slabs to the column kernel cost
  * 44 us of a 0.24 ms pass): a window of GIE_ZS_R2 planes on either side with full 32-bit keys (value << 10 | plane, no clamp on the
@@ -1308,13 +1409,76 @@ __device__ __noinline__ bool gie_zs_wide_trip(const uint32_t *cxy2, uint32_t *bc
     }
     return true;
 }
-__global__ __launch_bounds__(256, 6) void k_edt_z_stream(const gie_ctx c, const int full, const int nseg, const int seg_len)
+/* The same trip for the fused form, from pass Y's planes: the exact in-plane distance² of every site within 24 columns (one
+ * further costs at least 625, the trip's own limit), out of a row of 64 + 48 column values staged in the wave's LDS rows
+ * (dy² << 6, cy alongside), ties to the smaller x as pass X breaks them.  Inlined: its accesses go through the kernel's own
+ * buffer descriptors. */
+#define GIE_ZS_XW2 (64 + 2 * GIE_ZS_R2)
+static_assert(2 * GIE_ZS_XW2 <= GIE_ZS_ROWS * GIE_ZS_XW, "the wide trip's row and its cy fit the wave's LDS rows");
+__device__ __forceinline__ bool gie_zs_wide_trip_fused(const __amdgpu_buffer_rsrc_t rs_cy, const __amdgpu_buffer_rsrc_t rs_out, gie_lds_u32 *srow, const unsigned voff,
+                                                       const unsigned pstride, const unsigned ps2, const int zc, const int z1, const int Z, const int x0, const int x,
+                                                       const int y, const int X, const uint8_t *occ, const int lane)
+{
+    const int xa = x0 - GIE_ZS_R2 + lane, xb = x0 + 64 - GIE_ZS_R2 + lane;       /* row places lane / 64 + lane */
+    const bool oka = xa >= 0 && xa < X, okb = lane < 2 * GIE_ZS_R2 && xb < X;
+    const unsigned voa = oka ? (unsigned)(y * X + xa) * 2u : GIE_BUF_OOB, vob = okb ? (unsigned)(y * X + xb) * 2u : GIE_BUF_OOB;
+    gie_lds_u32 *sq = srow, *scy = srow + GIE_ZS_XW2;
+    uint32_t best[GIE_ZS_C], bc[GIE_ZS_C];
+#pragma unroll
+    for (int t = 0; t < GIE_ZS_C; t++) { best[t] = 0xffffffffu; bc[t] = GIE_BCOC_NONE; }
+    const int lo = max(zc - GIE_ZS_R2, 0), hi = min(zc + GIE_ZS_C + GIE_ZS_R2, Z);
+#pragma unroll 1
+    for (int i0 = lo; i0 < hi; i0 += 8) {
+        uint16_t va[8], vb[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const unsigned so = (unsigned)min(i0 + k, Z - 1) * ps2;
+            va[k] = __builtin_amdgcn_raw_buffer_load_b16(rs_cy, voa, so, 0);
+            vb[k] = __builtin_amdgcn_raw_buffer_load_b16(rs_cy, vob, so, 0);
+        }
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const int i = i0 + k;
+            if (i >= hi || !occ[i]) continue;             /* wave-uniform */
+            {
+                const int da = y - (int)va[k], db = y - (int)vb[k];
+                sq[lane] = (oka && va[k] != 0xffffu) ? ((uint32_t)(da * da) << 6) : 0x3fffffc0u; scy[lane] = va[k];
+                if (lane < 2 * GIE_ZS_R2) { sq[64 + lane] = (okb && vb[k] != 0xffffu) ? ((uint32_t)(db * db) << 6) : 0x3fffffc0u; scy[64 + lane] = vb[k]; }
+            }
+            gie_wave_sync();
+            uint32_t m = 0xffffffffu;                     /* in-plane distance² << 6 | column place (= dx + 24: the smaller x on a tie) */
+#pragma unroll
+            for (int q = 0; q <= 2 * GIE_ZS_R2; q++) m = min(m, sq[lane + q] + (((uint32_t)((q - GIE_ZS_R2) * (q - GIE_ZS_R2)) << 6) | (uint32_t)q));
+            const int q = (int)(m & 63u);
+            const uint32_t cc = gie_pack_bcoc(x - GIE_ZS_R2 + q, (int)scy[lane + q], i);
+            gie_wave_sync();                              /* (the row is rewritten for the next plane) */
+            const uint32_t a = min(m >> 6, 0x3fffffu);
+#pragma unroll
+            for (int t = 0; t < GIE_ZS_C; t++) {
+                const int d = zc + t - i;
+                const uint32_t nb = (min(a + (uint32_t)(d * d), 0x3fffffu) << 10) | (uint32_t)i;
+                if (nb < best[t]) { best[t] = nb; bc[t] = cc; }
+            }
+        }
+    }
+    uint32_t worst = 0;
+#pragma unroll
+    for (int t = 0; t < GIE_ZS_C; t++) if (zc + t < z1) worst = max(worst, best[t]);
+    if (__any(x < X && worst >= ((uint32_t)((GIE_ZS_R2 + 1) * (GIE_ZS_R2 + 1)) << 10))) return false;
+#pragma unroll
+    for (int t = 0; t < GIE_ZS_C; t++)
+        __builtin_amdgcn_raw_buffer_store_b32(bc[t], rs_out, (zc + t < z1) ? voff : GIE_BUF_OOB, (unsigned)min(zc + t, Z - 1) * pstride, 0);
+    return true;
+}
+template <bool FUSED>
+__global__ __launch_bounds__(256, FUSED ? GIE_ZS_FUSED_WGS : 6) void k_edt_z_stream(const gie_ctx c, const int full, const int nseg, const int seg_len, const int zs)
 {
     __shared__ uint8_t s_occ[1024 + 2 * (32 + 2 * GIE_ZS_R)];        /* plane holds obstacles, for planes -W .. Z + W (0 outside the volume) */
     const int Z = c.Z, X = c.X, Y = c.Y;
     if (full == 0 && gie_z_use_lists(c, c.cnt[GIE_CNT_TL_KNOWN])) { gie_edt_z_direct_body(c); return; }   /* few known tiles: the list form, in this launch (one launch less
                                                                                                          * per update than with a kernel of its own: 4.5 us each on the sparse workloads) */
-    if (*c.zcount <= GIE_BAND_MAXK) return;               /* planes with obstacles are few: the column kernel's envelope forms (same answer in every workgroup) */
+    if (!gie_zs_takes(c, zs, full)) return;               /* planes with obstacles are few: the column kernel's envelope forms (same answer in every workgroup) */
+    __shared__ __attribute__((aligned(16))) uint32_t s_row[FUSED ? 4 : 1][FUSED ? GIE_ZS_ROWS : 1][GIE_ZS_XW];    /* fused: the wave's rows of pass Y's planes */
     if (blockIdx.x == 0 && threadIdx.x == 0) c.cnt[GIE_CNT_ZSTREAM] = 1;
     for (int i = threadIdx.x; i < Z + 2 * GIE_ZS_W; i += 256) { const int z = i - GIE_ZS_W; s_occ[i] = (z >= 0 && z < Z) ? c.zocc[z] : (uint8_t)0; }
     __syncthreads();
@@ -1324,18 +1488,29 @@ __global__ __launch_bounds__(256, 6) void k_edt_z_stream(const gie_ctx c, const 
     const size_t plane = (size_t)X * Y;
     const unsigned nbytes = (unsigned)((size_t)X * Y * Z * 4u);
     const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(c.cxy2), 0, nbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_cy = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(c.cy1), 0, nbytes / 2u, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(c.bcoc, 0, nbytes, 0x00020000);
-    const unsigned pstride = (unsigned)(plane * 4u);
+    const unsigned pstride = (unsigned)(plane * 4u), pstride2 = (unsigned)(plane * 2u);
     for (int w = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6); w < total; w += (int)gridDim.x * 4) {
-        const int xr = w % nxr, seg = (w / nxr) % nseg, y = w / (nxr * nseg);
+        const int wu = __builtin_amdgcn_readfirstlane(w);  /* (said outright: the row offsets below are SGPRs, or every row access is a waterfall loop) */
+        const int xr = wu % nxr, seg = (wu / nxr) % nseg, y = wu / (nxr * nseg);
         const int x = xr * 64 + lane;
         const int z0 = seg * seg_len, z1 = min(Z, z0 + seg_len);
         if (z0 >= Z) continue;
         const unsigned voff = x < X ? (unsigned)(y * X + x) * 4u : GIE_BUF_OOB;
         const int x8 = x + 8, y8 = y + 8;
         uint32_t wk[GIE_ZS_W];
+        /* fused: this lane's two columns of the wave's rows of pass Y's planes (x0 - 8 + 2 lane, and the next: lanes < 40) */
+        const int xa = xr * 64 - GIE_ZS_R + 2 * lane;
+        const bool oka = lane < GIE_ZS_XW / 2 && xa >= 0 && xa < X, okb = lane < GIE_ZS_XW / 2 && xa + 1 >= 0 && xa + 1 < X;
+        const unsigned vpa = (oka || okb) ? (unsigned)(y * X + xa) * 2u : GIE_BUF_OOB;
+        uint32_t (*srow)[GIE_ZS_XW] = s_row[FUSED ? (threadIdx.x >> 6) : 0];
         /* the planes z0 - R .. z0 + R - 1 of the first trip (window places 0 .. 2R - 1) */
-        {
+        if (FUSED) {
+            const int zz = z0 - GIE_ZS_R + lane;
+            const unsigned long long pm = __ballot(lane < 2 * GIE_ZS_R && s_occ[zz + GIE_ZS_W] != 0);
+            gie_zs_fused_keys<2 * GIE_ZS_R, 0, 0>(wk, srow, rs_cy, vpa, pstride2, z0 - GIE_ZS_R, Z, pm, oka, okb, y8, lane);
+        } else {
             const int zz = z0 - GIE_ZS_R + lane;
             const unsigned long long pm = __ballot(lane < 2 * GIE_ZS_R && s_occ[zz + GIE_ZS_W] != 0);
             uint32_t v[2 * GIE_ZS_R];
@@ -1349,7 +1524,11 @@ __global__ __launch_bounds__(256, 6) void k_edt_z_stream(const gie_ctx c, const 
 #pragma unroll 1
         for (int zc = z0; zc < z1; zc += GIE_ZS_C) {
             /* planes zc + R .. zc + C + R - 1 -> window places 2R .. W - 1 */
-            {
+            if (FUSED) {
+                const int zz = zc + GIE_ZS_R + lane;
+                const unsigned long long pm = __ballot(lane < GIE_ZS_C && s_occ[zz + GIE_ZS_W] != 0);
+                gie_zs_fused_keys<GIE_ZS_C, 2 * GIE_ZS_R, GIE_ZS_LDAUX>(wk, srow, rs_cy, vpa, pstride2, zc + GIE_ZS_R, Z, pm, oka, okb, y8, lane);
+            } else {
                 const int zz = zc + GIE_ZS_R + lane;
                 const unsigned long long pm = __ballot(lane < GIE_ZS_C && s_occ[zz + GIE_ZS_W] != 0);
                 uint32_t v[GIE_ZS_C];
@@ -1394,12 +1573,25 @@ __global__ __launch_bounds__(256, 6) void k_edt_z_stream(const gie_ctx c, const 
 #pragma unroll
             for (int j = 0; j < 2 * GIE_ZS_R; j++) wk[j] = wk[GIE_ZS_C + j] - ((uint32_t)GIE_ZS_C << 18);      /* the last 2R planes are the next trip's first */
         }
-        if (!failed && wide > 0) failed = !gie_zs_wide_trip(c.cxy2, c.bcoc, nbytes, voff, pstride, wz0, z1, Z, x, y, x < X, s_occ + GIE_ZS_W);
-        if (!failed && wide > 1) failed = !gie_zs_wide_trip(c.cxy2, c.bcoc, nbytes, voff, pstride, wz1, z1, Z, x, y, x < X, s_occ + GIE_ZS_W);
-        if (failed && lane < 4) {                         /* the column kernel redoes the slab's tiles (whole columns: every segment's stores are overwritten) */
-            const int tx16 = xr * 4 + lane;
-            if (tx16 * 16 < X) c.zredo[(size_t)y * ((X + 15) >> 4) + tx16] = 1u;
-            if (lane == 0) atomicAdd(&c.cnt[GIE_CNT_ZFAIL], 1);
+        if (wide > 0 && lane == 0) atomicAdd(&c.cnt[GIE_CNT_ZWIDE], wide);
+        if (FUSED) {
+#pragma unroll 1
+            for (int k = 0; k < wide && !failed; k++)
+                failed = !gie_zs_wide_trip_fused(rs_cy, rs_out, (gie_lds_u32 *)&srow[0][0], voff, pstride, pstride2, __builtin_amdgcn_readfirstlane(k ? wz1 : wz0), z1, Z, xr * 64, x, y, X,
+                                                 s_occ + GIE_ZS_W, lane);
+        } else {
+            if (!failed && wide > 0) failed = !gie_zs_wide_trip(c.cxy2, c.bcoc, nbytes, voff, pstride, wz0, z1, Z, x, y, x < X, s_occ + GIE_ZS_W);
+            if (!failed && wide > 1) failed = !gie_zs_wide_trip(c.cxy2, c.bcoc, nbytes, voff, pstride, wz1, z1, Z, x, y, x < X, s_occ + GIE_ZS_W);
+        }
+        if (failed) {
+            if (lane < 4) {                               /* the column kernel redoes the slab's tiles (whole columns: every segment's stores are overwritten) */
+                const int tx16 = xr * 4 + lane;
+                if (tx16 * 16 < X) c.zredo[(size_t)y * ((X + 15) >> 4) + tx16] = 1u;
+                if (lane == 0) atomicAdd(&c.cnt[GIE_CNT_ZFAIL], 1);
+            }
+            /* the trips after the one that gave up recorded no bound: every tile of the segment is "81 or more" */
+            if ((lane & 7) == 0 && x < X)
+                for (int zt = z0; zt < z1; zt += 8) __hip_atomic_fetch_max(&c.tbmax[gie_tile_index(c, x, y, zt)], (int32_t)((GIE_ZS_R + 1) * (GIE_ZS_R + 1)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }

@@ -913,6 +913,13 @@ GIE_DEV int gie_batch_dist_direct(const gie_ctx &c, int x, int y, int z)
     const int K = *c.zcount;
     const size_t plane = (size_t)c.X * c.Y, o = (size_t)y * c.X + x;
     int best = c.max_width * c.max_width;
+    /* pass Z's streaming form did the volume (its fused form without pass X's planes): the batch closest obstacle is complete and
+     * exact in every slab it did not give up — and pass X has run on the rows of those it did (k_edt_x_redo) */
+    if (c.cnt[GIE_CNT_ZSTREAM] && c.zredo[(size_t)y * ((c.X + 15) >> 4) + (x >> 4)] == 0u) {
+        const uint32_t bc = c.bcoc[(size_t)z * plane + o];
+        const int d = gie_d2(x, y, z, (int)(bc & 1023u), (int)((bc >> 10) & 1023u), (int)(bc >> 20));
+        return d < best ? d : best;
+    }
     /* eight planes per trip, their loads in flight together (round 6: one load per trip made a lookup K dependent round trips — a lidar
      * scene has obstacles in 60-100 planes, and a block-run of wave B at a face of the volume waited 30-50 us for its unknown
      * neighbours' distances); a repeated plane does not change a minimum */

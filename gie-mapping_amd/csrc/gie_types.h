@@ -200,7 +200,8 @@ typedef struct gie_ctx {
 enum {
     GIE_CNT_A = 0, GIE_CNT_B, GIE_CNT_C,        /* seed counts from obtainFrontiers */
     GIE_CNT_TL_SWEPT,                           /* entries in tl_swept */
-    GIE_CNT_FREE4, GIE_CNT_FREE5,               /* (unused since the waves run in block / tile rounds) */
+    GIE_CNT_ZWIDE,                              /* pass Z, streaming form: trips redone with the wide window (a statistic: GIE_DEBUG_COUNTS) */
+    GIE_CNT_FREE5,                              /* (unused since the waves run in block / tile rounds) */
     GIE_CNT_LV0, GIE_CNT_LV1, GIE_CNT_LV2,      /* wave C: entries expanded in a level (rotating) */
     GIE_CNT_ERR,                                /* sticky error flags */
     GIE_CNT_NEWBLK,                             /* blocks allocated this frame */
