@@ -1409,6 +1409,40 @@ extern "C" int gie_debug_nbr_check(gie_mapper *m, int32_t *mismatches)
     be_d2h(&m->be, mismatches, d, sizeof(int32_t));
     return gie_sync(m);
 }
+/* test hook (not in gie.h): the per-tile state the last map update leaves to the next one's gie_tile_oldskip, copied out as it is —
+ * no launch, nothing written (the counters are copied, not fetched: gie_fetch_counters would clear a barrier fault).  Arrays have
+ * tfd[0] * tfd[1] * tfd[2] entries (zredo: ((X + 15) / 16) * Y), any may be null; tmax is this update's (the next gie_fuse rotates
+ * it into tmax_prev).  scalars[GIE_DBG_TS_NUM]: see GIE_DBG_TS_*.  Call it before gie_read_batch_edt: completing a partial pass Z
+ * runs the streaming form again, and its atomic max into tbmax would hide an underestimate. */
+enum { GIE_DBG_TS_PREV_VALID = 0, GIE_DBG_TS_COC_DEFER, GIE_DBG_TS_LAZY_OK, GIE_DBG_TS_ZSTREAM, GIE_DBG_TS_ZWIDE, GIE_DBG_TS_ZFAIL,
+       GIE_DBG_TS_LAZY_EXACT, GIE_DBG_TS_TSKIP, GIE_DBG_TS_STATE1, GIE_DBG_TS_STATE2, GIE_DBG_TS_NUM };
+extern "C" int gie_debug_tile_state(gie_mapper *m, uint8_t *tknown, uint8_t *tskip, uint8_t *tlazy, int32_t *tmax, int32_t *tbmax,
+                                    uint32_t *zredo, int32_t *scalars)
+{
+    if (!m || !scalars) { gie_set_err("gie_debug_tile_state: bad arguments"); return GIE_ERR_INVALID; }
+    const gie_ctx &c = m->c;
+    const size_t ntile = (size_t)c.tfd[0] * c.tfd[1] * c.tfd[2];
+    if (be_sync(&m->be) != 0) return GIE_ERR_DEVICE;
+    if (tknown) be_d2h(&m->be, tknown, c.tknown, ntile);
+    if (tskip) be_d2h(&m->be, tskip, c.tskip, ntile);
+    if (tlazy) be_d2h(&m->be, tlazy, c.tlazy, ntile);
+    if (tmax) be_d2h(&m->be, tmax, c.tmax, ntile * sizeof(int32_t));
+    if (tbmax) be_d2h(&m->be, tbmax, c.tbmax, ntile * sizeof(int32_t));
+    if (zredo) be_d2h(&m->be, zredo, c.zredo, (size_t)((c.X + 15) / 16) * c.Y * sizeof(uint32_t));
+    int32_t cnt[GIE_CNT_NUM];
+    be_d2h(&m->be, cnt, c.cnt, sizeof(cnt));
+    scalars[GIE_DBG_TS_PREV_VALID] = m->pp.owed == GIE_OWED_FRESH;       /* what the next gie_fuse's rotation sets c.prev_valid to */
+    scalars[GIE_DBG_TS_COC_DEFER] = c.coc_defer;
+    scalars[GIE_DBG_TS_LAZY_OK] = c.lazy_ok;
+    scalars[GIE_DBG_TS_ZSTREAM] = cnt[GIE_CNT_ZSTREAM];
+    scalars[GIE_DBG_TS_ZWIDE] = cnt[GIE_CNT_ZWIDE];
+    scalars[GIE_DBG_TS_ZFAIL] = cnt[GIE_CNT_ZFAIL];
+    scalars[GIE_DBG_TS_LAZY_EXACT] = cnt[GIE_CNT_LAZY_EXACT];
+    scalars[GIE_DBG_TS_TSKIP] = cnt[GIE_CNT_TSKIP];
+    scalars[GIE_DBG_TS_STATE1] = cnt[GIE_CNT_STATE1];
+    scalars[GIE_DBG_TS_STATE2] = cnt[GIE_CNT_STATE2];
+    return be_sync(&m->be) != 0 ? GIE_ERR_DEVICE : GIE_OK;
+}
 #endif /* GIE_TEST_HOOKS */
 extern "C" int gie_profile_enable(gie_mapper *m, int on)
 {

@@ -53,3 +53,8 @@ class EmuMapper(MapperBase):
         if _lib.gie_debug_nbr_check(self._h, C.byref(bad)):
             raise RuntimeError(self._err())
         return bad.value
+
+    def debug_tile_state(self):
+        """the per-tile state the last map update leaves to the next one (gie_debug_tile_state, test hook)"""
+        from hooks_py import read_tile_state
+        return read_tile_state(_lib, self)

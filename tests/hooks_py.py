@@ -6,6 +6,8 @@ base, staging chunk size, un-completed batch-EDT export ...) and that exports th
 import ctypes as C
 import os
 
+import numpy as np
+
 from gie import _capi
 from gie.mapper import Mapper, load_library
 
@@ -54,3 +56,31 @@ class HooksMapper(Mapper):
         if _lib.gie_debug_nbr_check(self._h, C.byref(bad)):
             raise RuntimeError(self._err())
         return bad.value
+
+    def debug_tile_state(self):
+        """the per-tile state the last map update leaves to the next one (gie_debug_tile_state); call it before read_batch_edt"""
+        return read_tile_state(_lib, self)
+
+
+# gie_debug_tile_state's scalars, in order (gie_api.inc.h GIE_DBG_TS_*)
+TILE_STATE_SCALARS = ("prev_valid", "coc_defer", "lazy_ok", "zstream", "zwide", "zfail", "lazy_exact", "tskip_count", "caught_up",
+                      "lazy_written_out")
+
+
+def read_tile_state(lib, m):
+    """gie_debug_tile_state of a mapper on `lib` (the test build or the emulation): per-tile arrays shaped [tz][ty][tx] (zredo: [y][x // 16])
+    and the scalars by name"""
+    X, Y, Z = m.size
+    tshape = ((Z + 7) // 8, (Y + 7) // 8, (X + 7) // 8)
+    out = {k: np.zeros(tshape, np.uint8) for k in ("tknown", "tskip", "tlazy")}
+    out.update({k: np.zeros(tshape, np.int32) for k in ("tmax", "tbmax")})
+    out["zredo"] = np.zeros((Y, (X + 15) // 16), np.uint32)
+    sc = np.zeros(len(TILE_STATE_SCALARS), np.int32)
+    f = lib.gie_debug_tile_state
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p] + [C.c_void_p] * 7
+    p = lambda a: a.ctypes.data_as(C.c_void_p)        # noqa: E731
+    if f(m._h, p(out["tknown"]), p(out["tskip"]), p(out["tlazy"]), p(out["tmax"]), p(out["tbmax"]), p(out["zredo"]), p(sc)):
+        raise RuntimeError(m._err())
+    out.update({k: int(v) for k, v in zip(TILE_STATE_SCALARS, sc)})
+    return out

@@ -56,7 +56,7 @@ def test_production_library_exports_nothing_but_the_header_and_reads_no_environm
     assert names(gie.LIB_PATH) == []
     test_so = __graft_entry__.build_hip_test_hooks()
     texp = {n for n in _dyn_symbols(test_so) if n.startswith("gie_")}
-    assert declared <= texp and {"gie_debug_fault_barrier", "gie_debug_place_probe"} <= texp
+    assert declared <= texp and {"gie_debug_fault_barrier", "gie_debug_place_probe", "gie_debug_tile_state"} <= texp
     assert {b"GIE_TILE_LIST", b"GIE_DEBUG_POOL_BASE", b"GIE_FUSED", b"GIE_STREAM_CHUNK_BLOCKS"} <= set(names(test_so))
 
 
