@@ -12,11 +12,13 @@
 #include <vector>
 
 enum { GIE_K_CLASSIFY = 0, GIE_K_RAY_REGISTER, GIE_K_RAY_FREE, GIE_K_RAY_FINAL, GIE_K_ALLOC, GIE_K_FUSE, GIE_K_EDT_Y, GIE_K_EDT_X,
-       GIE_K_EDT_Z, GIE_K_MARK, GIE_K_FRONTIER, GIE_K_WAVE_A, GIE_K_WAVE_B, GIE_K_WAVE_C, GIE_K_COMMIT, GIE_K_EDT_ZFACES, GIE_K_MARKC, GIE_K_NUM };
+       GIE_K_EDT_Z, GIE_K_MARK, GIE_K_FRONTIER, GIE_K_WAVE_A, GIE_K_WAVE_B, GIE_K_WAVE_C, GIE_K_COMMIT, GIE_K_EDT_ZFACES, GIE_K_MARKC,
+       GIE_K_SDF, GIE_K_SDF_QUERY, GIE_K_NUM };   /* (the signed distance field's ids come last: the others keep their indices) */
 #include <cstdio>
 #include <unistd.h>
 static const char *const gie_kernel_names[GIE_K_NUM] = { "ogm_classify", "ray_register", "ray_free", "ray_finalize", "block_alloc", "fuse",
-       "edt_pass_y", "edt_pass_x", "edt_pass_z", "mark", "frontiers", "wave_a", "wave_b", "waves", "commit", "edt_prep", "mark_commit" };
+       "edt_pass_y", "edt_pass_x", "edt_pass_z", "mark", "frontiers", "wave_a", "wave_b", "waves", "commit", "edt_prep", "mark_commit",
+       "sdf", "sdf_query" };
 
 #define GIE_REHASH_PERIOD 64                 /* map updates between two rebuilds of the hash table while blocks are being erased */
 static thread_local std::string g_gie_err;
@@ -45,6 +47,13 @@ struct gie_pair_state {
     int tsp_pvt[3] = {};                  /* the pivot tskip_prev's tiles refer to (c.ts_pvt: tskip's) */
     int fuse_fresh = 0;                   /* gie_fuse has run and no merge has consumed it yet (a merge needs the frame clear of its own map update) */
     int track_want = 0;                   /* gie_stream_enable: taken over by the next gie_fuse (an update runs in ONE order of kernels from its fuse to its merge) */
+};
+/* the planes of the signed distance field (gie_sdf.inc.h): allocated at its first call through gie_dalloc (so gie_destroy frees them
+ * with the rest), valid for the generation `gen` of the committed types */
+struct gie_sdf_cache {
+    uint64_t *occ = nullptr, *inner = nullptr;
+    int32_t *ids = nullptr, *count = nullptr;
+    long long gen = -1;
 };
 struct gie_mapper {
     gie_config cfg;
@@ -78,6 +87,8 @@ struct gie_mapper {
     /* CostMap publishing without a stall (gie_costmap_publish / gie_costmap_acquire): device staging + two pinned host buffers */
     gie_seendist *d_cm; void *h_cm[2]; size_t cm_bytes; int cm_slot, cm_pending;
     long long *d_round_stats;             /* exchange rounds without the host: rounds enqueued / run, updates / updates left unconverged (k_round_note) */
+    long long type_gen = 0;               /* bumped by every entry point that enqueues a kernel writing `_glb_type` (gie_fuse, gie_merge_end) */
+    gie_sdf_cache sdf;                    /* the signed distance field's inside distances (HIP backend: gie_sdf.inc.h) */
 };
 
 template <class T> static T *gie_dalloc(gie_mapper *m, size_t n, bool zero = true)
@@ -796,6 +807,7 @@ extern "C" int gie_fuse(gie_mapper *m)
     be_prof(&m->be, GIE_K_ALLOC, 1);
     be_prof(&m->be, GIE_K_FUSE, 0);
     be_fuse(&m->be, m->c, m->c.tl_front);
+    m->type_gen++;
     be_prof(&m->be, GIE_K_FUSE, 1);
     m->labels_pending = nullptr; m->c.scan_labels = nullptr;      /* (a label plane left in place has been read) */
     be_prof(&m->be, GIE_K_ALLOC, 0);
@@ -850,6 +862,7 @@ extern "C" int gie_merge_end(gie_mapper *m)
      * anything to look at) + the voxels on the faces of the volume, one per lane; then the listed tiles (tsum == 1), a wave
      * per tile out of LDS (k_frontier_faces / k_frontier_tiles; 0.32 -> 0.15 ms on the C5 workload) */
     be_frontier_tiles(&m->be, m->c, m->c.tl_known, GIE_CNT_TL_KNOWN, m->c.tl_front, GIE_CNT_TL_FRONT);
+    m->type_gen++;                        /* (FREE voxels next to unknown ones become FNT) */
     be_prof(&m->be, GIE_K_FRONTIER, 1);
     m->c.bar_fault = m->bar_fault_left > 0 ? 1 : 0;
     if (m->bar_fault_left > 0) m->bar_fault_left--;

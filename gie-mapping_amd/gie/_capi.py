@@ -145,6 +145,11 @@ DEVICE_ONLY = {
     "ogm_depth_dev": (C.c_int, [_H, C.c_void_p, C.POINTER(CamParam)]),
     "ogm_labels_dev": (C.c_int, [_H, C.c_void_p]),
     "ogm_labels_dev_borrow": (C.c_int, [_H, C.c_void_p, C.POINTER(C.c_int)]),
+    # signed distance field of the local volume (include/gie.h): not in SIGNATURES, the oracle and the emulation do not have it
+    "read_sdf": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
+    "read_sdf_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
+    "query_sdf": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "query_sdf_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 DEVICE_ONLY.update(ROUND_API)
 

@@ -382,6 +382,38 @@ class Mapper(MapperBase):
             raise RuntimeError(self._err())
         return {buf[i].name.decode(): (buf[i].total_ms, buf[i].launches) for i in range(n)}
 
+    # --- signed distance field of the local volume (include/gie.h) ---------------------------
+    def read_sdf(self, sdf=True, inside_dist_sq=True):
+        """{"sdf": float32 (voxel units), "inside_dist_sq": int32}, shaped [Z][Y][X] like read_local (synchronises)."""
+        out = {}
+        s = np.empty(self._shape(), np.float32) if sdf else None
+        d = np.empty(self._shape(), np.int32) if inside_dist_sq else None
+        self._chk(self._f["read_sdf"](self._h, _ptr(s), _ptr(d)))
+        for k, v in (("sdf", s), ("inside_dist_sq", d)):
+            if v is not None:
+                out[k] = v
+        return out
+
+    def read_sdf_dev(self, d_sdf, d_inside_dist_sq):
+        """The same planes into device buffers (raw device addresses, 0 = not wanted), asynchronous on the mapper's stream."""
+        self._chk(self._f["read_sdf_dev"](self._h, C.c_void_p(d_sdf or None), C.c_void_p(d_inside_dist_sq or None)))
+
+    def query_sdf(self, xyz):
+        """n points (metres, world frame) -> (dist [n] float32 metres, grad [n,3] float32, flags [n] uint8) (synchronises)."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        n = xyz.shape[0]
+        dist = np.empty(n, np.float32)
+        grad = np.empty((n, 3), np.float32)
+        flags = np.empty(n, np.uint8)
+        self._chk(self._f["query_sdf"](self._h, _ptr(xyz), n, _ptr(dist), _ptr(grad), _ptr(flags)))
+        return dist, grad, flags
+
+    def query_sdf_dev(self, d_xyz, n, d_dist, d_grad, d_flags):
+        """n queries with points (n x 3 float32) and results in DEVICE buffers (raw addresses, e.g. torch .data_ptr(); 0 = not
+        wanted), enqueued on the mapper's stream; nothing is copied and the host does not wait."""
+        self._chk(self._f["query_sdf_dev"](self._h, C.c_void_p(d_xyz or None), int(n), C.c_void_p(d_dist or None),
+                                           C.c_void_p(d_grad or None), C.c_void_p(d_flags or None)))
+
     def stream_handle(self):
         """The mapper's HIP stream as an integer (for torch.cuda.ExternalStream)."""
         p = C.c_void_p()

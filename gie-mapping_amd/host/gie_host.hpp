@@ -417,6 +417,18 @@ public:
         frame++;
     }
 
+    /* the signed distance field of the local volume (include/gie.h gie_read_sdf), voxel units, x fastest */
+    void readSignedDistance(std::vector<float> &sdf)
+    {
+        sdf.resize((size_t)cfg_.local_size[0] * cfg_.local_size[1] * cfg_.local_size[2]);
+        chk(gie_read_sdf(m_, sdf.data(), nullptr));
+    }
+    /* interpolated distance (m) and gradient (m/m, 3 per point) at n points xyz (m, world frame); flags as gie_query_sdf */
+    void querySignedDistance(const float *xyz, int n, float *dist, float *grad, uint8_t *flags)
+    {
+        chk(gie_query_sdf(m_, xyz, n, dist, grad, flags));
+    }
+
     gie_mapper *handle() { return m_; }
     const gie_config &config() const { return cfg_; }
 

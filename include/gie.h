@@ -247,6 +247,48 @@ int gie_query_global(gie_mapper *h, const int32_t *xyz, int n, gie_voxel *out);
 int gie_query_global_dev(gie_mapper *h, const int32_t *d_xyz, int n, gie_voxel *d_out);
 int gie_get_stats(gie_mapper *h, gie_frame_stats *out);
 
+/* ---- signed distance field of the local volume and interpolated distance / gradient queries, for gradient-based planners
+ * (the reference lists "Signed distance" as a feature in development, README.md "Additional features").  No counterpart in the
+ * reference's code.
+ *
+ * The field covers the local volume only, in the current frame: it is what gie_read_local / gie_read_costmap would read at the
+ * same point in the mapper's stream.
+ *  occupied(v)        glb_type[v] == GIE_VOX_OCCUPIED.  UNKNOWN, FREE and FNT count as non-occupied, as for the positive EDT.
+ *  inside_dist_sq(v)  0 when v is not occupied; otherwise the exact squared Euclidean distance, in voxels and as an integer, from v
+ *                     to the nearest non-occupied voxel OF THE LOCAL VOLUME; -1 when the volume holds no non-occupied voxel.
+ *  sdf(v)             voxel units, like _edt_D and gie_seendist.d:
+ *                       inside_dist_sq(v) <= 1:  sdf(v) = the `edt` gie_read_local returns for v, bit for bit;
+ *                       inside_dist_sq(v) >  1:  sdf(v) = 1.0f - sqrtf((float)inside_dist_sq(v));
+ *                       inside_dist_sq(v) == -1: sdf(v) = -(float)max_loc_dist_sq (X² + Y² + Z²), the mirror of the positive
+ *                                                side's value for "no obstacle".
+ *                     The usual "positive minus negative plus one voxel" convention: the surface layer of an obstacle stays at
+ *                     0, deeper voxels go negative.  The field differs from the EDT ONLY at occupied voxels without a
+ *                     non-occupied face neighbour in the volume.
+ * Query at a point p (metres, world frame: the frame of gie_set_pose):
+ *  u_k = p_k / w - (float)pvt_k    continuous local coordinate (voxel centres at integers: gie_pos2coord = floor(p/w + 0.5));
+ *  axis with size_k >= 2:          inside iff 0 <= u_k <= size_k - 1; i0 = min(floor(u_k), size_k - 2), t = u_k - i0;
+ *  axis with size_k == 1:          inside iff -0.5 <= u_k < 0.5; the field is constant along it, its gradient component is 0;
+ *  dist    trilinear interpolation of sdf over the 8 corners, times w: metres;
+ *  grad    the analytic gradient of that interpolant (n x 3, x y z per point): m/m;
+ *  flags   bit 0 inside the volume, bit 1 all corners known (type != UNKNOWN), bit 2 some corner occupied;
+ *  outside the volume: dist = NaN, grad = 0, flags = 0.
+ * Cache: inside_dist_sq is computed on the device at the first of these calls after anything that can change a committed type
+ * (every gie_fuse / gie_step and the frontier pass of gie_merge) and kept until the next such change.  A mapper that never calls
+ * them allocates nothing and launches nothing; the first call allocates 4 bytes per voxel plus two bit planes whose rows are
+ * padded to 64-bit words (16 * ceil(X/64) / X bytes per voxel: 4.25 bytes per voxel in all when X is a multiple of 64, at most
+ * 5 when X >= 22), freed by gie_destroy.  Nothing of the map update reads them.
+ * Arguments: sdf / inside_dist_sq are N values each (x fastest), either may be NULL; dist (n), grad (3n) and flags (n) may each be
+ * NULL, but not all three; n == 0 is valid; a bad argument gives GIE_ERR_INVALID.  The host forms synchronise; the _dev forms take
+ * DEVICE buffers and are enqueued on the mapper's stream (gie_get_stream) like gie_query_global_dev: nothing is copied, the host
+ * does not wait.
+ * A tiled mapper (gie_set_tile with a non-zero offset, or whole != local_size) gets GIE_ERR_INVALID from all four: its inside
+ * distances would stop at the tile's faces.
+ * gie_profile_read: "sdf" = the inside distances and the gie_read_sdf* exports, "sdf_query" = the queries (the last two entries). */
+int gie_read_sdf(gie_mapper *h, float *sdf, int32_t *inside_dist_sq);
+int gie_read_sdf_dev(gie_mapper *h, float *d_sdf, int32_t *d_inside_dist_sq);
+int gie_query_sdf(gie_mapper *h, const float *xyz, int n, float *dist, float *grad, uint8_t *flags);
+int gie_query_sdf_dev(gie_mapper *h, const float *d_xyz, int n, float *d_dist, float *d_grad, uint8_t *d_flags);
+
 /* ---- changed-block streaming: the CPU mirror the reference keeps for RViz and CPU planners.
  * GlbHashMap::streamPipeline / streamD2H / getUpdatedAddr (glb_hash_map.cu:209-247,
  * unify_helper.cuh:11-32), fed by the stream_VB_keys_D appends of the fuse / wave / commit kernels
