@@ -55,6 +55,15 @@ struct gie_sdf_cache {
     int32_t *ids = nullptr, *count = nullptr;
     long long gen = -1;
 };
+/* the NF1 navigation function (gie_nf1.inc.h): allocated at its first compute through gie_dalloc, kept until the next compute */
+struct gie_nf1_cache {
+    int32_t *f = nullptr;                 /* the field */
+    uint64_t *bits = nullptr;             /* five bit planes */
+    int32_t *words = nullptr;             /* control words, tile stamps, two tile lists */
+    int valid = 0;                        /* a compute has been enqueued */
+    int pvt[3] = { 0, 0, 0 };             /* the pivot and CostMap origin at that compute */
+    float origin[3] = { 0.f, 0.f, 0.f };
+};
 struct gie_mapper {
     gie_config cfg;
     gie_ctx c;
@@ -89,6 +98,7 @@ struct gie_mapper {
     long long *d_round_stats;             /* exchange rounds without the host: rounds enqueued / run, updates / updates left unconverged (k_round_note) */
     long long type_gen = 0;               /* bumped by every entry point that enqueues a kernel writing `_glb_type` (gie_fuse, gie_merge_end) */
     gie_sdf_cache sdf;                    /* the signed distance field's inside distances (HIP backend: gie_sdf.inc.h) */
+    gie_nf1_cache nf1;                    /* the navigation function (HIP backend: gie_nf1.inc.h) */
 };
 
 template <class T> static T *gie_dalloc(gie_mapper *m, size_t n, bool zero = true)
@@ -908,7 +918,7 @@ static int gie_fetch_counters(gie_mapper *m)
                          m->h_cnt[GIE_CNT_TL_FRONT], m->h_cnt[GIE_CNT_TL_FUSE], m->h_cnt[GIE_CNT_SEED_A], m->h_cnt[GIE_CNT_SEED_B], m->h_cnt[GIE_CNT_SEED_C], m->h_cnt[GIE_CNT_TSKIP],
                          m->h_cnt[GIE_CNT_STATE1], m->h_cnt[GIE_CNT_STATE2], m->h_cnt[GIE_CNT_ZSTREAM], m->h_cnt[GIE_CNT_ZWIDE], m->h_cnt[GIE_CNT_ZFAIL]);
     }
-    if (e & ~GIE_ERRF_BARRIER) {
+    if (e & ~(GIE_ERRF_BARRIER | GIE_ERRF_NF1_BARRIER)) {
         std::string s = "device capacity exceeded:";
         if (e & GIE_ERRF_POOL) s += " block pool (raise gie_config.max_blocks)";
         if (e & GIE_ERRF_QUEUE) s += " frontier queue";
@@ -916,12 +926,18 @@ static int gie_fetch_counters(gie_mapper *m)
         gie_set_err(s);
         return GIE_ERR_CAPACITY;
     }
-    if (e & GIE_ERRF_BARRIER) {
+    if (e & (GIE_ERRF_BARRIER | GIE_ERRF_NF1_BARRIER)) {
         /* not sticky: reported once, then cleared (the per-frame clear leaves the error word alone) */
         be_memset(&m->be, &m->c.cnt[GIE_CNT_ERR], 0, sizeof(int32_t));
         be_sync(&m->be);
-        gie_set_err("grid barrier of the wavefront kernel timed out (its workgroups were not all resident: another process is holding the "
-                    "device); this map update is incomplete, the next one runs normally");
+        std::string s;
+        if (e & GIE_ERRF_BARRIER)
+            s = "grid barrier of the wavefront kernel timed out (its workgroups were not all resident: another process is holding the "
+                "device); this map update is incomplete, the next one runs normally";
+        if (e & GIE_ERRF_NF1_BARRIER)
+            s += std::string(s.empty() ? "" : "; ") + "grid barrier of the navigation function's propagation timed out (its workgroups were not "
+                 "all resident: another process is holding the device); the NF1 field is incomplete until the next gie_nf1_compute, the map is not affected";
+        gie_set_err(s);
         return GIE_ERR_TIMEOUT;
     }
     return GIE_OK;

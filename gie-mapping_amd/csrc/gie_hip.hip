@@ -585,7 +585,9 @@ static void be_edt(be_state *b, const gie_ctx &c, int full)
  * different mappers on the same device at the same time need not be.  Waves launches of one
  * device are therefore chained through an event: a launch waits for the previous one, whichever
  * mapper (stream) it came from. */
-static void be_waves(be_state *b, const gie_ctx &c, int with_ab, int record_seeds, int clear_first)
+/* every grid-barrier launch of the library joins that chain (the waves; the navigation function's propagation, gie_nf1.inc.h):
+ * `enqueue` puts the chained work on b->stream */
+template <class F> static void be_chained(be_state *b, const F &enqueue)
 {
     std::lock_guard<std::mutex> lock(g_waves_mutex);
     const int dv = b->device & 63;
@@ -595,14 +597,21 @@ static void be_waves(be_state *b, const gie_ctx &c, int with_ab, int record_seed
         if (g_waves_event_set[dv]) GIE_HIP_OK(hipStreamWaitEvent(b->stream, g_waves_event[dv], 0));
         else { GIE_HIP_OK(hipEventCreateWithFlags(&g_waves_event[dv], hipEventDisableTiming)); g_waves_event_set[dv] = true; }
     }
-    if (clear_first) {
-        GIE_HIP_OK(hipMemsetAsync(&c.cnt[GIE_CNT_BAR_B], 0, 2 * sizeof(int32_t), b->stream));      /* (BAR_B, BAR_C: the barrier words of the two launches) */
-        GIE_HIP_OK(hipMemsetAsync(c.lvl_next, 0, 2 * GIE_MAX_LEVELS * sizeof(int32_t), b->stream));
-    }
-    if (with_ab) GIE_LAUNCH(b, k_waves_ab, dim3(b->num_cu), dim3(GIE_WAVE_THREADS), 0, c);
-    GIE_LAUNCH(b, k_waves_c, dim3(b->num_cu), dim3(GIE_WAVE_THREADS), 0, c, with_ab, record_seeds);
+    enqueue();
     if (chain) GIE_HIP_OK(hipEventRecord(g_waves_event[dv], b->stream));
+}
+static void be_waves(be_state *b, const gie_ctx &c, int with_ab, int record_seeds, int clear_first)
+{
+    be_chained(b, [&]() {
+        if (clear_first) {
+            GIE_HIP_OK(hipMemsetAsync(&c.cnt[GIE_CNT_BAR_B], 0, 2 * sizeof(int32_t), b->stream));      /* (BAR_B, BAR_C: the barrier words of the two launches) */
+            GIE_HIP_OK(hipMemsetAsync(c.lvl_next, 0, 2 * GIE_MAX_LEVELS * sizeof(int32_t), b->stream));
+        }
+        if (with_ab) GIE_LAUNCH(b, k_waves_ab, dim3(b->num_cu), dim3(GIE_WAVE_THREADS), 0, c);
+        GIE_LAUNCH(b, k_waves_c, dim3(b->num_cu), dim3(GIE_WAVE_THREADS), 0, c, with_ab, record_seeds);
+    });
 }
 
 #include "gie_api.inc.h"
 #include "gie_sdf.inc.h"
+#include "gie_nf1.inc.h"

@@ -241,16 +241,22 @@ __global__ __launch_bounds__(256) void k_sdf_query(const gie_ctx c, const gie_sd
 }
 
 /* ---- host side */
-static int gie_sdf_check(gie_mapper *m, const char *who)
+/* a mapper that is (or will be, at its next pose) one tile of a larger volume: gie_set_tile with a non-zero offset or whole != local_size */
+static bool gie_tiled(const gie_mapper *m)
 {
-    if (!m) { gie_set_err(std::string(who) + ": null handle"); return GIE_ERR_INVALID; }
     const gie_ctx &c = m->c;
     const int size[3] = { c.X, c.Y, c.Z };
     for (int i = 0; i < 3; i++)
-        if ((m->has_pose && (c.tile_off[i] != 0 || c.whole_lo[i] != 0 || c.whole_hi[i] != size[i])) || m->next_off[i] != 0 || m->next_whole[i] != size[i]) {
-            gie_set_err(std::string(who) + ": not for a tiled mapper (its inside distances would stop at the tile's faces)");
-            return GIE_ERR_INVALID;
-        }
+        if ((m->has_pose && (c.tile_off[i] != 0 || c.whole_lo[i] != 0 || c.whole_hi[i] != size[i])) || m->next_off[i] != 0 || m->next_whole[i] != size[i]) return true;
+    return false;
+}
+static int gie_sdf_check(gie_mapper *m, const char *who)
+{
+    if (!m) { gie_set_err(std::string(who) + ": null handle"); return GIE_ERR_INVALID; }
+    if (gie_tiled(m)) {
+        gie_set_err(std::string(who) + ": not for a tiled mapper (its inside distances would stop at the tile's faces)");
+        return GIE_ERR_INVALID;
+    }
     return GIE_OK;
 }
 static gie_sdf_dev gie_sdf_view(const gie_mapper *m)

@@ -232,6 +232,7 @@ enum {
 #define GIE_ERRF_QUEUE 2
 #define GIE_ERRF_HASH 4
 #define GIE_ERRF_BARRIER 8
+#define GIE_ERRF_NF1_BARRIER 16    /* a grid barrier of the navigation function's propagation timed out (gie_nf1.inc.h): the field is incomplete, the map is not */
 
 /* regions zeroed by one launch at the start of a map update */
 #define GIE_CLEAR_MAX 16

@@ -55,6 +55,14 @@ class Voxel(C.Structure):
                 ("dist_sq", C.c_int32), ("coc", C.c_int32 * 3)]
 
 
+class Nf1Param(C.Structure):
+    _fields_ = [("clearance", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+NF1_UNKNOWN_TRAVERSABLE = 1
+NF1_FROM_FRONTIERS = 2
+
+
 class CostMapHdr(C.Structure):
     _fields_ = [("x_size", C.c_int32), ("y_size", C.c_int32), ("z_size", C.c_int32),
                 ("x_origin", C.c_float), ("y_origin", C.c_float), ("z_origin", C.c_float),
@@ -150,6 +158,15 @@ DEVICE_ONLY = {
     "read_sdf_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
     "query_sdf": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "query_sdf_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # NF1 navigation function of the local volume (include/gie.h): device library only, like the signed distance field
+    "nf1_compute": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(Nf1Param), C.c_void_p]),
+    "nf1_compute_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(Nf1Param), C.c_void_p]),
+    "read_nf1": (C.c_int, [_H, C.c_void_p]),
+    "read_nf1_dev": (C.c_int, [_H, C.c_void_p]),
+    "nf1_path": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "nf1_path_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "read_costmap_nf1": (C.c_int, [_H, C.c_void_p, C.POINTER(CostMapHdr)]),
+    "read_costmap_nf1_dev": (C.c_int, [_H, C.c_void_p, C.POINTER(CostMapHdr)]),
 }
 DEVICE_ONLY.update(ROUND_API)
 

@@ -13,7 +13,8 @@ import sys
 import numpy as np
 
 from . import _capi
-from ._capi import CamParam, Config, CostMapHdr, FrameStats, MultiScanParam, ScanParam, Voxel
+from ._capi import NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE
+from ._capi import CamParam, Config, CostMapHdr, FrameStats, MultiScanParam, Nf1Param, ScanParam, Voxel
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG, "csrc", "libgie_hip.so")
@@ -413,6 +414,66 @@ class Mapper(MapperBase):
         wanted), enqueued on the mapper's stream; nothing is copied and the host does not wait."""
         self._chk(self._f["query_sdf_dev"](self._h, C.c_void_p(d_xyz or None), int(n), C.c_void_p(d_dist or None),
                                            C.c_void_p(d_grad or None), C.c_void_p(d_flags or None)))
+
+    # --- NF1 navigation function of the local volume (include/gie.h) -----------------------
+    def nf1_param(self, clearance=0.0, unknown_traversable=False, from_frontiers=False):
+        """gie_nf1_param for a clearance in METRES: float32(clearance) / float32(voxel_width) voxels."""
+        p = Nf1Param()
+        p.clearance = float(np.float32(clearance) / np.float32(self.cfg.voxel_width))
+        p.flags = (NF1_UNKNOWN_TRAVERSABLE if unknown_traversable else 0) | (NF1_FROM_FRONTIERS if from_frontiers else 0)
+        return p
+
+    def nf1_compute(self, goals=(), clearance=0.0, unknown_traversable=False, from_frontiers=False):
+        """The field towards goal points (n x 3 metres, world frame) and/or the frontiers; returns the number of sources (synchronises)."""
+        g = np.ascontiguousarray(np.asarray(goals, dtype=np.float32).reshape(-1, 3))
+        p = self.nf1_param(clearance, unknown_traversable, from_frontiers)
+        ns = C.c_int32(0)
+        self._chk(self._f["nf1_compute"](self._h, _ptr(g) if g.shape[0] else None, g.shape[0], C.byref(p), C.byref(ns)))
+        return ns.value
+
+    def nf1_compute_dev(self, d_goals, n, clearance=0.0, unknown_traversable=False, from_frontiers=False, d_n_sources=0):
+        """The same with goals (n x 3 float32) and the source count (int32; 0 = not wanted) in DEVICE buffers, on the mapper's stream."""
+        p = self.nf1_param(clearance, unknown_traversable, from_frontiers)
+        self._chk(self._f["nf1_compute_dev"](self._h, C.c_void_p(d_goals or None), int(n), C.byref(p), C.c_void_p(d_n_sources or None)))
+
+    def read_nf1(self):
+        """int32 field [Z][Y][X] (synchronises)."""
+        out = np.empty(self._shape(), np.int32)
+        self._chk(self._f["read_nf1"](self._h, _ptr(out)))
+        return out
+
+    def read_nf1_dev(self, d_nf1):
+        """The field into a device buffer (N int32, raw address), asynchronous on the mapper's stream."""
+        self._chk(self._f["read_nf1_dev"](self._h, C.c_void_p(d_nf1 or None)))
+
+    def nf1_path(self, starts, max_len):
+        """Descents from start points (n x 3 metres): (list of (min(len, max_len), 3) int32 arrays of global voxels, len [n] int32)
+        (synchronises)."""
+        xyz = np.ascontiguousarray(np.asarray(starts, dtype=np.float32).reshape(-1, 3))
+        n = xyz.shape[0]
+        path = np.zeros((n, max(int(max_len), 1), 3), np.int32)
+        ln = np.zeros(n, np.int32)
+        if n:
+            self._chk(self._f["nf1_path"](self._h, _ptr(xyz), n, int(max_len), _ptr(path), _ptr(ln)))
+        return [path[i, :min(int(ln[i]), int(max_len))] for i in range(n)], ln
+
+    def nf1_path_dev(self, d_starts, n, max_len, d_path, d_len):
+        """n descents with starts (n x 3 float32), points (n x max_len x 3 int32) and lengths (n int32) in DEVICE buffers."""
+        self._chk(self._f["nf1_path_dev"](self._h, C.c_void_p(d_starts or None), int(n), int(max_len), C.c_void_p(d_path or None),
+                                          C.c_void_p(d_len or None)))
+
+    def read_costmap_nf1(self):
+        """The TYPE_NF1 CostMap: (SeenDist payload [Z][Y][X], header) (synchronises)."""
+        pay = np.empty(self._shape(), SEENDIST_DTYPE)
+        hdr = CostMapHdr()
+        self._chk(self._f["read_costmap_nf1"](self._h, _ptr(pay), C.byref(hdr)))
+        return pay, hdr
+
+    def read_costmap_nf1_dev(self, dptr):
+        """The TYPE_NF1 payload into a device buffer (raw address), asynchronous on the mapper's stream; returns the header."""
+        hdr = CostMapHdr()
+        self._chk(self._f["read_costmap_nf1_dev"](self._h, C.c_void_p(dptr or None), C.byref(hdr)))
+        return hdr
 
     def stream_handle(self):
         """The mapper's HIP stream as an integer (for torch.cuda.ExternalStream)."""

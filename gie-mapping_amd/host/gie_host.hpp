@@ -20,6 +20,7 @@
 #ifndef GIE_HOST_HPP
 #define GIE_HOST_HPP
 
+#include <array>
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -427,6 +428,32 @@ public:
     void querySignedDistance(const float *xyz, int n, float *dist, float *grad, uint8_t *flags)
     {
         chk(gie_query_sdf(m_, xyz, n, dist, grad, flags));
+    }
+
+    /* the NF1 navigation function (include/gie.h gie_nf1_compute): steps to the nearest goal (metres, world frame, 3 per goal) or,
+     * with GIE_NF1_FROM_FRONTIERS, frontier, through voxels with clearance_m of free space; -1 where none is reachable; x fastest.
+     * Returns the number of sources. */
+    int navigationFunction(const float *goals, int n, float clearance_m, int flags, std::vector<int32_t> &nf1)
+    {
+        gie_nf1_param p = {};
+        p.clearance = clearance_m / cfg_.voxel_width;
+        p.flags = flags;
+        int32_t sources = 0;
+        chk(gie_nf1_compute(m_, goals, n, &p, &sources));
+        nf1.resize((size_t)cfg_.local_size[0] * cfg_.local_size[1] * cfg_.local_size[2]);
+        chk(gie_read_nf1(m_, nf1.data()));
+        return sources;
+    }
+    /* the descent from `start` (metres, world frame) in the last navigation function: global voxel coordinates, the start first,
+     * the source last; empty when no source is reachable from it; at most max_len points */
+    std::vector<std::array<int32_t, 3>> navigationPath(const float start[3], int max_len)
+    {
+        std::vector<int32_t> xyz((size_t)std::max(max_len, 1) * 3);
+        int32_t len = 0;
+        chk(gie_nf1_path(m_, start, 1, max_len, xyz.data(), &len));
+        std::vector<std::array<int32_t, 3>> out((size_t)std::min(len, max_len));
+        for (size_t i = 0; i < out.size(); i++) out[i] = { xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2] };
+        return out;
     }
 
     gie_mapper *handle() { return m_; }

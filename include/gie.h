@@ -110,7 +110,7 @@ typedef struct gie_costmap_hdr {
     int32_t x_size, y_size, z_size;
     float x_origin, y_origin, z_origin;
     float width;
-    uint8_t type; /* TYPE_EDT = 1 */
+    uint8_t type; /* TYPE_EDT = 1; TYPE_NF1 = 2 from gie_read_costmap_nf1 */
     uint8_t pad[3];
 } gie_costmap_hdr;
 
@@ -288,6 +288,56 @@ int gie_read_sdf(gie_mapper *h, float *sdf, int32_t *inside_dist_sq);
 int gie_read_sdf_dev(gie_mapper *h, float *d_sdf, int32_t *d_inside_dist_sq);
 int gie_query_sdf(gie_mapper *h, const float *xyz, int n, float *dist, float *grad, uint8_t *flags);
 int gie_query_sdf_dev(gie_mapper *h, const float *d_xyz, int n, float *d_dist, float *d_grad, uint8_t *d_flags);
+
+/* ---- NF1 navigation function of the local volume, for gradient planners and frontier exploration (msg/CostMap.msg reserves
+ * TYPE_NF1 = 2 for it; the reference never writes it).  No counterpart in the reference's code.
+ *
+ * Everything is over the local volume at the point of the mapper's stream where gie_nf1_compute* is enqueued; type(v) and edt(v)
+ * are exactly what gie_read_local would return there (edt in voxel units, as gie_seendist.d).
+ *  traversable(v)  type(v) is FREE or FNT (or UNKNOWN, with GIE_NF1_UNKNOWN_TRAVERSABLE) and edt(v) >= clearance (a float
+ *                  comparison; clearance in voxel units, finite and >= 0, otherwise GIE_ERR_INVALID).
+ *  sources         traversable voxels among: the voxel of each goal point g (metres, world frame) at gie_pos2coord(g_k, w) - pvt_k,
+ *                  points outside the volume (or not finite) ignored; every FNT voxel, with GIE_NF1_FROM_FRONTIERS (the distance
+ *                  to the nearest reachable frontier, the exploration guide).
+ *  nf1(v)          int32: for a traversable voxel with a path to a source, the number of steps of the shortest 6-connected path
+ *                  from v to a source whose every voxel is traversable and inside the volume (sources 0); -1 everywhere else.
+ * The field is kept until the next compute and refers to the pivot gie_get_pivot returned when it was enqueued; map updates do not
+ * change it.  n_sources: the number of sources (host int32 / device int32 of the caller's; either may be NULL).  n == 0 is valid.
+ * Path: one descent per start point s (mapped like the goals, at the field's pivot): len = 0 when s is outside the volume or
+ *  nf1(s) < 0; otherwise s = v0 .. vk, k = nf1(s), v_{i+1} = the first 6-neighbour of v_i in the order -x +x -y +y -z +z whose
+ *  value is nf1(v_i) - 1.  path_xyz: max_len points (3 int32 each, GLOBAL voxel coordinates = local + pivot) per start;
+ *  len[i] = k + 1 even when that exceeds max_len (only max_len points are written: truncated iff len > max_len).
+ * CostMap (TYPE_NF1): hdr as gie_read_costmap with type = 2 and the origin of the field's pivot; payload d = (float)nf1(v), or
+ *  -1.0f where nf1(v) = -1; o = type(v) != UNKNOWN at compute time (as gie_read_costmap's o); s = 0.
+ * The host forms synchronise; the _dev forms take DEVICE buffers and are enqueued on the mapper's stream without a host wait (the
+ * whole propagation is one persistent launch of gie_config.wave_workgroups workgroups, a grid barrier per BFS level: a few
+ * microseconds per level, so a winding field of many thousand levels holds those compute units for as many times that).
+ * Like the wavefront launches, that launch joins the device's chain of grid-barrier launches: while more than one mapper lives on
+ * a device, it starts after every such launch enqueued before it by any mapper and before any enqueued after it, so it is never
+ * resident half and half with another mapper's map update (which then waits for it).
+ * If a grid barrier of that launch times out (its workgroups were kept off the device by another process), the next sync reports
+ * GIE_ERR_TIMEOUT through the error word the map update uses, with its own message; the field is then incomplete (some values -1
+ * or too large) until the next compute; a descent stops early on it.  The map itself is not affected.
+ * gie_read_nf1*, gie_nf1_path* and gie_read_costmap_nf1* return GIE_ERR_INVALID before the first compute; a tiled mapper gets
+ * GIE_ERR_INVALID from all of them.
+ * Memory: allocated at the first compute (gie_dalloc, freed by gie_destroy): 4 bytes per voxel for the field, five bit planes with
+ * rows padded to 64-bit words (40 * ceil(X/64) / X bytes per voxel: 0.625 when X is a multiple of 64), 12 bytes per tile of
+ * 64 x 8 x 8 voxels: 4.63 bytes per voxel in all when X is a multiple of 64.  Nothing of the map update reads them. */
+#define GIE_NF1_UNKNOWN_TRAVERSABLE 1
+#define GIE_NF1_FROM_FRONTIERS 2
+typedef struct gie_nf1_param {
+    float clearance;        /* voxel units */
+    int32_t flags;          /* GIE_NF1_* */
+    int32_t reserved[2];    /* 0 */
+} gie_nf1_param;
+int gie_nf1_compute(gie_mapper *h, const float *goal_xyz, int n, const gie_nf1_param *p, int32_t *n_sources);
+int gie_nf1_compute_dev(gie_mapper *h, const float *d_goal_xyz, int n, const gie_nf1_param *p, int32_t *d_n_sources);
+int gie_read_nf1(gie_mapper *h, int32_t *nf1);
+int gie_read_nf1_dev(gie_mapper *h, int32_t *d_nf1);
+int gie_nf1_path(gie_mapper *h, const float *start_xyz, int n, int max_len, int32_t *path_xyz, int32_t *len);
+int gie_nf1_path_dev(gie_mapper *h, const float *d_start_xyz, int n, int max_len, int32_t *d_path_xyz, int32_t *d_len);
+int gie_read_costmap_nf1(gie_mapper *h, gie_seendist *payload, gie_costmap_hdr *hdr);
+int gie_read_costmap_nf1_dev(gie_mapper *h, gie_seendist *d_payload, gie_costmap_hdr *hdr);
 
 /* ---- changed-block streaming: the CPU mirror the reference keeps for RViz and CPU planners.
  * GlbHashMap::streamPipeline / streamD2H / getUpdatedAddr (glb_hash_map.cu:209-247,
