@@ -64,6 +64,17 @@ struct gie_nf1_cache {
     int pvt[3] = { 0, 0, 0 };             /* the pivot and CostMap origin at that compute */
     float origin[3] = { 0.f, 0.f, 0.f };
 };
+/* the frontier clusters (gie_frontier.inc.h): allocated at their first compute through gie_dalloc, kept until the next compute */
+struct gie_frontier_cache {
+    int32_t *planes = nullptr;            /* the union-find forest and the sizes */
+    uint64_t *bits = nullptr;             /* two bit planes */
+    int32_t *words = nullptr;             /* per-word counts and ranks, control words */
+    void *rec = nullptr;                  /* rec_cap records */
+    int rec_cap = 0;
+    int valid = 0;                        /* a compute has been enqueued */
+    int max_clusters = 0, min_size = 1;   /* of that compute */
+    int pvt[3] = { 0, 0, 0 };             /* the pivot at that compute */
+};
 struct gie_mapper {
     gie_config cfg;
     gie_ctx c;
@@ -99,6 +110,7 @@ struct gie_mapper {
     long long type_gen = 0;               /* bumped by every entry point that enqueues a kernel writing `_glb_type` (gie_fuse, gie_merge_end) */
     gie_sdf_cache sdf;                    /* the signed distance field's inside distances (HIP backend: gie_sdf.inc.h) */
     gie_nf1_cache nf1;                    /* the navigation function (HIP backend: gie_nf1.inc.h) */
+    gie_frontier_cache fr;                /* the frontier clusters (HIP backend: gie_frontier.inc.h) */
 };
 
 template <class T> static T *gie_dalloc(gie_mapper *m, size_t n, bool zero = true)

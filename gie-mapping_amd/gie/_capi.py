@@ -59,6 +59,18 @@ class Nf1Param(C.Structure):
     _fields_ = [("clearance", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class FrontierParam(C.Structure):
+    """gie_frontier_param (include/gie.h); clearance in voxel units."""
+    _fields_ = [("clearance", C.c_float), ("min_size", C.c_int32), ("connectivity", C.c_int32), ("max_clusters", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
+class FrontierCluster(C.Structure):
+    """gie_frontier_cluster (include/gie.h): 80 bytes, sum at offset 56."""
+    _fields_ = [("label", C.c_int32), ("size", C.c_int32), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("rep", C.c_int32 * 3),
+                ("centroid", C.c_float * 3), ("sum", C.c_int64 * 3)]
+
+
 NF1_UNKNOWN_TRAVERSABLE = 1
 NF1_FROM_FRONTIERS = 2
 
@@ -167,6 +179,13 @@ DEVICE_ONLY = {
     "nf1_path_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "read_costmap_nf1": (C.c_int, [_H, C.c_void_p, C.POINTER(CostMapHdr)]),
     "read_costmap_nf1_dev": (C.c_int, [_H, C.c_void_p, C.POINTER(CostMapHdr)]),
+    # frontier clusters of the local volume (include/gie.h): device library only
+    "frontier_compute": (C.c_int, [_H, C.POINTER(FrontierParam), C.c_void_p, C.c_void_p]),
+    "frontier_compute_dev": (C.c_int, [_H, C.POINTER(FrontierParam), C.c_void_p]),
+    "read_frontier_clusters": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "read_frontier_clusters_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "read_frontier_labels": (C.c_int, [_H, C.c_void_p]),
+    "read_frontier_labels_dev": (C.c_int, [_H, C.c_void_p]),
 }
 DEVICE_ONLY.update(ROUND_API)
 

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE
-from ._capi import CamParam, Config, CostMapHdr, FrameStats, MultiScanParam, Nf1Param, ScanParam, Voxel
+from ._capi import CamParam, Config, CostMapHdr, FrameStats, FrontierParam, MultiScanParam, Nf1Param, ScanParam, Voxel
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG, "csrc", "libgie_hip.so")
@@ -22,6 +22,9 @@ LIB_PATH = os.path.join(_PKG, "csrc", "libgie_hip.so")
 SEENDIST_DTYPE = np.dtype([("d", "<f4"), ("s", "u1"), ("o", "u1"), ("pad", "u1", (2,))])
 HALO_DTYPE = np.dtype([("dist_sq", "<i4"), ("coc", "<i4", (3,)), ("vox_type", "i1"), ("occ_val", "u1"), ("pad", "i1", (2,))])
 HALO_ENTRY_DTYPE = np.dtype([("index", "<i4"), ("v", HALO_DTYPE)])          # gie_halo_entry: a known voxel of a sparse face layer
+# gie_frontier_cluster: 80 bytes, the offsets of the C struct
+FRONTIER_CLUSTER_DTYPE = np.dtype([("label", "<i4"), ("size", "<i4"), ("lo", "<i4", (3,)), ("hi", "<i4", (3,)), ("rep", "<i4", (3,)),
+                                   ("centroid", "<f4", (3,)), ("sum", "<i8", (3,))])
 VOXEL_DTYPE = np.dtype([("occ_val", "u1"), ("vox_type", "i1"), ("pad", "<i2"), ("dist_sq", "<i4"),
                         ("coc", "<i4", (3,))])
 
@@ -474,6 +477,56 @@ class Mapper(MapperBase):
         hdr = CostMapHdr()
         self._chk(self._f["read_costmap_nf1_dev"](self._h, C.c_void_p(dptr or None), C.byref(hdr)))
         return hdr
+
+    # --- frontier clusters of the local volume (include/gie.h) ------------------------------
+    def frontier_param(self, clearance=0.0, min_size=1, connectivity=26, max_clusters=256):
+        """gie_frontier_param for a clearance in METRES: float32(clearance) / float32(voxel_width) voxels (as nf1_param)."""
+        p = FrontierParam()
+        p.clearance = float(np.float32(clearance) / np.float32(self.cfg.voxel_width))
+        p.min_size, p.connectivity, p.max_clusters = int(min_size), int(connectivity), int(max_clusters)
+        return p
+
+    def frontier_compute(self, clearance=0.0, min_size=1, connectivity=26, max_clusters=256):
+        """Connected components of the FNT voxels with `clearance` metres of free space, those of at least min_size voxels kept:
+        (n_clusters, n_voxels) (synchronises).  n_clusters counts every kept component, also beyond max_clusters."""
+        p = self.frontier_param(clearance, min_size, connectivity, max_clusters)
+        nc, nv = C.c_int32(0), C.c_int32(0)
+        self._chk(self._f["frontier_compute"](self._h, C.byref(p), C.byref(nc), C.byref(nv)))
+        self._frontier_cap = p.max_clusters                   # (what the readers' buffers hold)
+        return nc.value, nv.value
+
+    def frontier_compute_dev(self, clearance=0.0, min_size=1, connectivity=26, max_clusters=256, d_counts=0):
+        """The same on the mapper's stream; d_counts: 2 int32 in a DEVICE buffer (raw address; 0 = not wanted)."""
+        p = self.frontier_param(clearance, min_size, connectivity, max_clusters)
+        self._chk(self._f["frontier_compute_dev"](self._h, C.byref(p), C.c_void_p(d_counts or None)))
+        self._frontier_cap = p.max_clusters
+
+    def read_frontier_clusters(self):
+        """(records, goal_xyz, n_clusters): the records produced (FRONTIER_CLUSTER_DTYPE, ascending label; at most the compute's
+        max_clusters), the goal array [max_clusters, 3] float32 metres (NaN beyond the records) and the number of kept components
+        (synchronises)."""
+        cap = getattr(self, "_frontier_cap", 0)
+        rec = np.zeros(max(cap, 1), FRONTIER_CLUSTER_DTYPE)
+        goal = np.zeros((max(cap, 1), 3), np.float32)
+        n = C.c_int32(0)
+        self._chk(self._f["read_frontier_clusters"](self._h, _ptr(rec), _ptr(goal), C.byref(n)))
+        return rec[:min(n.value, cap)], goal[:cap], n.value
+
+    def read_frontier_clusters_dev(self, d_out, d_goal_xyz, d_n_clusters):
+        """Records (max_clusters x 80 bytes), goal points (max_clusters x 3 float32) and the count (int32) into DEVICE buffers
+        (raw addresses; 0 = not wanted), asynchronous on the mapper's stream."""
+        self._chk(self._f["read_frontier_clusters_dev"](self._h, C.c_void_p(d_out or None), C.c_void_p(d_goal_xyz or None),
+                                                        C.c_void_p(d_n_clusters or None)))
+
+    def read_frontier_labels(self):
+        """int32 label plane [Z][Y][X]: -1 not a member, -2 member of a filtered component, otherwise the label (synchronises)."""
+        out = np.empty(self._shape(), np.int32)
+        self._chk(self._f["read_frontier_labels"](self._h, _ptr(out)))
+        return out
+
+    def read_frontier_labels_dev(self, d_labels):
+        """The label plane into a device buffer (N int32, raw address), asynchronous on the mapper's stream."""
+        self._chk(self._f["read_frontier_labels_dev"](self._h, C.c_void_p(d_labels or None)))
 
     def stream_handle(self):
         """The mapper's HIP stream as an integer (for torch.cuda.ExternalStream)."""

@@ -456,6 +456,32 @@ public:
         return out;
     }
 
+    /* the frontier clusters (include/gie.h gie_frontier_compute): the connected components (connectivity 6 or 26) of the FNT voxels
+     * with clearance_m of free space, those of at least min_size voxels kept, at most max_clusters records in ascending label
+     * order; goals (3 floats per record, metres, world frame) are the records' representative voxels, ready for
+     * navigationFunction.  Returns the number of kept components (which may exceed max_clusters). */
+    int frontierClusters(float clearance_m, int min_size, int connectivity, int max_clusters, std::vector<gie_frontier_cluster> &clusters,
+                         std::vector<float> &goals)
+    {
+        gie_frontier_param p = {};
+        p.clearance = clearance_m / cfg_.voxel_width;
+        p.min_size = min_size; p.connectivity = connectivity; p.max_clusters = max_clusters;
+        int32_t n = 0, voxels = 0;
+        chk(gie_frontier_compute(m_, &p, &n, &voxels));
+        const size_t cap = (size_t)std::max(max_clusters, 0);
+        clusters.resize(std::max<size_t>(cap, 1)); goals.resize(3 * std::max<size_t>(cap, 1));
+        chk(gie_read_frontier_clusters(m_, clusters.data(), goals.data(), &n));
+        const size_t have = std::min<size_t>((size_t)n, cap);
+        clusters.resize(have); goals.resize(3 * have);
+        return n;
+    }
+    /* the label plane of the last frontierClusters: -1 not a frontier member, -2 filtered, otherwise the cluster's label; x fastest */
+    void frontierLabels(std::vector<int32_t> &labels)
+    {
+        labels.resize((size_t)cfg_.local_size[0] * cfg_.local_size[1] * cfg_.local_size[2]);
+        chk(gie_read_frontier_labels(m_, labels.data()));
+    }
+
     gie_mapper *handle() { return m_; }
     const gie_config &config() const { return cfg_; }
 

@@ -339,6 +339,68 @@ int gie_nf1_path_dev(gie_mapper *h, const float *d_start_xyz, int n, int max_len
 int gie_read_costmap_nf1(gie_mapper *h, gie_seendist *payload, gie_costmap_hdr *hdr);
 int gie_read_costmap_nf1_dev(gie_mapper *h, gie_seendist *d_payload, gie_costmap_hdr *hdr);
 
+/* ---- frontier clusters: the connected components of the local volume's FNT voxels, filtered by size, each with a goal a planner
+ * can drive to.  The reference's README says of its frontiers ("Frontiers for exploration"): "You may need to do some post-process
+ * to filter out the noise." — this is that post-process, on the device.  No counterpart in the reference's code.
+ *
+ * Everything is over the local volume at the point of the mapper's stream where gie_frontier_compute* is enqueued; type(v) and
+ * edt(v) are exactly what gie_read_local would return there.  id(v) = (z * Y + y) * X + x is the local linear index.
+ *  member(v)     type(v) == GIE_VOX_FNT and edt(v) >= clearance (a float comparison; clearance in voxel units, finite and >= 0,
+ *                otherwise GIE_ERR_INVALID: the rule of NF1's traversable, so with equal clearance every member is a legal NF1 source).
+ *  adjacent      two members that differ by at most 1 on every axis and are not equal (connectivity = 26), or that are face
+ *                neighbours (connectivity = 6).  Any other value: GIE_ERR_INVALID.  Frontier sheets are staircase surfaces: 26
+ *                is what callers normally want, 6 is the strict form.
+ *  component     a class of the transitive closure of `adjacent` inside the volume.  Its label is the smallest id of its members,
+ *                its size the number of members.  Both are independent of any schedule.
+ *  kept          size >= min_size (min_size >= 1, otherwise GIE_ERR_INVALID): the noise filter.
+ *  label plane   int32 per voxel (x fastest): -1 not a member; -2 member of a component that is not kept; otherwise the label.
+ *  cluster record  one gie_frontier_cluster per kept component, in ascending order of label.
+ *                centroid_k = ((float)((double)sum_k / (double)size) + (float)pvt_k) * w, in this order of operations.
+ *                rep: with c_k = (2 * sum_k + size) / (2 * size) (integer division: the centroid rounded half up to a voxel), the
+ *                member that minimises |v - c|^2 (integers), ties to the smaller id.  The centroid of a curved sheet is usually not
+ *                a frontier voxel and may lie inside an obstacle; rep always is a member, so with equal clearance it is a legal
+ *                NF1 goal.
+ *  capacity      max_clusters >= 0 (otherwise GIE_ERR_INVALID).  n_clusters is the number of KEPT components even when it exceeds
+ *                max_clusters; only the first max_clusters records (ascending label) are produced (the convention of
+ *                gie_nf1_path's len > max_len).  n_voxels = members in kept components.  The label plane is complete whatever
+ *                the capacity.  d_counts (device, 2 int32, may be NULL) = { n_clusters, n_voxels }.
+ *  readers       gie_read_frontier_clusters*: out and goal_xyz hold max_clusters (of the compute) entries, either may be NULL.
+ *                out: the records produced; entries beyond them are left as they are.  goal_xyz (3 floats per entry):
+ *                (float)rep_k * w for the records produced, NaN for the rest — so the whole array can be handed to
+ *                gie_nf1_compute_dev(h, d_goal_xyz, max_clusters, ...) without the host ever learning the count (NF1 ignores
+ *                goals that are not finite).  gie_pos2coord((float)rep_k * w, w) = floorf(p / w + 0.5f) gives rep_k back while
+ *                |rep_k| < 2^20: product and quotient are each off by at most a few ulp of a value below 2^20 (3 * 2^-4 of a
+ *                voxel in all), inside the half-voxel margin.  *n_clusters as the compute's.
+ * The result is kept until the next compute and refers to the pivot gie_get_pivot returned when the compute was enqueued (as NF1);
+ * map updates do not change it.  The readers return GIE_ERR_INVALID before the first compute; a NULL param and a tiled mapper
+ * (its components would stop at the tile's faces) get GIE_ERR_INVALID from all six.
+ * The host forms synchronise; the _dev forms take DEVICE buffers and are enqueued on the mapper's stream without a host wait.  A
+ * compute is a fixed sequence of launches (about a dozen, whatever the data), none with a grid barrier.
+ * Memory: allocated at the first compute (gie_dalloc, freed by gie_destroy): 8 bytes per voxel (the union-find forest and the
+ * sizes), two bit planes with rows padded to 64-bit words and 8 bytes per such word (0.375 bytes per voxel when X is a multiple of
+ * 64), and 80 bytes per record of the largest max_clusters asked for.  Nothing of the map update reads them. */
+typedef struct gie_frontier_cluster {   /* 80 bytes */
+    int32_t label;          /* smallest local linear index of a member */
+    int32_t size;
+    int32_t lo[3], hi[3];   /* bounding box, GLOBAL voxel coordinates (local + pivot), both inclusive */
+    int32_t rep[3];         /* representative member, GLOBAL voxel coordinates */
+    float centroid[3];      /* metres, world frame */
+    int64_t sum[3];         /* sums of the members' LOCAL coordinates */
+} gie_frontier_cluster;
+typedef struct gie_frontier_param {
+    float clearance;        /* voxel units */
+    int32_t min_size;
+    int32_t connectivity;   /* 6 or 26 */
+    int32_t max_clusters;
+    int32_t reserved[2];    /* 0 */
+} gie_frontier_param;
+int gie_frontier_compute(gie_mapper *h, const gie_frontier_param *p, int32_t *n_clusters, int32_t *n_voxels);
+int gie_frontier_compute_dev(gie_mapper *h, const gie_frontier_param *p, int32_t *d_counts);
+int gie_read_frontier_clusters(gie_mapper *h, gie_frontier_cluster *out, float *goal_xyz, int32_t *n_clusters);
+int gie_read_frontier_clusters_dev(gie_mapper *h, gie_frontier_cluster *d_out, float *d_goal_xyz, int32_t *d_n_clusters);
+int gie_read_frontier_labels(gie_mapper *h, int32_t *labels);
+int gie_read_frontier_labels_dev(gie_mapper *h, int32_t *d_labels);
+
 /* ---- changed-block streaming: the CPU mirror the reference keeps for RViz and CPU planners.
  * GlbHashMap::streamPipeline / streamD2H / getUpdatedAddr (glb_hash_map.cu:209-247,
  * unify_helper.cuh:11-32), fed by the stream_VB_keys_D appends of the fuse / wave / commit kernels
