@@ -9,6 +9,7 @@ import pytest
 
 import frontier_ref as fr
 import gie
+import planner_scenes as ps
 from gie import scenes
 
 pytestmark = pytest.mark.gpu
@@ -121,6 +122,25 @@ def test_exact_on_random_boxes(size):
                 for min_size in (1, 8, 200):
                     kept += _check(m, cl, conn, min_size, 64, loc=loc)["n_clusters"]
         assert kept >= 4
+    finally:
+        m.close()
+
+
+@pytest.mark.parametrize("size", ps.RIDER_SIZES, ids=lambda v: "x".join(map(str, v)))
+def test_exact_on_solid_scenes_at_flat_thin_and_long_shapes(size):
+    """X = 1, Y = 1, a partial last word of the bit rows, 16 words per row, 128 tiles along y or z: the solid scene of
+    planner_scenes, whose never-seen slab and blocks of side 3 give clusters of more than eight voxels at either connectivity"""
+    m = _mapper(size)
+    try:
+        pos, q = scenes.pose(0, 0.1, delta_vox=4, yaw_deg=0.0)
+        lab = ps.solid_labels(size, 12)                              # (a seed at which the reference keeps two clusters or more at every shape)
+        for _ in range(2):
+            _update(m, pos, q, lab)
+        loc = m.read_local(dist_sq=False, coc=False)
+        for conn in (6, 26):
+            for min_size in (1, 8):
+                assert _check(m, 0.0, conn, min_size, 64, loc=loc)["n_clusters"] >= 2      # (never two empty sets)
+        _check(m, 0.15, 26, 1, 3, loc=loc)
     finally:
         m.close()
 

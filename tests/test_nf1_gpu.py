@@ -7,6 +7,7 @@ import pytest
 
 import gie
 import nf1_ref
+import planner_scenes as ps
 from gie import scenes
 from gie._capi import CostMapHdr
 
@@ -125,6 +126,48 @@ def test_exact_on_random_boxes(size):
         assert deep >= 20
         f, *_ = _check(m, (), 0.0, loc=loc)                               # n == 0 without frontiers: no source
         assert (f == -1).all()
+    finally:
+        m.close()
+
+
+@pytest.mark.parametrize("size", ps.RIDER_SIZES, ids=lambda v: "x".join(map(str, v)))
+def test_exact_on_solid_scenes_at_flat_thin_and_long_shapes(size):
+    """X = 1, Y = 1, a partial last word of the bit rows, 16 words per row, 128 tiles along y or z: the solid scene of
+    planner_scenes (never-seen slab, blocks and specks in its free space)"""
+    rng = np.random.default_rng(sum(size))
+    m = _mapper(size)
+    try:
+        pos, q = scenes.pose(0, 0.1, delta_vox=4, yaw_deg=0.0)
+        lab = ps.solid_labels(size, 12)                              # (a seed at which the reference keeps two clusters or more at every shape)
+        for _ in range(2):
+            _update(m, pos, q, lab)
+        loc = m.read_local(dist_sq=False, coc=False)
+        assert (loc["type"] == nf1_ref.FNT).any() and (loc["type"] == nf1_ref.OCCUPIED).any() and (loc["type"] == 0).any()
+        goals = _goals(m, size, rng)
+        reached = 0
+        for cl in (0.0, 0.15):                                            # 0 and 1.5 voxels
+            for unknown in (False, True):
+                for frontiers, g in ((False, goals), (True, ()), (True, goals)):
+                    f, _, src, _ = _check(m, g, cl, unknown, frontiers, loc=loc)
+                    reached = max(reached, int((f > 0).sum()))
+        assert reached > 0
+        ax = int(np.argmax(size))
+        trav = nf1_ref.traversable(loc["type"], loc["edt"], 0.0, _flags(True, False))
+        cells = np.argwhere(trav)[:, ::-1]
+        goal = _world(m, cells[np.argsort(cells[:, ax], kind="stable")[:1]])     # ONE goal at the low end of the longest axis
+        f, trav, src, _ = _check(m, goal, 0.0, True, False, loc=loc)
+        assert src.sum() == 1
+        if size[ax] >= 1000:
+            assert f.max() >= 500                                         # the field crosses all 16 words / 128 tiles
+        reach = np.argwhere(f > 0)[:, ::-1]
+        starts = _world(m, reach[rng.choice(len(reach), 20, replace=False)], rng.uniform(-0.3, 0.3, (20, 3)))
+        for max_len in (7, int(f.max()) + 2):
+            got, glen = m.nf1_path(starts, max_len)
+            ref, rlen = nf1_ref.paths(f, starts, m.cfg.voxel_width, m.pivot(), max_len)
+            assert np.array_equal(glen, rlen)
+            for a, b in zip(got, ref):
+                assert np.array_equal(a, b)
+        assert (rlen > 0).all()
     finally:
         m.close()
 

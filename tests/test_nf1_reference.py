@@ -55,6 +55,8 @@ def _case(rng, shape, p_trav, n_src, faces=False):
     ((8, 9, 10), 1.0, 2, False),                # all traversable
     ((13, 3, 1), 0.8, 1, False),
     ((11, 12, 10), 0.45, 5, False),             # many components
+    ((19, 23, 1), 0.75, 2, True),               # array shapes [Z][Y][X]: X = 1 ...
+    ((17, 1, 29), 0.8, 2, False),               # ... and Y = 1, the flat volumes of the device test's shape table
 ])
 def test_bfs_equals_graph_shortest_paths(shape, p_trav, n_src, faces):
     rng = np.random.default_rng(sum(shape) * 7 + n_src)

@@ -4,18 +4,21 @@ import numpy as np
 import pytest
 
 import gie
+import planner_scenes as ps
 import sdf_ref
 from gie import scenes
 
 pytestmark = pytest.mark.gpu
 
 
-def _check(m, size, loc=None):
-    """read_sdf against the reference computed from read_local's types; returns (sdf, ids, loc)"""
+def _check(m, size, loc=None, ids=None):
+    """read_sdf against the reference computed from read_local's types (`ids`: inside_dist_sq of those types by another reference
+    than scipy's); returns (sdf, ids, loc)"""
     if loc is None:
         loc = m.read_local(dist_sq=False, coc=False)
     r = m.read_sdf()
-    ids = sdf_ref.inside_dist_sq(loc["type"])
+    if ids is None:
+        ids = sdf_ref.inside_dist_sq(loc["type"])
     assert np.array_equal(r["inside_dist_sq"], ids), int((r["inside_dist_sq"] != ids).sum())
     shallow = (ids >= 0) & (ids <= 1)
     assert np.array_equal(r["sdf"][shallow].view(np.uint32), loc["edt"][shallow].view(np.uint32))
@@ -347,3 +350,147 @@ def test_refusals():
     finally:
         m.close()
         t.close()
+
+
+# ---- the exact pass over its dispatch: k_sdf_line<CP, .> by max(Y, Z), long bit rows, word borders in x, axes of length 1 and 2
+
+def _solid_case(size, cp, seed, fill=0.0, w=0.1, fence=False, ids_of=None):
+    """a solid scene (planner_scenes.solid_labels) fed twice, read_sdf against the reference, the scene's properties on read_local's
+    types, and the same bytes from the planes rebuilt after a third identical update"""
+    assert ps.sdf_cp(size) == cp                               # the instantiation gie_sdf_ready selects for this shape
+    m = _mapper(size, voxel=w)
+    try:
+        pos, q = scenes.pose(0, w, delta_vox=4, yaw_deg=0.0)
+        if fence:                                              # as test_exact_with_external_boxes_and_fence, scaled to the volume
+            pvt, S = np.array(scenes.local_pivot(pos, w, size)), np.array(size)
+            ll = [(pvt + 20) * w, (pvt + S // 2 - S // 10) * w]
+            ur = [(pvt + S - 25) * w, (pvt + S // 2 + S // 8) * w]
+            m.set_ext_boxes(np.array(ll, np.float32), np.array(ur, np.float32), np.array([1, 1], np.uint8))
+        lab = ps.solid_labels(size, seed, fill)
+        for _ in range(2):
+            _update(m, pos, q, lab)
+        loc = m.read_local(dist_sq=False, coc=False)
+        sdf, ids, _ = _check(m, size, loc, None if ids_of is None else ids_of(loc["type"]))
+        if fill == 0:
+            ps.assert_scene(size, loc["type"], ids, fenced=fence)
+        elif max(size) > 2:
+            assert ids.max() >= int(fill * max(size)) ** 2     # the block at the low end: its first layer is that far from free space
+        assert size == (1, 1, 1) or (ids > 1).any()            # interior voxels: the gate cannot hide the line kernels
+        if fence:
+            assert (loc["type"] == 2).mean() > 0.2
+        _update(m, pos, q, lab)
+        r = m.read_sdf()
+        assert np.array_equal(r["inside_dist_sq"], ids) and np.array_equal(r["sdf"].view(np.uint32), sdf.view(np.uint32))
+    finally:
+        m.close()
+
+
+@pytest.mark.parametrize("size,cp", ps.SDF_SIZES, ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else "cp%d" % v)
+def test_exact_over_the_line_kernel_dispatch(size, cp):
+    _solid_case(size, cp, 1)
+    _solid_case(size, cp, 2, fill=0.45)                        # distances of almost half the longest side
+
+
+def test_exact_at_256_cube_with_interiors():
+    _solid_case((256, 256, 256), 4, 1, w=0.05, fence=True)
+
+
+def test_exact_at_512_cube_with_interiors(oracle_lib):
+    """the reference is the CPU EDT of the complement (tests/test_sdf_reference.py pins it against scipy and brute force)"""
+    from oracle_py import edt_mt
+    _solid_case((512, 512, 512), 8, 1, w=0.05, fence=True, ids_of=lambda t: ps.complement_inside_dist_sq(t, edt_mt, 16))
+
+
+# ---- key magnitude: a volume occupied but for one voxel; inside_dist_sq = (x-x0)² + (y-y0)² + (z-z0)², the largest a shape can hold
+
+def _hole_case(size, hole):
+    try:
+        m = _mapper(size, voxel=0.05, cutoff_dist=1.0)
+    except RuntimeError as e:
+        if "allocation failed" in str(e):
+            pytest.skip("the device cannot hold this volume right now: " + str(e))
+        raise
+    try:
+        pos, q = scenes.pose(0, 0.05, delta_vox=0, yaw_deg=0.0)
+        lab = ps.hole_labels(size, hole)
+        for _ in range(2):
+            _update(m, pos, q, lab)
+        loc = m.read_local(dist_sq=False, coc=False)
+        assert np.array_equal(loc["type"] == 2, lab == 2)
+        want = ps.hole_inside_dist_sq(size, hole)
+        _, ids, _ = _check(m, size, loc, want)
+        assert ids.max() == max((x - hole[0]) ** 2 + (y - hole[1]) ** 2 + (z - hole[2]) ** 2
+                                for x in (0, size[0] - 1) for y in (0, size[1] - 1) for z in (0, size[2] - 1))
+        return int(ids.max())
+    finally:
+        m.close()
+
+
+@pytest.mark.parametrize("hole", [0, 1, 2])
+@pytest.mark.parametrize("size", [(1024, 1024, 8), (1024, 8, 1024)])
+def test_one_free_voxel_in_a_thin_1024_volume(size, hole):
+    deepest = _hole_case(size, ps.hole_positions(size)[hole])
+    assert deepest == 2093107 if hole < 2 else deepest > 500000
+
+
+def test_one_free_voxel_at_1024_1024_128():
+    size = (1024, 1024, 128)                                   # gie_create accepts it: X² + Y² + Z² + 1 + max(X, Z)² = 3 162 113 < 2^22
+    deepest = [_hole_case(size, h) for h in ps.hole_positions(size)]
+    assert deepest[0] == deepest[1] == 2109187
+
+
+# ---- queries on the odd shapes
+
+def _query_case(size, dev_form):
+    import torch
+    w = 0.125                                                  # a power of two: u = p / w - pvt is exact on the faces
+    m = _mapper(size, voxel=w)
+    try:
+        pos, q = scenes.pose(0, w, delta_vox=4, yaw_deg=0.0)
+        lab = ps.solid_labels(size, 3, fill=0.4)
+        for _ in range(2):
+            _update(m, pos, q, lab)
+        r = m.read_sdf()
+        loc = m.read_local(edt=False, dist_sq=False, coc=False)
+        xyz = ps.query_points(np.random.default_rng(1), m.pivot(), size, w, 120000)
+        dist, grad, flags = m.query_sdf(xyz)
+        rd, rg, rf = sdf_ref.query(r["sdf"], loc["type"], size, m.pivot(), w, xyz)
+        assert np.array_equal(flags, rf)
+        assert (flags & 1).mean() > 0.3 and (flags == 0).any() and ((flags & 4) != 0).any()
+        assert max(size) <= 2 or ((flags & 1) != 0)[(flags & 2) == 0].any()       # a never-seen corner somewhere
+        assert np.array_equal(np.isnan(dist), np.isnan(rd))
+        ok = ~np.isnan(rd)
+        assert np.allclose(dist[ok], rd[ok], rtol=1e-5, atol=1e-5)
+        assert np.allclose(grad, rg, rtol=1e-5, atol=1e-5)
+        for k in range(3):
+            if size[k] == 1:
+                assert (grad[:, k] == 0).all()
+        # a tenth of the in-volume samples interpolate a voxel deeper than the surface: the interpolant of the indicator is positive
+        deep, _, _ = sdf_ref.query((r["inside_dist_sq"] > 1).astype(np.float32), loc["type"], size, m.pivot(), w, xyz)
+        assert (deep[ok] > 0).mean() >= 0.1
+        if dev_form:                                           # the _dev form through torch tensors on the mapper's stream
+            dev = torch.device("cuda", 0)
+            st = torch.cuda.ExternalStream(m.stream_handle(), device=dev)
+            with torch.cuda.stream(st):
+                dx = torch.from_numpy(xyz).to(dev)
+                dd = torch.empty(len(xyz), dtype=torch.float32, device=dev)
+                dg = torch.empty((len(xyz), 3), dtype=torch.float32, device=dev)
+                df = torch.empty(len(xyz), dtype=torch.uint8, device=dev)
+                m.query_sdf_dev(dx.data_ptr(), len(xyz), dd.data_ptr(), dg.data_ptr(), df.data_ptr())
+                ds = torch.empty(size[::-1], dtype=torch.float32, device=dev)
+                m.read_sdf_dev(ds.data_ptr(), 0)
+            m.sync()
+            assert np.array_equal(dd.cpu().numpy().view(np.uint32), dist.view(np.uint32))
+            assert np.array_equal(dg.cpu().numpy().view(np.uint32), grad.view(np.uint32)) and np.array_equal(df.cpu().numpy(), flags)
+            assert np.array_equal(ds.cpu().numpy().view(np.uint32), r["sdf"].view(np.uint32))
+    finally:
+        m.close()
+
+
+@pytest.mark.parametrize("size", ps.QUERY_SIZES, ids=lambda v: "x".join(map(str, v)))
+def test_queries_on_flat_thin_and_long_volumes(size):
+    _query_case(size, dev_form=size in ((1, 40, 40), (1024, 16, 12)))
+
+
+def test_queries_at_256_cube_with_interiors():
+    _query_case((256, 256, 256), dev_form=False)

@@ -7,6 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import planner_scenes as ps
 import sdf_ref
 from gie import _capi
 
@@ -130,6 +131,104 @@ def test_query_size_one_axis():
     assert ((fl & 1) == inside).all()
     assert (g[:, 2] == 0).all()
     assert np.allclose(d[inside], d[inside][0])        # constant along the flat axis
+
+
+@pytest.mark.parametrize("size", [(1, 5, 6), (6, 1, 5), (1, 1, 6), (2, 5, 2)])
+def test_query_flat_x_and_flat_y(size):
+    """a flat axis: inside for u in [-0.5, 0.5), zero gradient component, the value constant along it; a side of 2 is one cell"""
+    rng = np.random.default_rng(sum(size))
+    t, f = _field(size[::-1], rng)
+    pvt, w = (3, -4, 7), 0.25
+    n = 400
+    u = rng.uniform(0, np.maximum(np.array(size) - 1, 0), size=(n, 3)).astype(np.float32)
+    flat = [k for k in range(3) if size[k] == 1]
+    ends = np.array([-0.7, -0.5, -0.25, 0.0, 0.49, 0.5, 0.7], np.float32)
+    for k in flat:
+        u[:, k] = ends[rng.integers(0, len(ends), n)]
+    xyz = ((u + np.array(pvt, np.float32)) * np.float32(w)).astype(np.float32)
+    d, g, fl = sdf_ref.query(f, t, size, pvt, w, xyz)
+    inside = np.ones(n, bool)
+    for k in flat:
+        inside &= (u[:, k] >= -0.5) & (u[:, k] < 0.5)
+        assert (g[:, k] == 0).all()
+    assert ((fl & 1) != 0).tolist() == inside.tolist() and inside.any() and ((~inside).any() or not flat)
+    # moving a point along a flat axis inside [-0.5, 0.5) changes nothing
+    moved = u.copy()
+    for k in flat:
+        moved[:, k] = np.where(inside, 0.0, u[:, k])
+    d2, g2, fl2 = sdf_ref.query(f, t, size, pvt, w, ((moved + np.array(pvt, np.float32)) * np.float32(w)).astype(np.float32))
+    assert np.array_equal(d2[inside], d[inside]) and np.array_equal(g2, g) and np.array_equal(fl2, fl)
+    # a side of 2: the one cell 0..1, its value at the two ends of the axis is the plane's
+    for k in range(3):
+        if size[k] == 2:
+            z = np.zeros((2, 3), np.float32)
+            z[1, k] = 1.0
+            dd, _, ff = sdf_ref.query(f, t, size, pvt, w, (z + np.array(pvt, np.float32)) * np.float32(w))
+            idx = [[0, 0, 0], [0, 0, 0]]
+            idx[1][2 - k] = 1
+            assert (ff & 1).all() and np.allclose(dd, [f[tuple(i)] * w for i in idx])
+
+
+# ---- the scenes and references of the device tests on long lines and thin volumes (tests/planner_scenes.py)
+
+@pytest.mark.parametrize("size,cp", ps.SDF_SIZES + ps.BIG_SIZES[:1], ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else "cp%d" % v)
+def test_solid_scene_meets_its_requirements_at_every_shape(size, cp):
+    """on the labels: a fully labelled scan fed twice commits them (the device test asserts the same on read_local)"""
+    assert ps.sdf_cp(size) == cp
+    lab = ps.solid_labels(size, 1)
+    assert lab.shape == size[::-1] and lab.dtype == np.int8 and np.array_equal(lab, ps.solid_labels(size, 1))
+    ps.assert_scene(size, lab, sdf_ref.inside_dist_sq(lab))
+    if max(size) > 2 and max(size) <= 1024 and np.prod(size) < 10 ** 6:
+        filled = sdf_ref.inside_dist_sq(ps.solid_labels(size, 2, fill=0.45))
+        assert filled.max() >= int(0.45 * max(size)) ** 2
+
+
+def test_every_line_kernel_of_the_dispatch_is_in_the_table():
+    assert {cp for _, cp in ps.SDF_SIZES} == {1, 2, 4, 8, 16}
+    assert [ps.sdf_cp((8, y, 8)) for y in (64, 65, 128, 129, 256, 257, 512, 513, 1024)] == [1, 2, 2, 4, 4, 8, 8, 16, 16]
+    assert ps.sdf_cp((1024, 8, 8)) == 1 and ps.sdf_cp((8, 8, 600)) == 16      # by max(Y, Z): X does not count
+
+
+def test_complement_edt_is_inside_dist_sq(oracle_lib):
+    """the reference of the 512^3 device case: the project's CPU EDT on the complement of the obstacles, restricted to them"""
+    from oracle_py import edt_mt
+    mid = ps.solid_labels((96, 80, 72), 4)
+    assert np.array_equal(ps.complement_inside_dist_sq(mid, edt_mt, 4), sdf_ref.inside_dist_sq(mid))
+    thin = ps.solid_labels((16, 300, 12), 4, fill=0.45)
+    assert np.array_equal(ps.complement_inside_dist_sq(thin, edt_mt, 4), sdf_ref.inside_dist_sq(thin))
+    g = _grids()
+    for name in ("random_dense", "solid_cube", "shell_unknown_core", "all_occupied", "flat_z1", "line_x", "one_voxel"):
+        assert np.array_equal(ps.complement_inside_dist_sq(g[name], edt_mt, 2), sdf_ref.inside_dist_sq_brute(g[name])), name
+
+
+@pytest.mark.parametrize("size", [(1024, 1024, 8), (7, 5, 3)])
+def test_one_free_voxel_closed_form(size):
+    for hole in ps.hole_positions(size):
+        lab = ps.hole_labels(size, hole)
+        want = ps.hole_inside_dist_sq(size, hole)
+        assert want.dtype == np.int32 and (lab != 2).sum() == 1 and want[hole[2], hole[1], hole[0]] == 0
+        assert np.array_equal(want, sdf_ref.inside_dist_sq(lab))
+        if np.prod(size) < 1000:
+            assert np.array_equal(want, sdf_ref.inside_dist_sq_brute(lab))
+    if size[0] == 1024:
+        assert want.max() == 512 ** 2 + 512 ** 2 + 49 and ps.hole_inside_dist_sq(size, (0, 0, 0)).max() == 2093107
+
+
+def test_query_points_hit_the_faces_and_the_ends_of_flat_axes():
+    for size in ps.QUERY_SIZES:
+        pvt, w = (5, -3, 2), 0.125
+        xyz = ps.query_points(np.random.default_rng(1), pvt, size, w, 20000)
+        u = xyz / np.float32(w) - np.array(pvt, np.float32)
+        for k in range(3):
+            if size[k] == 1:
+                assert (u[:, k] == -0.5).any() and (u[:, k] == 0.5).any() and (np.abs(u[:, k]) <= 0.7).all()
+            else:
+                assert (u[:, k] == 0).any() and (u[:, k] == size[k] - 1).any() and (u[:, k] < 0).any() and (u[:, k] > size[k] - 1).any()
+        # with the labels for types: a tenth of the in-volume samples have a corner deeper than the surface
+        lab = ps.solid_labels(size, 3, fill=0.4)
+        ids = sdf_ref.inside_dist_sq(lab)
+        deep, _, fl = sdf_ref.query((ids > 1).astype(np.float32), lab, size, pvt, w, xyz)
+        assert (fl & 1).mean() > 0.3 and (deep[(fl & 1) != 0] > 0).mean() >= 0.1, size
 
 
 def _declared():
