@@ -417,7 +417,7 @@ static int gie_need_pose(gie_mapper *m, const char *who)
 static void gie_labels_materialise(gie_mapper *m)
 {
     if (!m->labels_pending) return;
-    be_labels(&m->be, m->c, m->labels_pending, 0);
+    be_labels(&m->be, m->c, m->labels_pending);       /* (the storing form: it flags the blocks as every other scan does) */
     m->labels_pending = nullptr; m->c.scan_labels = nullptr;
 }
 
@@ -504,11 +504,13 @@ static int gie_ogm_labels_dev_impl(gie_mapper *m, const int8_t *d_labels, int ma
     gie_labels_materialise(m);
     m->c.pntcld_mode = 0;
     be_time(&m->be, 0);
-    /* The plane stays where it is when the caller allows it and the device form applies: this launch only flags the blocks of the
-     * observed voxels, gie_fuse reads the labels from d_labels itself (1 byte written and 1 byte re-read and reset per voxel less:
-     * 0.4 GB of a 512^3 update).  d_labels must then not change before gie_fuse has run (include/gie.h: gie_ogm_labels_dev_borrow). */
+    /* The plane stays where it is when the caller allows it and the device form applies: nothing is launched here (no profile
+     * bracket either: a stage without a kernel is not a stage).  gie_fuse reads the labels from d_labels itself (1 byte written and
+     * 1 byte re-read and reset per voxel less: 0.4 GB of a 512^3 update), and its block allocation looks at them where a block is
+     * missing instead of at flags (k_cell_alloc, gie_block_observed).  d_labels must then not change before gie_fuse has run
+     * (include/gie.h: gie_ogm_labels_dev_borrow). */
     const int in_place = may_borrow && be_labels_in_place_ok(m->c, d_labels);
-    be_prof(&m->be, GIE_K_CLASSIFY, 0); be_labels(&m->be, m->c, d_labels, in_place); be_prof(&m->be, GIE_K_CLASSIFY, 1);
+    if (!in_place) { be_prof(&m->be, GIE_K_CLASSIFY, 0); be_labels(&m->be, m->c, d_labels); be_prof(&m->be, GIE_K_CLASSIFY, 1); }
     be_time(&m->be, 1);
     if (in_place) { m->labels_pending = d_labels; m->c.scan_labels = d_labels; }
     m->has_ogm = 1;

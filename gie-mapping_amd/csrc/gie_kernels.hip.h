@@ -95,8 +95,8 @@ __global__ __launch_bounds__(256) void k_lin(const gie_ctx c, const F f, const i
 }
 
 /* gie_ogm_labels for X % 16 == 0 without a robot sphere: a thread moves 16 voxels of a row (one
- * 16-byte load, one 16-byte store) and flags the (at most three) blocks its observed voxels lie in */
-template <bool STORE>
+ * 16-byte load, one 16-byte store) and flags the (at most three) blocks its observed voxels lie in.  (A plane gie_fuse reads in
+ * place gets no launch at all: k_cell_alloc looks at its labels where a block is missing, gie_block_observed.) */
 __global__ __launch_bounds__(256) void k_labels16(const gie_ctx c, const int8_t *labels, const int nvec)
 {
     const int v = blockIdx.x * 256 + threadIdx.x;
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256) void k_labels16(const gie_ctx c, const int8_t 
             known |= (ok ? 1u : 0u) << (4 * j + b);
         }
     }
-    if (STORE) reinterpret_cast<uint4 *>(c.inst_type)[v] = make_uint4(w[0], w[1], w[2], w[3]);      /* (!STORE: gie_fuse reads the caller's plane itself, c.scan_labels) */
+    reinterpret_cast<uint4 *>(c.inst_type)[v] = make_uint4(w[0], w[1], w[2], w[3]);
     if (!known) return;
     const int gx0 = x0 + c.pvt[0], gy = y + c.pvt[1], gz = z + c.pvt[2];
     const int cell0 = (((gz >> 3) - c.tb0[2]) * c.tdim[1] + ((gy >> 3) - c.tb0[1])) * c.tdim[0] - c.tb0[0];
@@ -370,7 +370,9 @@ __global__ __launch_bounds__(256) void k_cell_alloc(const gie_ctx c, const int n
         const int bx = i % c.tdim[0], by = (i / c.tdim[0]) % c.tdim[1], bz = i / (c.tdim[0] * c.tdim[1]);
         found = gie_cell_prev_slot(c, bx, by, bz);   /* one coalesced read instead of a chain of hash probes for every block the table before knew */
         if (found < 0) found = gie_hash_find(c, bx + c.tb0[0], by + c.tb0[1], bz + c.tb0[2]);
-        isnew = found < 0 && c.blk_need[i];
+        /* a label plane left in place has flagged nothing: its labels are looked at here, only where no block exists yet (on a drive
+         * that is the layer of cells the volume moved onto, not the volume) */
+        isnew = found < 0 && (c.blk_need[i] || (c.scan_labels && gie_block_observed(c, c.scan_labels, bx, by, bz)));
         c.blk_need[i] = 0;
     }
     /* Slots for the new blocks: ONE set of counter updates per workgroup (ballot inside the wavefronts, prefix across them in LDS).
@@ -2345,7 +2347,6 @@ __global__ __launch_bounds__(64 * GIE_FF_WAVES) void k_frontier_faces(const gie_
  * takes unaligned vectors), rows cut by a face of the volume fall back to per-voxel accesses.  The
  * thread-per-z-column sweeps (k_voxa) this replaces moved 8-voxel pieces of eight blocks per
  * instruction with one 1/4/8-byte access per voxel. */
-typedef uint64_t __attribute__((aligned(1))) gie_u64u;
 typedef uint32_t gie_v4 __attribute__((ext_vector_type(4)));
 typedef gie_v4 __attribute__((aligned(4))) gie_v4u;                 /* 16 bytes at any 4-byte boundary */
 __device__ __forceinline__ uint4 gie_ld16u(const void *p) { const gie_v4 v = *reinterpret_cast<const gie_v4u *>(p); return make_uint4(v.x, v.y, v.z, v.w); }

@@ -348,6 +348,54 @@ GIE_DEV int gie_cell_prev_slot(const gie_ctx &c, int bx, int by, int bz)
     return found;
 }
 
+/* ---- a label plane left in place (c.scan_labels, gie_ogm_labels_dev_borrow): was a table cell's block observed?
+ * Nobody flags c.blk_need for such a scan (a pass over the whole plane for flags that matter only where no block exists yet): the
+ * allocation asks here, for the cells both of its lookups have missed. */
+typedef uint64_t __attribute__((aligned(1))) gie_u64u;               /* 8 bytes at any address */
+/* nonzero iff one of the eight label bytes is an observation: FREE or OCCUPIED and nothing else (k_labels16's predicate; the zero-byte
+ * test of gie_fuse_row8_labels) */
+GIE_DEV uint64_t gie_row8_observed(uint64_t it8)
+{
+    const uint64_t ONES = 0x0101010101010101ull, L7 = 0x7f7f7f7f7f7f7f7full, H8 = 0x8080808080808080ull;
+    const uint64_t tf = it8 ^ ONES, to = it8 ^ (2ull * ONES);
+    const uint64_t zf = ((((tf & L7) + L7) | tf) & H8) ^ H8, zo = ((((to & L7) + L7) | to) & H8) ^ H8;
+    return zf | zo;
+}
+/* Does `labels` (the X·Y·Z bytes of the local volume, x fastest) hold an observed voxel of global block (bx + tb0[0], by + tb0[1],
+ * bz + tb0[2])?  The pivot need not be block aligned: the block's local box is the block clipped to the volume, and NO byte outside
+ * the plane is read — a row the x faces cut goes byte by byte (as gie_row_ld8), rows and layers beyond the y / z faces are not
+ * touched.  An uncut row is one unaligned 8-byte load; adjacent table cells are adjacent in x, so the loads of a wavefront for one
+ * (y, z) are one 512-byte run.  The eight rows of a z layer are issued together and the answer leaves after the first layer that
+ * holds an observation: a fully observed block costs one trip, a fresh map with nothing observed a streaming read of the plane
+ * with eight loads in flight per lane. */
+GIE_DEV int gie_block_observed(const gie_ctx &c, const int8_t *labels, int bx, int by, int bz)
+{
+    const int x0 = (bx + c.tb0[0]) * 8 - c.pvt[0], y0 = (by + c.tb0[1]) * 8 - c.pvt[1], z0 = (bz + c.tb0[2]) * 8 - c.pvt[2];
+    const int xlo = x0 < 0 ? -x0 : 0, xhi = c.X - x0 < 8 ? c.X - x0 : 8;
+    const int ylo = y0 < 0 ? -y0 : 0, yhi = c.Y - y0 < 8 ? c.Y - y0 : 8;
+    const int zlo = z0 < 0 ? -z0 : 0, zhi = c.Z - z0 < 8 ? c.Z - z0 : 8;
+    if (xlo >= xhi || ylo >= yhi || zlo >= zhi) return 0;            /* the block has no voxel in the volume */
+    const bool full = xhi - xlo == 8;
+    const long long plane = (long long)c.X * c.Y;
+    for (int k = zlo; k < zhi; k++) {
+        const long long id0 = (long long)(z0 + k) * plane + (long long)y0 * c.X + x0;      /* (may lie before the plane: only indices inside it are formed into addresses) */
+        uint64_t v[8];
+        GIE_UNROLL
+        for (int j = 0; j < 8; j++) {
+            v[j] = 0;
+            if (j < ylo || j >= yhi) continue;
+            const long long id = id0 + (long long)j * c.X;
+            if (full) v[j] = *reinterpret_cast<const gie_u64u *>(labels + id);
+            else for (int i = xlo; i < xhi; i++) v[j] |= (uint64_t)(uint8_t)labels[id + i] << (8 * i);
+        }
+        uint64_t seen = 0;
+        GIE_UNROLL
+        for (int j = 0; j < 8; j++) seen |= gie_row8_observed(v[j]);
+        if (seen) return 1;
+    }
+    return 0;
+}
+
 /* ---- block-pool lifecycle (gie_config.retain_radius_blocks > 0; the reference never erases: blockalloc.h:50-67) */
 /* Slot `r` of `cnt` blocks a caller allocates at once: the first `nf` come from the top of the free list (entries
  * [ftop - nf, ftop)), the rest from the bump allocator starting at `base`. */

@@ -180,7 +180,8 @@ int gie_ogm_labels(gie_mapper *h, const int8_t *labels);
 int gie_ogm_labels_dev(gie_mapper *h, const int8_t *d_labels);
 /* _dev_borrow (round 6; rounds 5's gie_ogm_labels_dev did this unasked): the plane MAY be read IN PLACE by gie_fuse instead (no copy
  * into `_inst_type`, no reset of it: 2 bytes per voxel less) — when the volume's X is a multiple of 16, d_labels is 16-byte aligned and
- * for_motion_planner is off; *borrowed (may be NULL) says whether it is.  A borrowed plane must stay unchanged until the gie_fuse /
+ * for_motion_planner is off; *borrowed (may be NULL) says whether it is.  The call itself then launches nothing: gie_fuse reads the
+ * labels, its block allocation included (only where a block is missing).  A borrowed plane must stay unchanged until the gie_fuse /
  * gie_step of this map update has been executed on the mapper's stream — or until another gie_ogm_* / gie_read_ogm call, which
  * copies it first. */
 int gie_ogm_labels_dev_borrow(gie_mapper *h, const int8_t *d_labels, int *borrowed);
