@@ -13,12 +13,12 @@
 
 enum { GIE_K_CLASSIFY = 0, GIE_K_RAY_REGISTER, GIE_K_RAY_FREE, GIE_K_RAY_FINAL, GIE_K_ALLOC, GIE_K_FUSE, GIE_K_EDT_Y, GIE_K_EDT_X,
        GIE_K_EDT_Z, GIE_K_MARK, GIE_K_FRONTIER, GIE_K_WAVE_A, GIE_K_WAVE_B, GIE_K_WAVE_C, GIE_K_COMMIT, GIE_K_EDT_ZFACES, GIE_K_MARKC,
-       GIE_K_SDF, GIE_K_SDF_QUERY, GIE_K_NUM };   /* (the signed distance field's ids come last: the others keep their indices) */
+       GIE_K_LOS, GIE_K_LOS_QUERY, GIE_K_SDF, GIE_K_SDF_QUERY, GIE_K_NUM };   /* (the signed distance field's ids come last, as gie.h says; the map update's keep their indices) */
 #include <cstdio>
 #include <unistd.h>
 static const char *const gie_kernel_names[GIE_K_NUM] = { "ogm_classify", "ray_register", "ray_free", "ray_finalize", "block_alloc", "fuse",
        "edt_pass_y", "edt_pass_x", "edt_pass_z", "mark", "frontiers", "wave_a", "wave_b", "waves", "commit", "edt_prep", "mark_commit",
-       "sdf", "sdf_query" };
+       "los", "los_query", "sdf", "sdf_query" };
 
 #define GIE_REHASH_PERIOD 64                 /* map updates between two rebuilds of the hash table while blocks are being erased */
 static thread_local std::string g_gie_err;
@@ -75,6 +75,15 @@ struct gie_frontier_cache {
     int max_clusters = 0, min_size = 1;   /* of that compute */
     int pvt[3] = { 0, 0, 0 };             /* the pivot at that compute */
 };
+/* line of sight (gie_los.inc.h): allocated at the first prepare through gie_dalloc, kept until the next prepare */
+struct gie_los_cache {
+    uint64_t *bits = nullptr;             /* the opaque bit plane */
+    int8_t *type = nullptr;               /* the types at the prepare */
+    float *edt = nullptr;                 /* edt at the prepare */
+    int32_t *words = nullptr;             /* control words (the count of opaque voxels) */
+    int valid = 0;                        /* a prepare has been enqueued */
+    int pvt[3] = { 0, 0, 0 };             /* the pivot at that prepare */
+};
 struct gie_mapper {
     gie_config cfg;
     gie_ctx c;
@@ -111,6 +120,7 @@ struct gie_mapper {
     gie_sdf_cache sdf;                    /* the signed distance field's inside distances (HIP backend: gie_sdf.inc.h) */
     gie_nf1_cache nf1;                    /* the navigation function (HIP backend: gie_nf1.inc.h) */
     gie_frontier_cache fr;                /* the frontier clusters (HIP backend: gie_frontier.inc.h) */
+    gie_los_cache los;                    /* line of sight (HIP backend: gie_los.inc.h) */
 };
 
 template <class T> static T *gie_dalloc(gie_mapper *m, size_t n, bool zero = true)

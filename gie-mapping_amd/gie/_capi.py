@@ -71,8 +71,36 @@ class FrontierCluster(C.Structure):
                 ("centroid", C.c_float * 3), ("sum", C.c_int64 * 3)]
 
 
+class LosParam(C.Structure):
+    """gie_los_param (include/gie.h); clearance in voxel units."""
+    _fields_ = [("clearance", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class LosHit(C.Structure):
+    """gie_los_hit (include/gie.h): 24 bytes."""
+    _fields_ = [("first", C.c_int32), ("len", C.c_int32), ("hit", C.c_int32 * 3), ("min_edt", C.c_float)]
+
+
+class View(C.Structure):
+    """gie_view (include/gie.h): 64 bytes."""
+    _fields_ = [("pos", C.c_float * 3), ("n_planes", C.c_int32), ("normal", (C.c_int32 * 3) * 4)]
+
+
+class ViewParam(C.Structure):
+    """gie_view_param (include/gie.h); ranges in metres."""
+    _fields_ = [("r_min", C.c_float), ("r_max", C.c_float), ("tan2_elev", C.c_float), ("reserved", C.c_int32)]
+
+
+class ViewScore(C.Structure):
+    """gie_view_score (include/gie.h): 16 bytes."""
+    _fields_ = [("unknown", C.c_int32), ("frontier", C.c_int32), ("occupied", C.c_int32), ("candidates", C.c_int32)]
+
+
+assert C.sizeof(LosHit) == 24 and C.sizeof(View) == 64 and C.sizeof(ViewScore) == 16 and C.sizeof(LosParam) == 16 and C.sizeof(ViewParam) == 16
+
 NF1_UNKNOWN_TRAVERSABLE = 1
 NF1_FROM_FRONTIERS = 2
+LOS_UNKNOWN_OPAQUE = 1
 
 
 class CostMapHdr(C.Structure):
@@ -186,6 +214,15 @@ DEVICE_ONLY = {
     "read_frontier_clusters_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p]),
     "read_frontier_labels": (C.c_int, [_H, C.c_void_p]),
     "read_frontier_labels_dev": (C.c_int, [_H, C.c_void_p]),
+    # line of sight over the local volume (include/gie.h): device library only
+    "los_prepare": (C.c_int, [_H, C.POINTER(LosParam), C.c_void_p]),
+    "los_prepare_dev": (C.c_int, [_H, C.POINTER(LosParam), C.c_void_p]),
+    "read_los_opaque": (C.c_int, [_H, C.c_void_p]),
+    "read_los_opaque_dev": (C.c_int, [_H, C.c_void_p]),
+    "los_segments": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "los_segments_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "view_gain": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(ViewParam), C.c_void_p]),
+    "view_gain_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(ViewParam), C.c_void_p]),
 }
 DEVICE_ONLY.update(ROUND_API)
 

@@ -13,8 +13,8 @@ import sys
 import numpy as np
 
 from . import _capi
-from ._capi import NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE
-from ._capi import CamParam, Config, CostMapHdr, FrameStats, FrontierParam, MultiScanParam, Nf1Param, ScanParam, Voxel
+from ._capi import LOS_UNKNOWN_OPAQUE, NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE
+from ._capi import CamParam, Config, CostMapHdr, FrameStats, FrontierParam, LosParam, MultiScanParam, Nf1Param, ScanParam, ViewParam, Voxel
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG, "csrc", "libgie_hip.so")
@@ -25,6 +25,10 @@ HALO_ENTRY_DTYPE = np.dtype([("index", "<i4"), ("v", HALO_DTYPE)])          # gi
 # gie_frontier_cluster: 80 bytes, the offsets of the C struct
 FRONTIER_CLUSTER_DTYPE = np.dtype([("label", "<i4"), ("size", "<i4"), ("lo", "<i4", (3,)), ("hi", "<i4", (3,)), ("rep", "<i4", (3,)),
                                    ("centroid", "<f4", (3,)), ("sum", "<i8", (3,))])
+# gie_los_hit (24 bytes), gie_view (64 bytes), gie_view_score (16 bytes)
+LOS_HIT_DTYPE = np.dtype([("first", "<i4"), ("len", "<i4"), ("hit", "<i4", (3,)), ("min_edt", "<f4")])
+VIEW_DTYPE = np.dtype([("pos", "<f4", (3,)), ("n_planes", "<i4"), ("normal", "<i4", (4, 3))])
+VIEW_SCORE_DTYPE = np.dtype([("unknown", "<i4"), ("frontier", "<i4"), ("occupied", "<i4"), ("candidates", "<i4")])
 VOXEL_DTYPE = np.dtype([("occ_val", "u1"), ("vox_type", "i1"), ("pad", "<i2"), ("dist_sq", "<i4"),
                         ("coc", "<i4", (3,))])
 
@@ -60,6 +64,32 @@ def make_config(voxel_width, local_size, occupancy_threshold=180, ogm_min_h=-100
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def view_frustum(yaw, pitch, hfov, vfov):
+    """The four inward normals (int32 [4, 3]) of a camera frustum for gie_view.normal: the camera looks along +x turned by `yaw`
+    about z and tilted up by `pitch` (radians), with full opening angles hfov and vfov (each below pi).  Every normal is the unit
+    normal times 16384, rounded to integers: a quantisation of the angles to about 1e-4 rad — the planes that are tested are exactly
+    these integer ones (include/gie.h), the angles they stand for differ from the arguments by that much."""
+    cy, sy, cp, sp = math.cos(yaw), math.sin(yaw), math.cos(pitch), math.sin(pitch)
+    fwd = np.array([cp * cy, cp * sy, sp])
+    left = np.array([-sy, cy, 0.0])
+    up = np.array([-sp * cy, -sp * sy, cp])
+    ch, sh, cv, sv = math.cos(hfov / 2), math.sin(hfov / 2), math.cos(vfov / 2), math.sin(vfov / 2)
+    n = [sh * fwd + ch * left, sh * fwd - ch * left, sv * fwd + cv * up, sv * fwd - cv * up]
+    return np.array([np.rint(16384.0 * v) for v in n]).astype(np.int32)
+
+
+def make_views(pos, normals=None):
+    """gie_view records (VIEW_DTYPE [n]) from positions (n x 3 metres) and, for all of them, one set of 0..4 normals (k x 3 integers)."""
+    pos = np.asarray(pos, dtype=np.float32).reshape(-1, 3)
+    v = np.zeros(len(pos), VIEW_DTYPE)
+    v["pos"] = pos
+    if normals is not None:
+        nm = np.asarray(normals, dtype=np.int32).reshape(-1, 3)
+        v["n_planes"] = len(nm)
+        v["normal"][:, :min(len(nm), 4)] = nm[:4]
+    return v
 
 
 class MapperBase:
@@ -567,3 +597,67 @@ class Mapper(MapperBase):
     def ogm_multiscan_dev(self, dptr, scan_num, ring_num, theta_inc, theta_min, phi_inc, phi_min, max_r=100.0):
         p = MultiScanParam(scan_num, ring_num, max_r, theta_inc, theta_min, phi_inc, phi_min)
         self._chk(self._f["ogm_multiscan_dev"](self._h, C.c_void_p(dptr), C.byref(p)))
+
+    # --- line of sight over the local volume (include/gie.h) --------------------------------
+    def los_param(self, clearance=0.0, flags=0):
+        """gie_los_param for a clearance in METRES: float32(clearance) / float32(voxel_width) voxels (as frontier_param)."""
+        p = LosParam()
+        p.clearance = float(np.float32(clearance) / np.float32(self.cfg.voxel_width))
+        p.flags = int(flags)
+        return p
+
+    def los_prepare(self, clearance=0.0, flags=0):
+        """The opaque plane of the current map (clearance in metres, flags: LOS_UNKNOWN_OPAQUE); returns the number of opaque
+        voxels (synchronises)."""
+        p = self.los_param(clearance, flags)
+        n = C.c_int32(0)
+        self._chk(self._f["los_prepare"](self._h, C.byref(p), C.byref(n)))
+        return n.value
+
+    def los_prepare_dev(self, clearance=0.0, flags=0, d_n_opaque=0):
+        """The same on the mapper's stream; d_n_opaque: one int32 in a DEVICE buffer (raw address; 0 = not wanted)."""
+        p = self.los_param(clearance, flags)
+        self._chk(self._f["los_prepare_dev"](self._h, C.byref(p), C.c_void_p(d_n_opaque or None)))
+
+    def read_los_opaque(self):
+        """uint8 plane [Z][Y][X] of 0 / 1 (synchronises)."""
+        out = np.empty(self._shape(), np.uint8)
+        self._chk(self._f["read_los_opaque"](self._h, _ptr(out)))
+        return out
+
+    def read_los_opaque_dev(self, d_opaque):
+        """The plane into a device buffer (N bytes, raw address), asynchronous on the mapper's stream."""
+        self._chk(self._f["read_los_opaque_dev"](self._h, C.c_void_p(d_opaque or None)))
+
+    def los_segments(self, a, b):
+        """n segments between points a and b (n x 3 metres, world frame) -> LOS_HIT_DTYPE [n] (synchronises)."""
+        a = np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(-1, 3))
+        b = np.ascontiguousarray(np.asarray(b, dtype=np.float32).reshape(-1, 3))
+        if len(a) != len(b):
+            raise ValueError("los_segments: as many start points as end points")
+        out = np.zeros(len(a), LOS_HIT_DTYPE)
+        self._chk(self._f["los_segments"](self._h, _ptr(a), _ptr(b), len(a), _ptr(out)))
+        return out
+
+    def los_segments_dev(self, d_a, d_b, n, d_out):
+        """n segments with endpoints (n x 3 float32 each) and results (n x 24 bytes) in DEVICE buffers (raw addresses)."""
+        self._chk(self._f["los_segments_dev"](self._h, C.c_void_p(d_a or None), C.c_void_p(d_b or None), int(n), C.c_void_p(d_out or None)))
+
+    def view_param(self, r_min=0.0, r_max=1.0, tan2_elev=-1.0):
+        p = ViewParam()
+        p.r_min, p.r_max, p.tan2_elev = float(np.float32(r_min)), float(np.float32(r_max)), float(np.float32(tan2_elev))
+        return p
+
+    def view_gain(self, views, r_min=0.0, r_max=1.0, tan2_elev=-1.0):
+        """Scores of n views (VIEW_DTYPE, see make_views; ranges in metres; tan2_elev < 0: no band) -> VIEW_SCORE_DTYPE [n]
+        (synchronises)."""
+        v = np.ascontiguousarray(np.asarray(views, dtype=VIEW_DTYPE).reshape(-1))
+        p = self.view_param(r_min, r_max, tan2_elev)
+        out = np.zeros(len(v), VIEW_SCORE_DTYPE)
+        self._chk(self._f["view_gain"](self._h, _ptr(v), len(v), C.byref(p), _ptr(out)))
+        return out
+
+    def view_gain_dev(self, d_views, n, d_out, r_min=0.0, r_max=1.0, tan2_elev=-1.0):
+        """n views (n x 64 bytes) and scores (n x 16 bytes) in DEVICE buffers (raw addresses), on the mapper's stream."""
+        p = self.view_param(r_min, r_max, tan2_elev)
+        self._chk(self._f["view_gain_dev"](self._h, C.c_void_p(d_views or None), int(n), C.byref(p), C.c_void_p(d_out or None)))

@@ -482,6 +482,34 @@ public:
         chk(gie_read_frontier_labels(m_, labels.data()));
     }
 
+    /* line of sight (include/gie.h gie_los_prepare): the opaque plane of the current map — OCCUPIED, UNKNOWN too with
+     * GIE_LOS_UNKNOWN_OPAQUE, and everything closer than clearance_m to an obstacle; returns the number of opaque voxels.
+     * lineOfSight / viewGain refer to it until the next call, whatever the map does meanwhile. */
+    int losPrepare(float clearance_m, int flags)
+    {
+        gie_los_param p = {};
+        p.clearance = clearance_m / cfg_.voxel_width;
+        p.flags = flags;
+        int32_t n = 0;
+        chk(gie_los_prepare(m_, &p, &n));
+        return n;
+    }
+    /* n segments a -> b (3 floats per point, metres, world frame): first opaque voxel, length, minimum clearance along each */
+    void lineOfSight(const float *a_xyz, const float *b_xyz, int n, std::vector<gie_los_hit> &hits)
+    {
+        hits.resize((size_t)std::max(n, 0));
+        chk(gie_los_segments(m_, a_xyz, b_xyz, n, hits.data()));
+    }
+    /* what a sensor of range [r_min_m, r_max_m] (tan2_elev < 0: no vertical band) would see from each view: the visible UNKNOWN,
+     * FNT and OCCUPIED voxels and the number of candidates */
+    void viewGain(const std::vector<gie_view> &views, float r_min_m, float r_max_m, float tan2_elev, std::vector<gie_view_score> &scores)
+    {
+        gie_view_param vp = {};
+        vp.r_min = r_min_m; vp.r_max = r_max_m; vp.tan2_elev = tan2_elev;
+        scores.resize(views.size());
+        chk(gie_view_gain(m_, views.data(), (int)views.size(), &vp, scores.data()));
+    }
+
     gie_mapper *handle() { return m_; }
     const gie_config &config() const { return cfg_; }
 

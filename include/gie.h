@@ -402,6 +402,93 @@ int gie_read_frontier_clusters_dev(gie_mapper *h, gie_frontier_cluster *d_out, f
 int gie_read_frontier_labels(gie_mapper *h, int32_t *labels);
 int gie_read_frontier_labels_dev(gie_mapper *h, int32_t *d_labels);
 
+/* ---- line of sight: is the straight segment between two points clear, and how much would a sensor see from a pose?  The two
+ * questions between "clusters with goals" and "drive there": shortcutting gie_nf1_path's staircase, the collision test of a sampling
+ * planner, the information-gain half of frontier exploration.  The reference's README: "To access the global EDT directly, you are
+ * recommended to implement a GPU-based motion planner together with GIE-mapping."  No counterpart in the reference's code.
+ *
+ * Everything is over the local volume at the point of the mapper's stream where gie_los_prepare* is enqueued; type(v) and edt(v) are
+ * exactly what gie_read_local would return there.  Every later call refers to that prepare and its pivot until the next prepare;
+ * map updates do not change a result (as NF1 and the clusters).
+ *  opaque(v)     type(v) == GIE_VOX_OCCUPIED, or type(v) == GIE_VOX_UNKNOWN with GIE_LOS_UNKNOWN_OPAQUE, or clearance > 0 and
+ *                edt(v) < clearance (a float comparison; clearance in voxel units, finite and >= 0, otherwise GIE_ERR_INVALID:
+ *                NF1's rule).  With clearance == 0 edt(v) has no part in it.  Flags other than GIE_LOS_UNKNOWN_OPAQUE:
+ *                GIE_ERR_INVALID.  n_opaque = the number of opaque voxels (host int32 / device int32 of the caller's, may be NULL).
+ *  voxel line    L(a, b), for local voxels a and b: the voxels whose cube shares a piece of POSITIVE length with the straight
+ *                segment between the two voxel centres, in the order of those pieces from a to b.  L(a, a) = (a).  The walk: with
+ *                n_k = |b_k - a_k|, crossing j (1..n_k) of axis k lies at t = (2j - 1) / (2 n_k); take the smallest pending t and
+ *                step ALL axes tied at it together, until none is pending.  A line through an edge or a corner of the grid makes
+ *                a diagonal move: the voxels that touch it only there are not on it.  (2 j_a - 1) * n_b against (2 j_b - 1) * n_a
+ *                decides the order of two crossings, exactly in 32-bit integers (gie_create keeps every side <= 1024).
+ *                L(b, a) is L(a, b) reversed; no voxel repeats; 1 + max n_k <= len <= 1 + n_x + n_y + n_z.
+ *  segment       a pair of points (metres, world frame), each mapped like NF1's goals: gie_pos2coord(p_k, w) - pvt_k.  Result,
+ *                one gie_los_hit per segment:
+ *                  first    index along L(a, b) of the first opaque voxel (a has index 0); -1 when none is opaque; -2 when an
+ *                           endpoint is not finite or lies outside the volume (every other field is then 0);
+ *                  len      the number of voxels of L(a, b);
+ *                  hit      the first opaque voxel, GLOBAL coordinates (local + pivot); b's when first == -1;
+ *                  min_edt  the minimum of edt(v) over the voxels of index 0 .. first (all of the line when first == -1): the
+ *                           exact float minimum of the values at prepare time, voxel units.
+ *  view gain     per gie_view, with p = the voxel of pos (mapped like a segment's endpoint), d = v - p, rmin = r_min / w and
+ *                rmax = r_max / w (float), voxel v is a CANDIDATE iff
+ *                  v is inside the volume and v != p;
+ *                  (float)|d|^2 >= rmin * rmin and (float)|d|^2 <= rmax * rmax (|d|^2 is an exact integer below 2^24: one
+ *                  float product and one comparison on each side);
+ *                  tan2_elev < 0, or (float)(d_z^2) <= tan2_elev * (float)(d_x^2 + d_y^2): the vertical band of a spinning lidar;
+ *                  normal[i] . d >= 0 (an exact 64-bit integer dot product) for each i < n_planes: four planes make a camera's
+ *                  frustum.
+ *                A candidate is VISIBLE iff no voxel of L(p, v) other than v itself is opaque; p's own opacity is ignored, v may
+ *                be anything.  gie_view_score: unknown / frontier / occupied = the visible candidates of type UNKNOWN / FNT /
+ *                OCCUPIED, candidates = all candidates; all four are -1 when pos is not finite or lies outside the volume.  The
+ *                counts are sums: they depend on no schedule.
+ *                Refused with GIE_ERR_INVALID: r_min or r_max not finite, r_min < 0, r_min > r_max, tan2_elev NaN; in the host
+ *                form also a view with n_planes outside 0..4 or a component of one of its n_planes normals beyond +-32767.  The
+ *                _dev form never reads the views on the host: such a view scores -1 in all four fields there.
+ * Arguments follow the NF1 section: n == 0 is valid; a NULL param, a NULL buffer that would be read or written, n < 0:
+ * GIE_ERR_INVALID.  Everything but gie_los_prepare* returns GIE_ERR_INVALID before the first prepare.  A tiled mapper gets
+ * GIE_ERR_INVALID from all ten: its lines would stop at the tile's faces.  The host forms synchronise (gie_los_prepare also when
+ * n_opaque is NULL); the _dev forms take DEVICE buffers and are enqueued on the mapper's stream without a host wait.  Every call
+ * is a fixed sequence of launches, none with a grid barrier.
+ * gie_read_los_opaque*: N bytes of 0 / 1, x fastest.
+ * Memory: allocated at the first prepare (gie_dalloc, freed by gie_destroy): the opaque bit plane with rows padded to 64-bit words
+ * (8 * ceil(X/64) / X bytes per voxel: 0.125 when X is a multiple of 64), the types (1 byte per voxel) and edt (4 bytes per voxel)
+ * of the prepare — a segment's min_edt and a view's counts have to be those of the prepare whatever the map does afterwards, so
+ * they are copies.  Nothing of the map update reads them; a mapper that never calls gie_los_prepare* allocates and launches nothing.
+ * gie_profile_read: "los" = prepare and the plane's reader, "los_query" = segments and gain (the two entries before "sdf"). */
+#define GIE_LOS_UNKNOWN_OPAQUE 1
+typedef struct gie_los_param {
+    float clearance;        /* voxel units */
+    int32_t flags;          /* GIE_LOS_* */
+    int32_t reserved[2];    /* 0 */
+} gie_los_param;
+typedef struct gie_los_hit {            /* 24 bytes */
+    int32_t first;
+    int32_t len;
+    int32_t hit[3];
+    float min_edt;
+} gie_los_hit;
+typedef struct gie_view {               /* 64 bytes */
+    float pos[3];           /* metres, world frame */
+    int32_t n_planes;       /* 0..4 */
+    int32_t normal[4][3];   /* inward normals of the half spaces, integers of magnitude <= 32767 */
+} gie_view;
+typedef struct gie_view_param {
+    float r_min, r_max;     /* metres */
+    float tan2_elev;        /* tan^2 of the half opening of the vertical band; < 0: no band */
+    int32_t reserved;       /* 0 */
+} gie_view_param;
+typedef struct gie_view_score {         /* 16 bytes */
+    int32_t unknown, frontier, occupied, candidates;
+} gie_view_score;
+int gie_los_prepare(gie_mapper *h, const gie_los_param *p, int32_t *n_opaque);
+int gie_los_prepare_dev(gie_mapper *h, const gie_los_param *p, int32_t *d_n_opaque);
+int gie_read_los_opaque(gie_mapper *h, uint8_t *opaque);
+int gie_read_los_opaque_dev(gie_mapper *h, uint8_t *d_opaque);
+int gie_los_segments(gie_mapper *h, const float *a_xyz, const float *b_xyz, int n, gie_los_hit *out);
+int gie_los_segments_dev(gie_mapper *h, const float *d_a_xyz, const float *d_b_xyz, int n, gie_los_hit *d_out);
+int gie_view_gain(gie_mapper *h, const gie_view *views, int n, const gie_view_param *vp, gie_view_score *out);
+int gie_view_gain_dev(gie_mapper *h, const gie_view *d_views, int n, const gie_view_param *vp, gie_view_score *d_out);
+
 /* ---- changed-block streaming: the CPU mirror the reference keeps for RViz and CPU planners.
  * GlbHashMap::streamPipeline / streamD2H / getUpdatedAddr (glb_hash_map.cu:209-247,
  * unify_helper.cuh:11-32), fed by the stream_VB_keys_D appends of the fuse / wave / commit kernels
