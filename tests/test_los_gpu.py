@@ -8,66 +8,14 @@ import pytest
 
 import gie
 import los_ref as lr
-import planner_scenes as ps
 from gie import scenes
+from los_common import W, BoxDrive as _BoxDrive, bits as _bits, cv as _cv, mapper as _mapper, probe as _probe, scene as _scene
+from los_common import update as _update, world as _world
 
 pytestmark = pytest.mark.gpu
 
 OPAQUE_SIZES = [(96, 80, 72), (97, 61, 45), (77, 53, 1), (48, 40, 33), (65, 20, 20), (1, 40, 40)]
 BOX_SIZES = OPAQUE_SIZES[:4]
-W = 0.1
-
-
-def _mapper(size, voxel=W, **kw):
-    kw.setdefault("cutoff_dist", 3.0)
-    return gie.Mapper(gie.make_config(voxel, size, fast_mode=False, **kw))
-
-
-def _update(m, pos, q, labels):
-    m.set_pose(pos, q)
-    m.ogm_labels(labels)
-    m.step()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint8)
-
-
-def _room(lab, x0, y0, z0, inner, unknown):
-    """a closed room (local voxels): occupied walls one voxel thick around `inner` free voxels with `unknown` never-seen voxels in
-    its middle; a flat volume has no floor and ceiling.  Returns (a free voxel next to the room's low corner, the never-seen box)."""
-    Z, Y, X = lab.shape
-    ix, iy, iz = inner
-    lab[z0:min(z0 + iz + 2, Z), y0:y0 + iy + 2, x0:x0 + ix + 2] = 2
-    zi0, zi1 = (z0 + 1, z0 + 1 + iz) if Z > 1 else (0, 1)
-    lab[zi0:zi1, y0 + 1:y0 + 1 + iy, x0 + 1:x0 + 1 + ix] = 1
-    ux, uy, uz = unknown
-    uz = min(uz, zi1 - zi0)
-    cx, cy, cz = x0 + 1 + (ix - ux) // 2, y0 + 1 + (iy - uy) // 2, zi0 + (zi1 - zi0 - uz) // 2
-    lab[cz:cz + uz, cy:cy + uy, cx:cx + ux] = 0
-    return (x0 + 1, y0 + 1, zi0), (slice(cz, cz + uz), slice(cy, cy + uy), slice(cx, cx + ux))
-
-
-def _scene(m, size, seed=3, room=True):
-    """two updates of the solid scene of planner_scenes (with a closed room where it fits): (loc, corner voxel, never-seen box)"""
-    pos, q = scenes.pose(0, m.cfg.voxel_width, delta_vox=4, yaw_deg=0.0)
-    lab = ps.solid_labels(size, seed)
-    corner = pocket = None
-    if room and size[0] >= 40 and size[1] >= 40:
-        corner, pocket = _room(lab, 12, 10, max(size[2] // 2 - 5, 0), (9, 9, 9), (3, 3, 3))
-    for _ in range(2):
-        _update(m, pos, q, lab)
-    return m.read_local(dist_sq=False, coc=False), corner, pocket
-
-
-def _world(m, v, pvt=None):
-    """world points (float32 metres) of local voxel coordinates (possibly fractional)"""
-    pvt = np.asarray(m.pivot() if pvt is None else pvt, np.float32)
-    return ((np.asarray(v, np.float32) + pvt) * np.float32(m.cfg.voxel_width)).astype(np.float32)
-
-
-def _cv(m, clearance):
-    return np.float32(clearance) / np.float32(m.cfg.voxel_width)
 
 
 # ---- the opaque plane
@@ -199,6 +147,97 @@ def test_long_lines(size):
         m.close()
 
 
+def _beyond_scene(size):
+    """free labels and four lines along the longest axis, far apart in the cross-section (straight end to end; oblique end to end
+    forwards and backwards; oblique between inner points).  The opaque voxels come from a clearance of 1.2 voxels: an occupied
+    voxel one voxel BESIDE the line gives the line's voxel next to it edt 1 (opaque) and its neighbours on the line sqrt(2) (not).
+    On each line: such a voxel at index i; before i an occupied voxel two voxels beside the line (edt 2: a dip above the
+    clearance); beyond i a second opaque voxel of the same kind at j, and an occupied voxel ON the line at c (edt 0: lower than
+    anything up to i, and opaque as well), once between i and j and once right behind i.
+    Returns (labels, a [4, 3], b [4, 3], i [4], j [4], c [4]) in local voxels."""
+    ax = int(np.argmax(size))
+    o1, o2 = [k for k in range(3) if k != ax]
+    n, s1, s2 = size[ax], size[o1], size[o2]
+    if s2 >= 10:
+        anchors = [(2, 2), (s1 - 3, 2), (2, s2 - 3), (s1 - 3, s2 - 3)]
+    else:                                                      # a thin cross-section: four lines side by side
+        anchors = [(3 + k * ((s1 - 7) // 3), s2 // 2) for k in range(4)]
+    a = np.zeros((4, 3), np.int64)
+    b = np.zeros((4, 3), np.int64)
+    side = []
+    for k, (p1, p2) in enumerate(anchors):
+        d1 = (2 if p1 < s1 / 2 else -2) if k else 0            # the drift of the oblique ones, towards the middle
+        d2 = (1 if p2 < s2 / 2 else -1) if k else 0
+        lo, hi = (n // 8, n - 1 - n // 8) if k == 3 else (0, n - 1)
+        a[k, ax], a[k, o1], a[k, o2] = lo, p1, p2
+        b[k, ax], b[k, o1], b[k, o2] = hi, p1 + d1, p2 + d2
+        side.append(-1 if p1 < s1 / 2 else 1)                  # beside the line: away from the middle along o1
+    a[2], b[2] = b[2].copy(), a[2].copy()
+    lab = np.ones(size[::-1], np.int8)
+    lines = [lr.line(a[k], b[k]) for k in range(4)]
+    on_a_line = {v for ln in lines for v in ln}
+
+    def beside(ln, t, dist, sd):
+        """an occupied voxel `dist` beside the line's voxel t, or the next one where the line keeps its place in the cross-section
+        over five voxels (beside a side step of an oblique line stands the line itself): the index used"""
+        while True:
+            v = list(ln[t])
+            v[o1] += sd * dist
+            if tuple(v) not in on_a_line and all(ln[t + e][o1] == ln[t][o1] and ln[t + e][o2] == ln[t][o2] for e in (-2, -1, 1, 2)):
+                lab[v[2], v[1], v[0]] = 2
+                return t
+            t += 1
+
+    first, second, lower = [], [], []
+    for k, ln in enumerate(lines):
+        i = beside(ln, (63, 2 * len(ln) // 5, 511 if n > 600 else 129, len(ln) // 3)[k], 1, side[k])
+        beside(ln, i // 2, 2, side[k])
+        j = beside(ln, (i + 8, 4 * len(ln) // 5, len(ln) - 4, i + 70)[k], 1, side[k])
+        c = (i + 4, j + (len(ln) - j) // 2, i + 1, len(ln) - 1)[k]
+        lab[ln[c][2], ln[c][1], ln[c][0]] = 2
+        first.append(i)
+        second.append(j)
+        lower.append(c)
+    return lab, a, b, np.array(first), np.array(second), np.array(lower)
+
+
+BEYOND_CLEARANCE = 0.12                                        # metres at w = 0.1: 1.2 voxels, between 1 and sqrt(2)
+
+
+@pytest.mark.parametrize("size", [(1024, 16, 12), (16, 1024, 12), (12, 16, 1024), (300, 40, 7)], ids=lambda v: "x".join(map(str, v)))
+def test_segments_beyond_the_first_hit(size):
+    """after its first hit the kernel walks on without loads, for len: a second opaque voxel and a voxel of lower edt beyond the
+    hit must change nothing — first and hit stay the first opaque voxel, min_edt is the minimum over indices 0 .. first only.
+    (An opaque voxel has the smallest edt seen so far whatever made it opaque — occupied and never-seen voxels have edt 0, a
+    clearance is a bound on edt — so the minimum up to i is at i itself; what can be asked is that it is not the line's.)"""
+    m = _mapper(size)
+    try:
+        lab, a, b, want, second, lower = _beyond_scene(size)
+        pos, q = scenes.pose(0, W, delta_vox=0, yaw_deg=0.0)
+        for _ in range(2):
+            _update(m, pos, q, lab)
+        loc = m.read_local(dist_sq=False, coc=False)
+        pvt = np.array(m.pivot())
+        assert np.array_equal(loc["type"] == lr.OCCUPIED, lab == 2)
+        m.los_prepare(BEYOND_CLEARANCE, 0)
+        opq = lr.opaque(loc["type"], loc["edt"], _cv(m, BEYOND_CLEARANCE), 0)
+        ref = _check_segments(m, loc, opq, a, b)               # every field, bit for bit
+        got = m.los_segments(_world(m, a), _world(m, b))
+        for k in range(len(a)):
+            ln = lr.line(a[k], b[k])
+            e = np.array([loc["edt"][v[2], v[1], v[0]] for v in ln], np.float32)
+            o = np.array([opq[v[2], v[1], v[0]] for v in ln])
+            i, j, c = int(want[k]), int(second[k]), int(lower[k])
+            assert not o[:i].any() and o[i] and o[j] and o[c] and i < j and i < c and o[i + 1:].sum() >= 2
+            # the case proves something: a dip before i that is not the hit, and the line goes strictly lower beyond i
+            assert e[i] == 1.0 and e[:i - 2].min() == 2.0 and e[i + 1:].min() == 0.0 < e[:i + 1].min(), (k, e[:i].min(), e[i], e[i + 1:].min())
+            for r in (ref[k], got[k]):
+                assert r["first"] == i and r["len"] == len(ln) and r["hit"].tolist() == (np.array(ln[i]) + pvt).tolist()
+                assert _bits(r["min_edt"]).tobytes() == _bits(e[:i + 1].min()).tobytes()
+    finally:
+        m.close()
+
+
 # ---- view gain
 def _view_set(m, rng, size, loc, corner, pocket, reps):
     """local voxels of the views: random ones, the cluster representatives, one inside an obstacle, the closed room's corner (the
@@ -290,37 +329,6 @@ def test_view_gain_256_cubed_range_60():
 
 
 # ---- life cycle
-def _random_boxes(rng, n, extent, smin, smax):
-    out = []
-    for _ in range(n):
-        s = rng.integers(smin, smax, size=3)
-        lo = rng.integers(-extent, extent, size=3)
-        out.append((lo, lo + s))
-    return out
-
-
-class _BoxDrive:
-    """boxes fixed in the world that toggle from frame to frame, seen from a pose that moves out and back; a never-seen x-slab"""
-
-    def __init__(self, size, seed=3, w=W, delta=3):
-        self.size, self.w, self.delta = size, w, delta
-        self.boxes = _random_boxes(np.random.default_rng(seed), 24, 60, 6, 26)
-
-    def frame(self, k):
-        pos, q = scenes.pose(k if k < 15 else 30 - k, self.w, delta_vox=self.delta, yaw_deg=0.0)
-        pvt = scenes.local_pivot(pos, self.w, self.size)
-        X, Y, Z = self.size
-        gx = np.arange(X)[None, None, :] + pvt[0]
-        gy = np.arange(Y)[None, :, None] + pvt[1]
-        gz = np.arange(Z)[:, None, None] + pvt[2]
-        lab = np.ones((Z, Y, X), np.int8)
-        for i, (lo, hi) in enumerate(self.boxes):
-            if (k + i) % 4 != 3:
-                lab[(gx >= lo[0]) & (gx < hi[0]) & (gy >= lo[1]) & (gy < hi[1]) & (gz >= lo[2]) & (gz < hi[2])] = 2
-        lab[:, :, :4] = 0
-        return pos, q, lab
-
-
 def _whole_feature(m, rng, size, cl, fl, loc=None, check=True):
     """prepare + the three readers on the current map; with check, against the reference.  Returns what the device gave."""
     if loc is None and check:
@@ -472,12 +480,6 @@ def test_dev_forms_through_torch():
         assert prof["los"][1] == 1 and prof["los_query"][1] == 2 and prof["los"][0] > 0 and prof["los_query"][0] > 0
     finally:
         m.close()
-
-
-def _probe(m, size, rng):
-    pvt = np.array(m.pivot())
-    xyz = (pvt + rng.integers(-4, np.array(size) + 4, size=(500, 3))).astype(np.int32)
-    return m.query_global(xyz)
 
 
 def test_los_calls_change_nothing_of_the_map_update():

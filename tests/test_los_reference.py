@@ -1,6 +1,7 @@
 """The numpy statement of the line-of-sight queries (tests/los_ref.py) against slower, plainer statements of the same definitions:
 the voxel line against an exact rational brute force of "the cube shares a piece of positive length with the segment", the view
-gain against a triple loop.  And the presence of the feature in the header, both libraries and the binding."""
+gain against a triple loop and against the exhaustive statement of tests/los_exact.py (no candidate radius), with the properties
+of the tie radii the device tests rely on.  And the presence of the feature in the header, both libraries and the binding."""
 import ctypes as C
 import os
 import re
@@ -9,6 +10,7 @@ from fractions import Fraction
 import numpy as np
 
 import gie
+import los_exact as lx
 import los_ref as lr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -201,6 +203,80 @@ def test_view_gain_occlusion_by_hand():
     assert inside["candidates"] == 5 and inside["occupied"] == 3
     # r_min cuts the shell below it
     assert one((1, 4, 3), rmin=2.0, rmax=3.0)["candidates"] == one((1, 4, 3), rmax=3.0)["candidates"] - one((1, 4, 3), rmax=1.9)["candidates"]
+
+
+def _tie_scene(size):
+    """types of a scene for the tie radii: the solid scene's labels taken as committed types (free next to never-seen is not
+    turned into FNT here: the two statements are compared on whatever plane they are given)"""
+    import planner_scenes as ps
+    t = ps.solid_labels(size, 3)
+    return t, lr.opaque(t, None, 0.0, 0)
+
+
+def test_exhaustive_statement_against_the_radius_bounded_one():
+    """tests/los_exact.py asks every voxel of the volume; los_ref.view_gain bounds its candidates by a radius derived from r_max.
+    Equal on the room cases, and at every tie radius of the device test (r_max / w one float32 step either side of k)."""
+    t = _room()
+    opq = lr.opaque(t, None, 0.0, 0)
+    frustum = gie.view_frustum(0.1, -0.05, 1.2, 0.9)
+    cases = [((1, 4, 3), 0.0, 20.0, -1.0, ()), ((1, 4, 3), 2.5, 6.0, -1.0, ()), ((1, 4, 3), 0.0, 20.0, 0.25, ()),
+             ((1, 4, 3), 0.0, 20.0, -1.0, [(1, 0, 0)]), ((1, 4, 3), 0.0, 9.0, -1.0, list(frustum)),
+             ((0, 0, 0), 0.0, 7.0, -1.0, ()), ((8, 4, 6), 0.0, 5.0, 1.0, [(-1, 0, 0)]), ((4, 2, 3), 0.0, 8.0, -1.0, ()),
+             ((5, 5, 3), 1.0, 1.0, -1.0, ()), ((4, 4, 3), 0.0, 0.0, -1.0, ()), ((4, 4, 3), 0.0, 1e18, 0.09, ())]
+    for p, rmin, rmax, tan2, normals in cases:
+        got = lx.view_gain(t, opq, _views([p], normals), rmin, rmax, tan2, 1.0, (0, 0, 0))[0]
+        assert tuple(got) == _gain_loops(t, opq, p, rmin, rmax, tan2, normals), (p, rmin, rmax, tan2)
+        assert got.tobytes() == lr.view_gain(t, opq, _views([p], normals), rmin, rmax, tan2, 1.0, (0, 0, 0))[0].tobytes()
+    out = lx.view_gain(t, opq, _views([(-1, 4, 3), (np.nan, 0, 0), (9, 0, 0)]), 0.0, 5.0, -1.0, 1.0, (0, 0, 0))
+    assert (out.view(np.int32) == -1).all()
+    for size in lx.TIE_SIZES:
+        t, opq = _tie_scene(size)
+        cache = {}
+        pvt = (7, -3, 2)
+        for w in lx.TIE_WIDTHS:
+            for k in lx.TIE_KS:
+                vox = lx.tie_views(size, k)[:3 if k > 3 else 10]           # (the bounded statement walks every call anew)
+                views = _views((vox + np.array(pvt)) * np.float32(w))
+                for r in lx.tie_radii(k, w)[:: 1 if k in (5, 13) else 3]:
+                    a = lx.view_gain(t, opq, views, 0.0, r, -1.0, w, pvt, cache=cache)
+                    b = lr.view_gain(t, opq, views, 0.0, r, -1.0, w, pvt)
+                    assert a.tobytes() == b.tobytes() and (a["candidates"] > 0).all(), (size, w, k, float(r))
+
+
+def test_tie_radii_are_populated_and_tell_one_step_from_the_next():
+    """for every tie radius k of the device test and every view used there: at least 6 voxels of the volume lie at distance exactly
+    k (k = 1 and 2 have only the six axis neighbours: a view on a face, an edge or a corner keeps five, four or three of them,
+    and three are asked there), the radii hold quotients r_max / w below k, at k and above k, and the candidate count differs between the two float32
+    neighbours of k * w — so a candidate radius one too small cannot go unnoticed at these radii"""
+    for size in lx.TIE_SIZES:
+        for w in lx.TIE_WIDTHS:
+            for k in lx.TIE_KS:
+                radii = lx.tie_radii(k, w)
+                q = [r / np.float32(w) for r in radii]
+                assert len(radii) >= 3 and all(r.dtype == np.float32 for r in radii) and len({float(r) for r in radii}) == len(radii)
+                # (no float32 r_max need give the quotient k itself: around 13 * 0.1 the quotients step over 13)
+                lo, hi = max(r for r, v in zip(radii, q) if v < k), min(r for r, v in zip(radii, q) if v >= k)
+                assert np.nextafter(lo, np.float32(np.inf)) == hi and any(v > k for v in q), (w, k, q)
+                for p in lx.tie_views(size, k):
+                    shell = lx.shell_count(size, p, k)
+                    inner = all(0 < c < s - 1 for c, s in zip(p, size))
+                    assert shell >= (6 if k >= 3 or (inner and k == 1) else lx.tie_need(k)), (size, k, p)
+                    n = [int(lx.candidate_mask(size, p, *lx.thresholds(0.0, r, -1.0, w)).sum()) for r in radii[:3]]
+                    assert n[2] - n[1] == shell, (size, w, k, p, n)         # the two neighbours of k * w: without and with the shell
+                    assert n[0] in (n[1], n[2])
+
+
+def test_elevation_ties_are_populated():
+    """tan2_elev 1 and 0.25 have exact ties d_z^2 == tan2 * (d_x^2 + d_y^2): at least 20 candidates per view of the device test"""
+    for size in lx.TIE_SIZES:
+        for p in lx.tie_views(size, 9):
+            dx, dy, dz = lx.offsets(size, p)
+            for tan2, num, den in ((1.0, 1, 1), (0.25, 1, 4)):
+                cand = lx.candidate_mask(size, p, *lx.thresholds(0.0, 3e38, tan2, 0.1))
+                tie = (den * dz * dz == num * (dx * dx + dy * dy)) & (dz != 0)
+                assert int((tie & cand).sum()) == int(tie.sum()) >= 20, (size, p, tan2, int(tie.sum()))
+            flat = lx.candidate_mask(size, p, *lx.thresholds(0.0, 3e38, 0.0, 0.1))
+            assert np.array_equal(flat, (dz == 0) & ((dx != 0) | (dy != 0)) & np.ones(size[::-1], bool))
 
 
 def test_opaque_and_segments():
