@@ -22,6 +22,7 @@ import gie
 from gie import scenes
 from ogm_f64 import _compare, _depth_f64, _g2l, _multiscan_f64, _rot64, _scan2d_f64, _voxel_positions  # noqa: F401
 from oracle_py import OracleMapper
+from raycast_ref import _F, _pos2coord, _raycast_second_statement
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SHIM_SRC = os.path.join(HERE, "shims", "math_shim.c")
@@ -330,74 +331,9 @@ def test_scan2d_ogm_against_float64_restatement_of_the_reference(oracle_lib):
 
 
 # ------------------------------------------------------------------ ray-casting OGM + fusion: a second statement
-# Written from pntcld_raycast.cu:11-117, ray_cast.h:57-144, local_batch.h:114-126,250-258,303-350 and unify_helper.cuh:34-118 /
-# voxmap_utils.cuh:182-200, not from the oracle: plain Python loops, every float operation an np.float32 operation in the order
-# the reference writes them (no fused multiply-add: DESIGN.md deviation 4).  The pose has no rotation, so the sensor-to-map
-# transform is a single float addition per coordinate and does not go through anybody's SE3 code.
-_F = np.float32
-
-
-def _pos2coord(p, w):
-    return [int(np.floor(_F(_F(p[i]) / w) + _F(0.5))) for i in range(3)]          # floorf(p / w + 0.5f)
-
-
-def _raycast_second_statement(origin, pts, pvt, size, w, min_h, max_h):
-    X, Y, Z = size
-    count = np.zeros((Z, Y, X), np.int32)
-    occ = np.zeros((Z, Y, X), bool)
-    inside = lambda c: 0 <= c[0] < X and 0 <= c[1] < Y and 0 <= c[2] < Z
-    glb = [[_F(_F(p[i]) + _F(origin[i])) for i in range(3)] for p in pts]
-    for g in glb:                                                                   # registerLocObs
-        if g[2] >= min_h and g[2] <= max_h:
-            c = [a - b for a, b in zip(_pos2coord(g, w), pvt)]
-            if inside(c):
-                occ[c[2], c[1], c[0]] = True
-                count[c[2], c[1], c[0]] += 1
-
-    def clear(cg):                                                                  # clearRayLoc on a global coordinate
-        c = [a - b for a, b in zip(cg, pvt)]
-        if inside(c):
-            if occ[c[2], c[1], c[0]]:
-                return False
-            count[c[2], c[1], c[0]] -= 1
-        return True                                                                 # (outside: type UNKNOWN, the add is dropped)
-
-    max_length = _F(_F(_F(0.707) * _F(X)) * w)
-    FLT_MAX = np.finfo(np.float32).max
-    p0 = [_F(v) for v in origin]
-    i0 = _pos2coord(p0, w)
-    for p1 in glb:                                                                  # freeLocObs -> rayCastLoc
-        i1 = _pos2coord(p1, w)
-        clear(i0)
-        if i0 == i1:
-            continue
-        d = [_F(p1[i] - p0[i]) for i in range(3)]
-        ln = _F(np.sqrt(_F(_F(_F(d[0] * d[0]) + _F(d[1] * d[1])) + _F(d[2] * d[2]))))
-        d = [_F(v / ln) for v in d]
-        step, tmax, tdelta = [0] * 3, [FLT_MAX] * 3, [FLT_MAX] * 3
-        cur = list(i0)
-        for i in range(3):
-            step[i] = 1 if d[i] > 0 else (-1 if d[i] < 0 else 0)
-            if step[i]:
-                border = _F(_F(_F(cur[i]) * w) + _F(_F(_F(step[i]) * w) * _F(0.5)))
-                tmax[i] = _F(_F(border - p0[i]) / d[i])
-                tdelta[i] = _F(w / _F(abs(d[i])))
-        while True:
-            if tmax[0] < tmax[1]:
-                dim = 0 if tmax[0] < tmax[2] else 2
-            else:
-                dim = 1 if tmax[1] < tmax[2] else 2
-            cur[dim] += step[dim]
-            tmax[dim] = _F(tmax[dim] + tdelta[dim])
-            if not clear(cur):
-                break
-            if cur == i1:
-                break
-            far = min(min(tmax[0], tmax[1]), tmax[2])
-            if far > max_length or far > ln:
-                break
-    lab = np.where(count > 0, 2, np.where(count < 0, 1, 0)).astype(np.int8)        # getAllocKeys: OCCUPIED / FREE / untouched
-    return count, lab
+# The statement of registerLocObs / freeLocObs -> rayCastLoc lives in tests/raycast_ref.py (tests/test_ray_cast_edges.py holds the
+# emulation and the HIP library against it on hand-made clouds); the fusion below is written from unify_helper.cuh:34-118 /
+# voxmap_utils.cuh:182-200, in the same way: plain Python, every float operation an np.float32 operation.
 
 
 def _fuse_second_statement(occ_val, vox_type, count, thresh):
