@@ -96,6 +96,22 @@ class ViewScore(C.Structure):
     _fields_ = [("unknown", C.c_int32), ("frontier", C.c_int32), ("occupied", C.c_int32), ("candidates", C.c_int32)]
 
 
+class ShortcutParam(C.Structure):
+    """gie_shortcut_param (include/gie.h): 16 bytes."""
+    _fields_ = [("lookahead", C.c_int32), ("max_wp", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class Waypoint(C.Structure):
+    """gie_waypoint (include/gie.h): 24 bytes."""
+    _fields_ = [("xyz", C.c_int32 * 3), ("index", C.c_int32), ("min_edt", C.c_float), ("forced", C.c_int32)]
+
+
+class ShortcutInfo(C.Structure):
+    """gie_shortcut_info (include/gie.h): 16 bytes."""
+    _fields_ = [("count", C.c_int32), ("forced", C.c_int32), ("length", C.c_float), ("reserved", C.c_int32)]
+
+
+assert C.sizeof(ShortcutParam) == 16 and C.sizeof(Waypoint) == 24 and C.sizeof(ShortcutInfo) == 16
 assert C.sizeof(LosHit) == 24 and C.sizeof(View) == 64 and C.sizeof(ViewScore) == 16 and C.sizeof(LosParam) == 16 and C.sizeof(ViewParam) == 16
 
 NF1_UNKNOWN_TRAVERSABLE = 1
@@ -223,6 +239,9 @@ DEVICE_ONLY = {
     "los_segments_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "view_gain": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(ViewParam), C.c_void_p]),
     "view_gain_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(ViewParam), C.c_void_p]),
+    # path shortcutting over the opaque plane (include/gie.h): device library only
+    "path_shortcut": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(ShortcutParam), C.c_void_p, C.c_void_p]),
+    "path_shortcut_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(ShortcutParam), C.c_void_p, C.c_void_p]),
 }
 DEVICE_ONLY.update(ROUND_API)
 

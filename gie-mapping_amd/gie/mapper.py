@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import LOS_UNKNOWN_OPAQUE, NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE
-from ._capi import CamParam, Config, CostMapHdr, FrameStats, FrontierParam, LosParam, MultiScanParam, Nf1Param, ScanParam, ViewParam, Voxel
+from ._capi import CamParam, Config, CostMapHdr, FrameStats, FrontierParam, LosParam, MultiScanParam, Nf1Param, ScanParam, ShortcutParam, ViewParam, Voxel
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG, "csrc", "libgie_hip.so")
@@ -29,6 +29,9 @@ FRONTIER_CLUSTER_DTYPE = np.dtype([("label", "<i4"), ("size", "<i4"), ("lo", "<i
 LOS_HIT_DTYPE = np.dtype([("first", "<i4"), ("len", "<i4"), ("hit", "<i4", (3,)), ("min_edt", "<f4")])
 VIEW_DTYPE = np.dtype([("pos", "<f4", (3,)), ("n_planes", "<i4"), ("normal", "<i4", (4, 3))])
 VIEW_SCORE_DTYPE = np.dtype([("unknown", "<i4"), ("frontier", "<i4"), ("occupied", "<i4"), ("candidates", "<i4")])
+# gie_waypoint (24 bytes), gie_shortcut_info (16 bytes)
+WAYPOINT_DTYPE = np.dtype([("xyz", "<i4", (3,)), ("index", "<i4"), ("min_edt", "<f4"), ("forced", "<i4")])
+SHORTCUT_INFO_DTYPE = np.dtype([("count", "<i4"), ("forced", "<i4"), ("length", "<f4"), ("reserved", "<i4")])
 VOXEL_DTYPE = np.dtype([("occ_val", "u1"), ("vox_type", "i1"), ("pad", "<i2"), ("dist_sq", "<i4"),
                         ("coc", "<i4", (3,))])
 
@@ -661,3 +664,39 @@ class Mapper(MapperBase):
         """n views (n x 64 bytes) and scores (n x 16 bytes) in DEVICE buffers (raw addresses), on the mapper's stream."""
         p = self.view_param(r_min, r_max, tan2_elev)
         self._chk(self._f["view_gain_dev"](self._h, C.c_void_p(d_views or None), int(n), C.byref(p), C.c_void_p(d_out or None)))
+
+    # --- path shortcutting over the opaque plane (include/gie.h) -----------------------------
+    def shortcut_param(self, lookahead, max_wp):
+        p = ShortcutParam()
+        p.lookahead, p.max_wp = int(lookahead), int(max_wp)
+        return p
+
+    def path_shortcut(self, paths, lens, lookahead, max_wp, wp=None):
+        """Waypoints of n paths (paths: (n, max_len, 3) int32 global voxels and lens [n] int32, as nf1_path_dev leaves them) with a
+        look-ahead of `lookahead` points: (wp [n, max_wp] WAYPOINT_DTYPE, info [n] SHORTCUT_INFO_DTYPE) (synchronises).  Only the
+        first min(info.count, max_wp) records of a path are written: the rest of wp is zero, or what the caller's `wp` held."""
+        pts = np.ascontiguousarray(np.asarray(paths, dtype=np.int32))
+        if pts.ndim != 3 or pts.shape[2] != 3:
+            raise ValueError("path_shortcut: paths must be (n, max_len, 3)")
+        n, max_len = pts.shape[0], pts.shape[1]
+        ln = np.ascontiguousarray(np.asarray(lens, dtype=np.int32).reshape(-1))
+        if len(ln) != n:
+            raise ValueError("path_shortcut: one length per path")
+        max_wp = int(max_wp)
+        if wp is None:
+            wp = np.zeros((n, max(max_wp, 0)), WAYPOINT_DTYPE)
+        elif wp.dtype != WAYPOINT_DTYPE or wp.shape != (n, max_wp) or not wp.flags.c_contiguous:
+            raise ValueError("path_shortcut: wp must be a contiguous (n, max_wp) WAYPOINT_DTYPE array")
+        info = np.zeros(n, SHORTCUT_INFO_DTYPE)
+        p = self.shortcut_param(lookahead, max_wp)
+        spare = np.zeros(1, WAYPOINT_DTYPE)                   # (an empty array has no address to give: n == 0, or max_wp == 0)
+        self._chk(self._f["path_shortcut"](self._h, _ptr(pts) if pts.size else None, _ptr(ln) if n else None, n, max_len, C.byref(p),
+                                           _ptr(wp if wp.size else spare), _ptr(info) if n else None))
+        return wp, info
+
+    def path_shortcut_dev(self, d_path, d_len, n, max_len, d_wp, d_info, lookahead, max_wp):
+        """n paths with points (n x max_len x 3 int32), lengths (n int32), waypoints (n x max_wp x 24 bytes) and infos (n x 16 bytes)
+        in DEVICE buffers (raw addresses; 0 = not wanted), on the mapper's stream."""
+        p = self.shortcut_param(lookahead, max_wp)
+        self._chk(self._f["path_shortcut_dev"](self._h, C.c_void_p(d_path or None), C.c_void_p(d_len or None), int(n), int(max_len), C.byref(p),
+                                               C.c_void_p(d_wp or None), C.c_void_p(d_info or None)))

@@ -489,6 +489,64 @@ int gie_los_segments_dev(gie_mapper *h, const float *d_a_xyz, const float *d_b_x
 int gie_view_gain(gie_mapper *h, const gie_view *views, int n, const gie_view_param *vp, gie_view_score *out);
 int gie_view_gain_dev(gie_mapper *h, const gie_view *d_views, int n, const gie_view_param *vp, gie_view_score *d_out);
 
+/* ---- path shortcutting: any-angle waypoints from a polyline of voxels — what turns gie_nf1_path's 6-connected staircase into the
+ * few straight legs a controller can follow: from the current waypoint, go to the farthest point of the path (within a look-ahead)
+ * that is still visible over the opaque plane, repeat.  One call on the device, between gie_nf1_path_dev and whatever flies the
+ * result.  No counterpart in the reference's code.
+ *
+ * Everything refers to the last gie_los_prepare* and its pivot (the line-of-sight section): its volume, its opaque plane, its edt
+ * copy, its voxel line L(a, b).  Map updates do not change a result.
+ *  input         the buffers of gie_nf1_path*: n paths of max_len points (3 int32 each, GLOBAL voxel coordinates), len[i] as that
+ *                call left it: path i has m = min(max(len[i], 0), max_len) points v_0 .. v_{m-1}.  Any polyline of voxels is legal:
+ *                it need not be 6-connected or come from NF1, points may repeat, lie outside the volume or be any int32 (local =
+ *                global - pivot is computed in 64 bits).
+ *  Clear(a, b)   a and b are inside the prepare's volume and no voxel of L(a, b), both ends included, is opaque.
+ *  waypoints     indices k_0 = 0 < k_1 < .. < k_T = m - 1.  While k_t < m - 1, with K = lookahead:
+ *                  J = { j : k_t < j <= min(k_t + K, m - 1) and Clear(v_{k_t}, v_j) };  k_{t+1} = max J,
+ *                or, when J is empty, k_{t+1} = k_t + 1 and that leg is FORCED: the path stays connected and the caller learns that
+ *                it is not valid there.  Visibility along a path is not monotone (a pillar's shadow hides a stretch of points and
+ *                lets the ones behind it through): max J is the largest clear index of the whole window, not the last before the
+ *                first blocked one.  count = T + 1; 0 when m = 0.
+ *  gie_waypoint  record t: xyz = v_{k_t} as given, index = k_t.
+ *                  t = 0: forced = 0; min_edt = edt(v_0) when v_0 is inside the volume, otherwise -1.0f.
+ *                  a clear leg: forced = 0; min_edt = the exact float minimum of edt over all voxels of L(v_{k_{t-1}}, v_{k_t})
+ *                  (values of the prepare, voxel units).
+ *                  a forced leg: forced = 1; min_edt = -1.0f.
+ *  gie_shortcut_info  count as above, even when it exceeds max_wp; forced = the number of forced legs; length = a float sum,
+ *                started at 0.0f and accumulated in leg order t = 1 .. T: each CLEAR leg adds sqrtf((float)|v_{k_t} - v_{k_{t-1}}|^2)
+ *                (an exact integer below 2^22: both ends lie inside a volume of sides <= 1024; sqrtf as in gie_read_sdf), a forced
+ *                leg adds nothing.  Voxel units.
+ *  capacity      wp holds max_wp records per path; only the first min(count, max_wp) of a path are written (the convention of
+ *                gie_nf1_path's len > max_len), entries beyond them are left as they are.  info is complete whatever max_wp is.
+ * GIE_ERR_INVALID: no prepare yet; a tiled mapper; a NULL param; lookahead outside 1..4096; max_wp < 0; n < 0; with n > 0,
+ * max_len < 1 or a NULL path_xyz / len; wp NULL while max_wp > 0; wp and info both NULL.  n == 0 is valid and launches nothing.
+ * The host form synchronises; it stages through the two scratch slots of the host forms and hands the entries of wp beyond a
+ * path's records back as they were.  The _dev form takes DEVICE buffers and is enqueued on the mapper's stream without a host wait
+ * or a read-back: one launch, no grid barrier, a wave per path (a leg costs its window's lines in chunks of 64 from the far end,
+ * up to the first chunk with a clear one; a point outside the volume or in an opaque voxel costs nothing).
+ * Memory: none is kept.  gie_profile_read: counted under "los_query". */
+typedef struct gie_shortcut_param {     /* 16 bytes */
+    int32_t lookahead;      /* K >= 1: a leg may reach at most K path points ahead; <= 4096 */
+    int32_t max_wp;         /* >= 0: capacity of the waypoint array, per path */
+    int32_t reserved[2];    /* 0 */
+} gie_shortcut_param;
+typedef struct gie_waypoint {           /* 24 bytes */
+    int32_t xyz[3];         /* the path point, GLOBAL voxel coordinates, copied from the input */
+    int32_t index;          /* its index in the input path */
+    float   min_edt;        /* voxel units; -1.0f: a forced leg, or a first point outside the volume */
+    int32_t forced;         /* 1: the leg that ends here is not a clear line */
+} gie_waypoint;
+typedef struct gie_shortcut_info {      /* 16 bytes, one per path */
+    int32_t count;          /* waypoints of the path, even when > max_wp */
+    int32_t forced;         /* forced legs */
+    float   length;         /* voxel units */
+    int32_t reserved;       /* 0 */
+} gie_shortcut_info;
+int gie_path_shortcut(gie_mapper *h, const int32_t *path_xyz, const int32_t *len, int n, int max_len,
+                      const gie_shortcut_param *p, gie_waypoint *wp, gie_shortcut_info *info);
+int gie_path_shortcut_dev(gie_mapper *h, const int32_t *d_path_xyz, const int32_t *d_len, int n, int max_len,
+                          const gie_shortcut_param *p, gie_waypoint *d_wp, gie_shortcut_info *d_info);
+
 /* ---- changed-block streaming: the CPU mirror the reference keeps for RViz and CPU planners.
  * GlbHashMap::streamPipeline / streamD2H / getUpdatedAddr (glb_hash_map.cu:209-247,
  * unify_helper.cuh:11-32), fed by the stream_VB_keys_D appends of the fuse / wave / commit kernels
