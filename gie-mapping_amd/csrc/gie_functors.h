@@ -1,6 +1,9 @@
 /*
  * gie_functors.h — the per-voxel / per-item operations as functors, shared by the HIP kernels
- * (k_vox / k_lin in gie_kernels.hip.h) and by the test-only sequential emulation (tests/emu).
+ * (k_voxz / k_voxa / k_fuse_rows / k_lin in gie_kernels.hip.h) and by the test-only sequential
+ * emulation (tests/emu).  Two are not launched on the device: op_markc (the device's Mark + commit
+ * sweep is k_markc, built from the same gie_mark_logic, gie_commit_pair and gie_markc_column) and
+ * op_frontier (k_frontier_faces / k_frontier_tiles); the emulation runs both.
  */
 #ifndef GIE_FUNCTORS_H
 #define GIE_FUNCTORS_H
@@ -10,13 +13,13 @@
 
 /* skip(c, id, x, y, z): cheap test (at most one small load, issued for a whole z-column up
  * front by k_voxz) that is true only when operator() would do nothing for the voxel. */
-struct op_classify_depth { static constexpr bool rolled = false;
+struct op_classify_depth {
     GIE_DEVM bool tile_skip(const gie_ctx &, int, int, int) const { return false; } const float *img; gie_cam_param p;
     GIE_DEVM bool skip(const gie_ctx &, int, int, int, int) const { return false; }
     GIE_DEVM void operator()(const gie_ctx &c, int x, int y, int z) const {
         const int t = gie_classify_depth(c, img, p, x, y, z);
         if (t != GIE_VOX_UNKNOWN) { c.inst_type[gie_lid(c, x, y, z)] = (int8_t)t; gie_mark_block_needed(c, x, y, z); } } };
-struct op_classify_multiscan { static constexpr bool rolled = false;
+struct op_classify_multiscan {
     const float *img; gie_multiscan_param p; float tan_lo, tan_hi; int fov_test;
     /* the whole z-column (a straight segment in the sensor frame) lies above or below the field of
      * view when both its end voxels do: lz - hor*tan_hi is concave along a segment for tan_hi >= 0
@@ -45,26 +48,27 @@ struct op_classify_multiscan { static constexpr bool rolled = false;
     GIE_DEVM void operator()(const gie_ctx &c, int x, int y, int z) const {
         const int t = gie_classify_multiscan(c, img, p, x, y, z);
         if (t != GIE_VOX_UNKNOWN) { c.inst_type[gie_lid(c, x, y, z)] = (int8_t)t; gie_mark_block_needed(c, x, y, z); } } };
-struct op_classify_scan2d { static constexpr bool rolled = false;
+struct op_classify_scan2d {
     GIE_DEVM bool tile_skip(const gie_ctx &, int, int, int) const { return false; } const float *img; gie_scan_param p;
     GIE_DEVM bool skip(const gie_ctx &, int, int, int, int) const { return false; }
     GIE_DEVM void operator()(const gie_ctx &c, int x, int y, int z) const {
         const int t = gie_classify_scan2d(c, img, p, x, y, z);
         if (t != GIE_VOX_UNKNOWN) { c.inst_type[gie_lid(c, x, y, z)] = (int8_t)t; gie_mark_block_needed(c, x, y, z); } } };
-struct op_classify_labels { static constexpr bool rolled = false;
+struct op_classify_labels {
     GIE_DEVM bool tile_skip(const gie_ctx &, int, int, int) const { return false; } const int8_t *labels;
     GIE_DEVM bool skip(const gie_ctx &, int, int, int, int) const { return false; }
     GIE_DEVM void operator()(const gie_ctx &c, int x, int y, int z) const {
         const int t = gie_classify_label(c, labels, x, y, z);
         c.inst_type[gie_lid(c, x, y, z)] = (int8_t)t;              /* the scan IS the label plane: unknown is written too */
         if (t != GIE_VOX_UNKNOWN) gie_mark_block_needed(c, x, y, z); } };
-struct op_raycast_finalize { static constexpr bool rolled = false;
+struct op_raycast_finalize {
     /* no ray went through the tile (the robot sphere of for_motion_planner is written without rays) */
     GIE_DEVM bool tile_skip(const gie_ctx &c, int x, int y, int z0) const { return !c.for_motion_planner && !c.tray[gie_tile_index(c, x, y, z0)]; }
     GIE_DEVM bool skip(const gie_ctx &c, int id, int, int, int) const { return c.ray_count[id] == 0 && !c.for_motion_planner; }
     GIE_DEVM void operator()(const gie_ctx &c, int x, int y, int z) const { gie_raycast_finalize(c, x, y, z); } };
-/* staged ops (k_voxa<F, true>): st = per-voxel registers, load1/load2/finish as in gie_ops.h */
-struct op_fuse { static constexpr bool rolled = false;
+/* staged ops (gie_vox_column<F, true> on the device: op_commit under k_voxa, op_fuse in the list form of k_fuse_rows): st = per-voxel
+ * registers, load1/load2/finish as in gie_ops.h; operator() is the whole voxel at once (the emulation; op_mark under k_voxa) */
+struct op_fuse {
     typedef gie_fuse_st st;
     GIE_DEVM bool tile_skip(const gie_ctx &c, int x, int y, int z0) const { return gie_fuse_column_idle(c, x, y, z0) != 0; }
     /* per z-column (8 voxels of one 8x8x8 tile): which of them ended up known */
@@ -74,7 +78,7 @@ struct op_fuse { static constexpr bool rolled = false;
     GIE_DEVM void load2(const gie_ctx &c, int, int, int, int, st &s) const { gie_fuse_load2(c, s); }
     GIE_DEVM int finish(const gie_ctx &c, int id, int x, int y, int z, const st &s) const { return gie_fuse_finish(c, id, x, y, z, s); }
     GIE_DEVM int operator()(const gie_ctx &c, int x, int y, int z) const { return gie_fuse_voxel(c, x, y, z); } };
-struct op_mark { static constexpr bool rolled = false;
+struct op_mark {
     typedef gie_mark_st st;
     GIE_DEVM bool tile_skip(const gie_ctx &c, int x, int y, int z0) const { return !c.tknown[gie_tile_index(c, x, y, z0)]; }
     GIE_DEVM bool skip(const gie_ctx &c, int id, int, int, int) const { return c.glb_type[id] == GIE_VOX_UNKNOWN; }
@@ -82,7 +86,7 @@ struct op_mark { static constexpr bool rolled = false;
     GIE_DEVM void load2(const gie_ctx &c, int, int, int, int, st &s) const { gie_mark_load2(c, s); }
     GIE_DEVM int finish(const gie_ctx &c, int id, int x, int y, int z, const st &s) const { gie_mark_finish(c, id, x, y, z, s); return 0; }
     GIE_DEVM void operator()(const gie_ctx &c, int x, int y, int z) const { gie_mark_voxel(c, x, y, z); } };
-struct op_markc { static constexpr bool rolled = false;
+struct op_markc {
     typedef gie_markc_st st;
     GIE_DEVM bool tile_skip(const gie_ctx &c, int x, int y, int z0) const { return !c.tknown[gie_tile_index(c, x, y, z0)]; }
     GIE_DEVM bool skip(const gie_ctx &c, int id, int, int, int) const { return c.glb_type[id] == GIE_VOX_UNKNOWN; }
@@ -92,8 +96,7 @@ struct op_markc { static constexpr bool rolled = false;
     /* per z-column: which voxels were committed and the largest value finish() returned (the tile's bound for the next map update) */
     GIE_DEVM void column_max(const gie_ctx &c, int x, int y, int z0, unsigned known, unsigned valid, int vmax) const { gie_markc_column(c, x, y, z0, known, valid, vmax); }
     GIE_DEVM int operator()(const gie_ctx &c, int x, int y, int z) const { return gie_markc_voxel(c, x, y, z); } };
-struct op_tile_oldskip { GIE_DEVM void operator()(const gie_ctx &c, int t) const { (void)gie_tile_oldskip(c, t); } };
-struct op_commit { static constexpr bool rolled = false;
+struct op_commit {
     typedef gie_commit_st st;
     /* a map update whose waves were cut short by a barrier timeout commits nothing (GIE_ERR_TIMEOUT, include/gie.h): the flag of
      * THIS update (cleared with the frame), not the sticky one the host fetches — an enqueue-only pipeline that never
@@ -106,7 +109,7 @@ struct op_commit { static constexpr bool rolled = false;
     GIE_DEVM void operator()(const gie_ctx &c, int x, int y, int z) const { gie_commit_voxel(c, x, y, z); } };
 
 /* obtainFrontiers with wave64 ballot compaction of the C seeds: one atomicAdd per wave */
-struct op_frontier { static constexpr bool rolled = false;
+struct op_frontier {
     typedef gie_frontier_st st;
     /* the ballot inside finish() works on whatever lanes are active, so skipping is safe.
      * tsum == 0: nothing in or around this 8x8x8 tile can make obtainFrontiers act. */

@@ -39,11 +39,9 @@ struct be_state {
     int cur_id;                         /* bracket the launches currently belong to (-1: none) */
     double acc_ms[32]; int acc_n[32];
 };
-#include <vector>
 
 struct be_arena { char *base; size_t size, top; int k; std::vector<long long> skew; };
 static void gie_set_err(const std::string &s);
-#include <string>
 
 #define GIE_HIP_OK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { gie_set_err(std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
 
@@ -294,7 +292,7 @@ static int be_labels_in_place_ok(const gie_ctx &c, const int8_t *labels)
 { return (c.X & 15) == 0 && !c.for_motion_planner && ((uintptr_t)labels & 15) == 0; }
 static void be_labels(be_state *b, const gie_ctx &c, const int8_t *labels)
 {
-    if ((c.X & 15) == 0 && !c.for_motion_planner && ((uintptr_t)labels & 15) == 0) {
+    if (be_labels_in_place_ok(c, labels)) {
         const int nvec = c.N >> 4;
         GIE_LAUNCH(b, k_labels16, dim3((nvec + 255) / 256), dim3(256), 0, c, labels, nvec);
     } else { op_classify_labels op; op.labels = labels; be_vox(b, c, op); }
@@ -308,13 +306,13 @@ static void be_round_note(be_state *b, const gie_ctx &c, int32_t *changed, long 
     GIE_LAUNCH(b, k_round_note, dim3(1), dim3(64), 0, c, changed, stats, go, end);
 }
 /* allocHashTB + block table (see k_cell_alloc) */
+#define GIE_INIT_MULT 4         /* workgroups per compute unit of the block initialisation */
 /* fuse_list_ntile > 0: the fuse tile list (op_fuse_list over that many tiles) is built in the block-initialisation launch */
 static void be_block_alloc(be_state *b, const gie_ctx &c, int ncell, int32_t *, int clear_list, int fuse_list_ntile = 0)
 {
     if (clear_list) GIE_HIP_OK(hipMemsetAsync(&c.cnt[GIE_CNT_NEWLIST], 0, sizeof(int32_t), b->stream));
     GIE_LAUNCH(b, k_cell_alloc, dim3((ncell + 255) / 256), dim3(256), 0, c, ncell);
-    static const int imult = GIE_SWITCH("GIE_INIT_MULT", 4);
-    const int ninit = b->cu_total * imult;
+    const int ninit = b->cu_total * GIE_INIT_MULT;
     int nfl = (fuse_list_ntile + 255) / 256; if (nfl > 2 * b->cu_total) nfl = 2 * b->cu_total;
     GIE_LAUNCH(b, k_block_init_list, dim3(ninit + nfl), dim3(256), 0, c, ninit, fuse_list_ntile);
 }
@@ -376,9 +374,8 @@ static void gie_launch_edt_dim(be_state *b, const gie_ctx &c, int L, bool zpass,
 static int be_zs_mode(const gie_ctx &c)
 {
     if (c.Z < 64 || c.Z > 1024) return 0;          /* (short columns: the column kernel) */
-    static const int on = GIE_SWITCH("GIE_ZSTREAM", 1);
     static const int fused = GIE_SWITCH("GIE_ZS_FUSED", 1);
-    return on ? ((fused && (c.X & 1) == 0) ? 2 : 1) : 0;     /* (the fused form loads its rows two columns to a dword) */
+    return (fused && (c.X & 1) == 0) ? 2 : 1;     /* (the fused form loads its rows two columns to a dword) */
 }
 /* pass Z: the streaming form (if it takes the volume), pass X on the rows of the slabs it gave up (fused form: pass X did not
  * run), the column kernel (the rest, or the repair of those slabs) */
@@ -395,44 +392,34 @@ static void be_edt_z(be_state *b, const gie_ctx &c, int full) { be_edt_z_rest(b,
  * length calls for; staged = the functor's load1/load2/finish form; always_list = never sweep */
 /* mode: 0 = the kernel walks its list or sweeps the volume (decided on the device), 1 = always the list,
  * 2 = the list or nothing (the dense form is a block-row kernel launched next to this one) */
-template <bool STAGED, class F> static void be_vox_list(be_state *b, const gie_ctx &c, const F &f, const int32_t *list, int count_idx, int always_list, int lx = 64)
+/* workgroups per compute unit: 8 / 16 / 32 / 64 measured 0.33 / 0.27 / 0.25 / 0.25 ms for Mark on a densely known
+ * volume (sweep side); the list side does not care */
+#define GIE_VOXA_MULT 32
+template <bool STAGED, class F> static void be_vox_list(be_state *b, const gie_ctx &c, const F &f, const int32_t *list, int count_idx, int always_list)
 {
-    /* workgroups per compute unit: 8 / 16 / 32 / 64 measured 0.33 / 0.27 / 0.25 / 0.25 ms for Mark on a densely known
-     * volume (sweep side); the list side does not care */
-    static const int mult = GIE_SWITCH("GIE_VOXA_MULT", 32);
-    const dim3 g(b->cu_total * mult), t(256);
-    if (lx == 32) GIE_LAUNCH(b, (k_voxa<F, STAGED, 32>), g, t, 0, c, f, list, count_idx, always_list);
-    else if (lx == 16) GIE_LAUNCH(b, (k_voxa<F, STAGED, 16>), g, t, 0, c, f, list, count_idx, always_list);
-    else if (lx == 8) GIE_LAUNCH(b, (k_voxa<F, STAGED, 8>), g, t, 0, c, f, list, count_idx, always_list);
-    else GIE_LAUNCH(b, (k_voxa<F, STAGED, 64>), g, t, 0, c, f, list, count_idx, always_list);
+    GIE_LAUNCH(b, (k_voxa<F, STAGED>), dim3(b->cu_total * GIE_VOXA_MULT), dim3(256), 0, c, f, list, count_idx, always_list);
 }
-/* Mark + commit as one sweep: its own kernel (k_markc); GIE_MARKC_GENERIC=1 keeps the staged functor sweep (tests run both) */
+/* Mark + commit as one sweep: its own kernel (k_markc) */
+#define GIE_MARKC_MULT 64       /* workgroups per compute unit of the dense sweep: 16 / 32 / 48 / 64 / 96 / 128 measured 1.00 / 0.80 / 0.78 / 0.76 / 0.78 / 0.79 ms at 512^3 (round 4; 64 = exactly four virtual workgroups each) */
+#define GIE_MARKC_LAZY_MULT 40  /* ... of the lazy walk (5 / 10 / 20 / 40 / 64 / 96 per compute unit: 0.193 / 0.186 / 0.178 / 0.174 / 0.179 / 0.180 ms on the headline — a wave per swept tile, no second tile behind it) */
 static void be_markc(be_state *b, const gie_ctx &c, const int32_t *list)
 {
-    static const int generic = GIE_SWITCH("GIE_MARKC_GENERIC", 0);
-    static const int lx = GIE_SWITCH("GIE_MARKC_LX", 32);
-    static const int mult = GIE_SWITCH("GIE_VOXA_MULT", 64);     /* workgroups per compute unit of the dense sweep: 16 / 32 / 48 / 64 / 96 / 128 measured 1.00 / 0.80 / 0.78 / 0.76 / 0.78 / 0.79 ms at 512^3 (round 4; 64 = exactly four virtual workgroups each) */
-    if (generic) { be_vox_list<true>(b, c, op_markc(), list, GIE_CNT_TL_KNOWN, 0, lx == 16 || lx == 8 || lx == 32 ? lx : 64); return; }
     /* with lazy tiles the kernel walks the swept tiles, a wave each (k_markc): a grid that is resident at once */
-    static const int lmult = GIE_SWITCH("GIE_MARKC_LGRID", 40);      /* (5 / 10 / 20 / 40 / 64 / 96 per compute unit: 0.193 / 0.186 / 0.178 / 0.174 / 0.179 / 0.180 ms on the headline — a wave per swept tile, no second tile behind it) */
-    const dim3 g(b->cu_total * ((c.coc_defer && c.lazy_ok) ? lmult : mult)), t(256);
-    if (lx == 16) GIE_LAUNCH(b, k_markc<16>, g, t, 0, c, list);
-    else if (lx == 64) GIE_LAUNCH(b, k_markc<64>, g, t, 0, c, list);
-    else GIE_LAUNCH(b, k_markc<32>, g, t, 0, c, list);
+    const dim3 g(b->cu_total * ((c.coc_defer && c.lazy_ok) ? GIE_MARKC_LAZY_MULT : GIE_MARKC_MULT)), t(256);
+    GIE_LAUNCH(b, k_markc, g, t, 0, c, list);
 }
-/* placement probe (k_place_probe): median of `reps` timed launches, ms */
+/* placement probe (k_place_probe) on the Mark + commit sweep's own grid: median of `reps` timed launches, ms */
 static float be_place_probe(be_state *b, const gie_ctx &c, int reps, int streams = 15)
 {
-    static const int mult = GIE_SWITCH("GIE_VOXA_MULT", 64);     /* (the sweep's own grid: be_markc) */
     const long long ntile = (long long)c.tfd[0] * c.tfd[1] * c.tfd[2];
     const int nslot = (int)(ntile < c.max_blocks ? ntile : c.max_blocks);
     hipEvent_t e0, e1;
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -1.f;
     std::vector<float> ms;
-    hipLaunchKernelGGL(k_place_probe, dim3(b->cu_total * mult), dim3(256), 0, b->stream, c, nslot, streams);      /* warm-up: page tables, clocks */
+    hipLaunchKernelGGL(k_place_probe, dim3(b->cu_total * GIE_MARKC_MULT), dim3(256), 0, b->stream, c, nslot, streams);      /* warm-up: page tables, clocks */
     for (int r = 0; r < reps; r++) {
         (void)hipEventRecord(e0, b->stream);
-        hipLaunchKernelGGL(k_place_probe, dim3(b->cu_total * mult), dim3(256), 0, b->stream, c, nslot, streams);
+        hipLaunchKernelGGL(k_place_probe, dim3(b->cu_total * GIE_MARKC_MULT), dim3(256), 0, b->stream, c, nslot, streams);
         (void)hipEventRecord(e1, b->stream);
         (void)hipEventSynchronize(e1);
         float t = 0.f; (void)hipEventElapsedTime(&t, e0, e1); ms.push_back(t);
@@ -442,18 +429,13 @@ static float be_place_probe(be_state *b, const gie_ctx &c, int reps, int streams
     GIE_HIP_OK(hipMemsetAsync(c.pair, 0, (size_t)c.N * sizeof(uint64_t), b->stream));
     return ms.empty() ? -1.f : ms[ms.size() / 2];
 }
-/* dense (block-row) form of fuse; GIE_ROWS=0 keeps the thread-per-z-column sweep */
-static int be_rows_mode() { static const int v = GIE_SWITCH("GIE_ROWS", 1); return v ? 2 : 0; }
 /* fuse: one launch — the kernel walks its tile list (a wave per tile) or sweeps the volume by block rows, whichever the list's
- * length calls for; GIE_ROWS=0: the thread-per-z-column sweep of k_voxa instead of the block rows */
+ * length calls for */
+#define GIE_ROWS_MULT 32        /* 8 / 16 / 32 / 48 workgroups per compute unit: 0.225 / 0.215 / 0.195 / 0.19 ms at 512^3 (round 4: with the byte-parallel filter the kernel is short enough for the tail of its last workgroups to show; 32 = one virtual wavefront per wavefront) */
 static void be_fuse(be_state *b, const gie_ctx &c, const int32_t *list)
 {
-    static const int mult = GIE_SWITCH("GIE_ROWS_MULT", 32);     /* 8 / 16 / 32 / 48 workgroups per compute unit: 0.225 / 0.215 / 0.195 / 0.19 ms at 512^3 (round 4: with the byte-parallel filter the kernel is short enough for the tail of its last workgroups to show; 32 = one virtual wavefront per wavefront) */
-    if (be_rows_mode()) {
-        if (c.pntcld_mode) GIE_LAUNCH(b, k_fuse_rows<true>, dim3(b->cu_total * mult), dim3(256), 0, c, op_fuse(), list);
-        else GIE_LAUNCH(b, k_fuse_rows<false>, dim3(b->cu_total * mult), dim3(256), 0, c, op_fuse(), list);
-    }
-    else be_vox_list<true>(b, c, op_fuse(), list, GIE_CNT_TL_FUSE, 0);
+    if (c.pntcld_mode) GIE_LAUNCH(b, k_fuse_rows<true>, dim3(b->cu_total * GIE_ROWS_MULT), dim3(256), 0, c, op_fuse(), list);
+    else GIE_LAUNCH(b, k_fuse_rows<false>, dim3(b->cu_total * GIE_ROWS_MULT), dim3(256), 0, c, op_fuse(), list);
 }
 /* obtainFrontiers: the voxels on the six faces of the volume one per lane (an 8x8 patch per wave) with the tile summary + tile
  * list in the first workgroups of the same launch, then a wave per listed tile for the voxels off the faces (tile + halo
@@ -471,11 +453,9 @@ static void be_frontier_tiles(be_state *b, const gie_ctx &c, const int32_t *know
     /* (tried in round 4: the face voxels on a side stream next to the tiles, forked and joined with events — 2.352 against 2.352 ms per
      * C5 update: what the overlap saves the two stream hand-overs cost) */
     GIE_LAUNCH(b, k_frontier_faces, dim3(nsum + nface), dim3(64 * GIE_FF_WAVES), 0, c, fp, known, known_idx, nsum);
-    static int mult = GIE_SWITCH("GIE_FRONT_MULT", 0);
+    static int mult = 0;
     if (mult <= 0) {    /* as many workgroups as are resident at once: every wave walks the same share of the list (a second round of workgroups would start when the first is done) */
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(&k_frontier_tiles), 64 * GIE_FR_WAVES, 0) != hipSuccess || per_cu < 1) per_cu = 2;
-        mult = per_cu;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&mult, reinterpret_cast<const void *>(&k_frontier_tiles), 64 * GIE_FR_WAVES, 0) != hipSuccess || mult < 1) mult = 2;
     }
     GIE_LAUNCH(b, k_frontier_tiles, dim3(b->cu_total * mult), dim3(64 * GIE_FR_WAVES), 0, c, list, count_idx);
 }
@@ -484,15 +464,15 @@ static void be_edt_z_direct(be_state *b, const gie_ctx &c)
     GIE_LAUNCH(b, k_edt_z_direct, dim3(b->cu_total * 16), dim3(256), 0, c);
 }
 /* the streaming form of pass Z (k_edt_z_stream): a wave per (64 columns, y, z segment) */
+#define GIE_ZSTREAM_WAVES 8
 /* returns 1 when launched: the launch also carries the list form of the pass (k_edt_z_direct's body) when `full` is 0 */
 static int be_edt_z_stream(be_state *b, const gie_ctx &c, int full)
 {
     const int zs = be_zs_mode(c);
     if (!zs) return 0;
     const int nxr = (c.X + 63) / 64;
-    /* z segments so that the launch has about eight waves per SIMD to overlap its rows' round trips (a segment re-reads 16 planes) */
-    static const int target = GIE_SWITCH("GIE_ZSTREAM_WAVES", 8);
-    const long long want = (long long)b->cu_total * 4 * target;
+    /* z segments so that the launch has about eight waves per SIMD (GIE_ZSTREAM_WAVES) to overlap its rows' round trips (a segment re-reads 16 planes) */
+    const long long want = (long long)b->cu_total * 4 * GIE_ZSTREAM_WAVES;
     int nseg = (int)((want + (long long)nxr * c.Y - 1) / ((long long)nxr * c.Y));
     const int maxseg = c.Z / 64 > 0 ? c.Z / 64 : 1;
     if (nseg > maxseg) nseg = maxseg; if (nseg < 1) nseg = 1;
@@ -546,35 +526,30 @@ static void be_edt_prep(be_state *b, const gie_ctx &c)
 static void be_edt(be_state *b, const gie_ctx &c, int full)
 {
     dim3 gy((c.X + GIE_EDTY_COLS - 1) / GIE_EDTY_COLS, c.Z);
-    be_prof(b, 6, 0);   /* GIE_K_EDT_Y */
+    be_prof(b, GIE_K_EDT_Y, 0);
     /* one 32-voxel mask word per thread: with only the planes that hold obstacles at work, the
      * pass is bound by how many loads are in flight, not by bytes */
     /* X % 4 == 0: four columns per lane, dword loads / 8-byte stores (k_edt_y4) */
-    static const int y4 = GIE_SWITCH("GIE_EDTY4", 1);
-    if (y4 && (c.X & 3) == 0) {
-        /* y4: 1 = 16 lanes x 4 columns per workgroup (more, smaller workgroups), 3 = 32 lanes */
+    if ((c.X & 3) == 0) {
+        /* 16 lanes x 4 columns per workgroup (more, smaller workgroups than 32 lanes) */
         const int yb = c.Y > 512 ? 32 : 16, nq = (c.Y + yb - 1) / yb;
-        const int lanes = (y4 == 3) ? 32 : 16;
-        dim3 g4((c.X / 4 + lanes - 1) / lanes, c.Z), b4(lanes, nq);
-        if (yb == 16 && lanes == 16) GIE_LAUNCH(b, (k_edt_y4<16, 16>), g4, b4, 0, c);
-        else if (yb == 16) GIE_LAUNCH(b, (k_edt_y4<16, 32>), g4, b4, 0, c);
-        else if (lanes == 16) GIE_LAUNCH(b, (k_edt_y4<32, 16>), g4, b4, 0, c);
-        else GIE_LAUNCH(b, (k_edt_y4<32, 32>), g4, b4, 0, c);
+        dim3 g4((c.X / 4 + GIE_EDTY4_LANES - 1) / GIE_EDTY4_LANES, c.Z), b4(GIE_EDTY4_LANES, nq);
+        if (yb == 16) GIE_LAUNCH(b, k_edt_y4<16>, g4, b4, 0, c);
+        else GIE_LAUNCH(b, k_edt_y4<32>, g4, b4, 0, c);
     }
     else if (c.Y <= 256) GIE_LAUNCH(b, (k_edt_y<8, 8>), gy, dim3(GIE_EDTY_COLS, 8), 0, c);
     else if (c.Y <= 512) GIE_LAUNCH(b, (k_edt_y<16, 16>), gy, dim3(GIE_EDTY_COLS, 16), 0, c);
     else GIE_LAUNCH(b, (k_edt_y<32, 16>), gy, dim3(GIE_EDTY_COLS, 16), 0, c);
-    be_prof(b, 6, 1);
+    be_prof(b, GIE_K_EDT_Y, 1);
     const int zs = be_zs_mode(c);
-    be_prof(b, 7, 0); gie_launch_edt_dim(b, c, c.X, false, full, zs == 2 ? zs : 0); be_prof(b, 7, 1);   /* GIE_K_EDT_X */
-    be_prof(b, 8, 0);                                                                                  /* GIE_K_EDT_Z */
+    be_prof(b, GIE_K_EDT_X, 0); gie_launch_edt_dim(b, c, c.X, false, full, zs == 2 ? zs : 0); be_prof(b, GIE_K_EDT_X, 1);
+    be_prof(b, GIE_K_EDT_Z, 0);
     /* dense fields: the streaming form does the whole pass and flags what it could not finish for the column kernel; few known
      * tiles: the list form — in the same launch */
     const int zl = be_edt_z_stream(b, c, full);
     if (!zl && !full) be_edt_z_direct(b, c);
     be_edt_z_rest(b, c, full, zl ? zs : 0);
-    be_prof(b, 8, 1);
-
+    be_prof(b, GIE_K_EDT_Z, 1);
 }
 /* waves A, B and C in one launch; workgroups are co-resident by construction (512 threads and ≈ 151 KB of LDS each:
  * at most one per compute unit).  The frame clear has zeroed the barrier word and the per-level

@@ -3,8 +3,12 @@
  *
  *  k_voxz<F>          streaming per-voxel sweep of the whole volume (projective OGM classify):
  *                     one wave = 64 consecutive x → every plane access is a coalesced segment.
- *  k_voxa<F>          the same functors over a tile list or the volume, chosen on the device
- *                     (fuse, Mark, obtainFrontiers, commit).
+ *  k_voxa<F>          per-voxel functors over a tile list or the volume, chosen on the device
+ *                     (Mark and commit while they are two sweeps: op_mark, op_commit).
+ *  k_fuse_rows        fuse: block rows over the volume or op_fuse over a tile list.
+ *  k_markc            Mark + commit as one sweep.  op_markc is the emulation's sequential statement
+ *                     of the same sweep (tests/emu); the two meet in gie_mark_logic,
+ *                     gie_commit_pair and gie_markc_column (gie_ops.h).
  *  k_edt_y            EDT pass Y (EDTphase1, local_edt_core.h:14-82): the column's occupancy
  *                     lives in registers as a bit mask; one read of _glb_type, one 2-byte write.
  *  k_edt_x / k_edt_z  EDT passes X/Z (EDTphase2/3, :84-193): the Meijster lower envelope is
@@ -50,14 +54,10 @@
  * by workgroup dispatch and exposed latency, not by HBM); the skip tests of the whole column are
  * issued back to back before any voxel is processed. */
 #define GIE_VOX_ZPER 8
-/* optional per-column hook of the staged sweep (only op_fuse has one: tile known/unknown summaries) */
+/* optional per-column hook of the staged sweep (only op_fuse has one: tile known/unknown summaries; the list form of k_fuse_rows) */
 template <class F> __device__ __forceinline__ auto gie_column_hook_impl(const F &f, const gie_ctx &c, int x, int y, int z0, unsigned known, unsigned valid, int)
     -> decltype(f.column(c, x, y, z0, known, valid), void()) { f.column(c, x, y, z0, known, valid); }
 template <class F> __device__ __forceinline__ void gie_column_hook_impl(const F &, const gie_ctx &, int, int, int, unsigned, unsigned, long) {}
-/* ... or column_max(c, x, y, z0, committed mask, valid mask, largest value finish() returned) (op_markc) */
-template <class F> __device__ __forceinline__ auto gie_column_max_hook_impl(const F &f, const gie_ctx &c, int x, int y, int z0, unsigned known, unsigned valid, int vmax, int)
-    -> decltype(f.column_max(c, x, y, z0, known, valid, vmax), void()) { f.column_max(c, x, y, z0, known, valid, vmax); }
-template <class F> __device__ __forceinline__ void gie_column_max_hook_impl(const F &, const gie_ctx &, int, int, int, unsigned, unsigned, int, long) {}
 template <class F>
 __global__ __launch_bounds__(GIE_VOX_BX *GIE_VOX_BY) void k_voxz(const gie_ctx c, const F f)
 {
@@ -72,18 +72,9 @@ __global__ __launch_bounds__(GIE_VOX_BX *GIE_VOX_BY) void k_voxz(const gie_ctx c
         const int z = z0 + k;
         sk[k] = z >= c.Z || f.skip(c, z < c.Z ? gie_lid(c, x, y, z) : 0, x, y, z);
     }
-    if (F::rolled) {            /* big bodies: keep one copy of the code (instruction cache) */
-        unsigned m = 0;
 #pragma unroll
-        for (int k = 0; k < GIE_VOX_ZPER; k++) m |= (sk[k] ? 0u : 1u) << k;
-#pragma unroll 1
-        for (int k = 0; k < GIE_VOX_ZPER; k++)
-            if ((m >> k) & 1u) f(c, x, y, z0 + k);
-    } else {
-#pragma unroll
-        for (int k = 0; k < GIE_VOX_ZPER; k++)
-            if (!sk[k]) f(c, x, y, z0 + k);
-    }
+    for (int k = 0; k < GIE_VOX_ZPER; k++)
+        if (!sk[k]) f(c, x, y, z0 + k);
 }
 
 template <class F>
@@ -514,12 +505,13 @@ __global__ __launch_bounds__(GIE_EDTY_COLS * TPC) void k_edt_y(const gie_ctx c)
  * bound by the number of memory instructions, not by bytes).  Thread (l, q) owns the YB
  * positions y = q·YB .. of its four columns; what lies below / above its own mask word comes
  * from the other threads' words in LDS (one 16-byte read per word covers the four columns). */
-template <int YB, int LANES>
-__global__ __launch_bounds__(32 * LANES) void k_edt_y4(const gie_ctx c)
+#define GIE_EDTY4_LANES 16      /* lanes along x of a workgroup (more, smaller workgroups than 32) */
+template <int YB>
+__global__ __launch_bounds__(32 * GIE_EDTY4_LANES) void k_edt_y4(const gie_ctx c)
 {
-    __shared__ __attribute__((aligned(16))) uint32_t s_m[32][LANES * 4];
+    __shared__ __attribute__((aligned(16))) uint32_t s_m[32][GIE_EDTY4_LANES * 4];
     const int l = threadIdx.x, q = threadIdx.y, nq = blockDim.y;
-    const int x = (blockIdx.x * LANES + l) * 4;
+    const int x = (blockIdx.x * GIE_EDTY4_LANES + l) * 4;
     const int z = blockIdx.y;
     if (!c.zocc[z]) return;                              /* plane without obstacle: passes X/Z never read its cy1 */
     const int X = c.X, Y = c.Y;
@@ -1708,7 +1700,7 @@ __global__ __launch_bounds__(256) void k_coc_catchup_run(const gie_ctx c, const 
 }
 
 /* ------------------------------------------------------------------ adaptive sweeps */
-/* The per-voxel functors of fuse / Mark / obtainFrontiers / commit over either the tiles on a list
+/* The per-voxel functors of Mark / commit (and, through gie_vox_column, fuse's list form in k_fuse_rows) over either the tiles on a list
  * (one wave per 8x8x8 tile, lane = (x,y) column of the tile) or the whole volume (the geometry of
  * k_voxz: 64 x 4 columns per virtual workgroup), chosen by the kernel itself from the length of
  * the list (gie_use_lists).  A fixed grid strides through the work either way: for a sparsely
@@ -1732,25 +1724,21 @@ __device__ __forceinline__ void gie_vox_column(const gie_ctx &c, const F &f, con
 #pragma unroll
         for (int k = 0; k < 8; k++) if (!sk[k]) f.load2(c, id[k], x, y, z0 + k, s[k]);
         unsigned known = 0, valid = 0;
-        int vmax = 0;
 #pragma unroll
         for (int k = 0; k < 8; k++) {
             if (z0 + k < c.Z) valid |= 1u << k;
-            if (!sk[k]) { const int r = f.finish(c, id[k], x, y, z0 + k, s[k]); known |= (unsigned)(r != 0) << k; vmax = r > vmax ? r : vmax; }
+            if (!sk[k]) known |= (unsigned)(f.finish(c, id[k], x, y, z0 + k, s[k]) != 0) << k;
         }
         gie_column_hook_impl(f, c, x, y, z0, known, valid, 0);
-        gie_column_max_hook_impl(f, c, x, y, z0, known, valid, vmax, 0);
     } else {
 #pragma unroll
         for (int k = 0; k < 8; k++) if (!sk[k]) f(c, x, y, z0 + k);
     }
 }
-/* LX = lanes of a wave along x in the sweep form (64 / LX rows of y per wave): 64 gives the local
- * x-fastest planes whole 64-voxel rows per instruction but the global block planes 8-voxel pieces of
- * eight blocks; smaller LX trades row length for longer runs inside a block (a block plane holds
- * x | y<<3 | z<<6): LX = 16 reads 4 rows of 16 voxels and touches 2 blocks with 32 consecutive
- * voxels each. */
-template <class F, bool STAGED, int LX>
+/* The sweep form has a wave's 64 lanes along x: the local x-fastest planes go by whole 64-voxel rows
+ * per instruction, the global block planes by 8-voxel pieces of eight blocks (a block plane holds
+ * x | y<<3 | z<<6). */
+template <class F, bool STAGED>
 __global__ __launch_bounds__(256) void k_voxa(const gie_ctx c, const F f, const int32_t *list, const int count_idx, const int always_list)
 {
     if (GIE_GATE_CLOSED(c)) return;
@@ -1765,7 +1753,7 @@ __global__ __launch_bounds__(256) void k_voxa(const gie_ctx c, const F f, const 
             gie_vox_column<F, STAGED>(c, f, tx * 8 + (lane & 7), ty * 8 + (lane >> 3), tz * 8);
         }
     } else {
-        constexpr int LY = 64 / LX, WY = 4 * LY;               /* rows per wave / per workgroup */
+        constexpr int LX = 64, LY = 64 / LX, WY = 4 * LY;      /* lanes along x / rows per wave / per workgroup */
         const int gx = (c.X + LX - 1) / LX, gy = (c.Y + WY - 1) / WY, gz = (c.Z + 7) / 8;
         const int nv = gx * gy * gz;
         /* a workgroup takes a contiguous run of virtual workgroups (whole x rows of one (y, z) strip):
@@ -1783,12 +1771,13 @@ __global__ __launch_bounds__(256) void k_voxa(const gie_ctx c, const F f, const 
 }
 
 /* ------------------------------------------------------------------ Mark + commit, the dense sweep's own kernel */
-/* MarkLimitedObserve + UpdateHashBatch as one sweep (gie_ops.h "Mark + commit"): the same per-voxel functions as op_markc
- * under k_voxa (gie_mark_logic, gie_commit_pair, gie_markc_column) and the same geometry (thread = z-column of one tile, lanes LX
- * along x), but every load of a column's batch goes out BEFORE anything is tested: types, batch obstacles, the two block slots a
- * column can touch and the tile's skip flag in one batch, the stored records in a second one, then arithmetic and stores.  The
- * generic staged sweep tests the type first and loads behind the branch — four dependent round trips per column instead of
- * two; on the C5 volume the sweep is bound by how many bytes it keeps in flight, and by its stores (tools/sweep_probe.hip:
+/* MarkLimitedObserve + UpdateHashBatch as one sweep (gie_ops.h "Mark + commit").  The device runs k_markc; op_markc
+ * (gie_functors.h) is the emulation's sequential statement of the same sweep, and the two meet in the per-voxel functions
+ * gie_mark_logic, gie_commit_pair and gie_markc_column.  A thread takes the z-column of one tile (32 lanes along x), and every
+ * load of a column's batch goes out BEFORE anything is tested: types, batch obstacles, the two block slots a
+ * column can touch and the tile's skip flag in one batch, the stored records in a second one, then arithmetic and stores.  A
+ * staged functor sweep (gie_vox_column) tests the type first and loads behind the branch — four dependent round trips per column
+ * instead of two; on the C5 volume the sweep is bound by how many bytes it keeps in flight, and by its stores (tools/sweep_probe.hip:
  * this device writes at ~4.1 TB/s and reads at ~6.5, one after the other). */
 /* "LAZY PAIRS" (round 6, gie_ops.h).  A tskip tile with deferred records inside the wave range — 3/4 of the headline volume — has
  * nothing to decide: no stored record can win, every voxel is known (the update before committed them all), its batch obstacle lies
@@ -1958,7 +1947,6 @@ __device__ __forceinline__ void gie_markc_column_fast(const gie_ctx &c, const in
 #ifndef GIE_MARKC_OCC
 #define GIE_MARKC_OCC 5
 #endif
-template <int LX>
 __global__ __launch_bounds__(256, GIE_MARKC_OCC) void k_markc(const gie_ctx c, const int32_t *list)   /* (five waves per SIMD: 96 registers; one more costs the sweep a tenth of its time) */
 {
     const int n = c.cnt[GIE_CNT_TL_KNOWN];
@@ -1984,7 +1972,7 @@ __global__ __launch_bounds__(256, GIE_MARKC_OCC) void k_markc(const gie_ctx c, c
             gie_markc_column_fast(c, x, y, tz * 8, gie_markc_flags(c, x, y, tz * 8));
         }
     } else {
-        constexpr int LY = 64 / LX, WY = 4 * LY;
+        constexpr int LX = 32, LY = 64 / LX, WY = 4 * LY;      /* 32 lanes along x by 2 along y (k_place_probe repeats this geometry) */
         const int gx = (c.X + LX - 1) / LX, gy = (c.Y + WY - 1) / WY, gz = (c.Z + 7) / 8;
         const int nv = gx * gy * gz;
         const int per = (nv + (int)gridDim.x - 1) / (int)gridDim.x;

@@ -89,7 +89,7 @@ static void be_vox_list_col(const gie_ctx &c, const op_markc &f, int x, int y, i
 }
                        /* the block-row kernels are device-only forms of the same functors */
 
-template <bool STAGED, class F> static void be_vox_list(be_state *b, const gie_ctx &c, const F &f, const int32_t *list, int count_idx, int always_list, int = 64)
+template <bool STAGED, class F> static void be_vox_list(be_state *b, const gie_ctx &c, const F &f, const int32_t *list, int count_idx, int always_list)
 {
     if (GIE_GATE_CLOSED(c)) return;
     const int n = c.cnt[count_idx];
