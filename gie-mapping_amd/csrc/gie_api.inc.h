@@ -1164,6 +1164,10 @@ extern "C" int gie_stream_changed(gie_mapper *m, int32_t *keys, gie_voxel *block
     if (n_changed) *n_changed = total;
     if (!keys || !blocks || total == 0 || max_blocks == 0) return gie_sync(m);
     const int deliver = total < max_blocks ? total : max_blocks;
+    /* the gather reads stored records: a flag that has outlived fused updates (set while the flags were on, drained after they were
+     * switched off) may lie on a block of a tskip tile, whose records are the pair plane's since — so the debts are paid first, and
+     * a delivered block is what gie_query_global returns at this call.  Counting alone, or nothing flagged, costs nothing more. */
+    gie_catchup_everything(m);
     op_stream_list ol; ol.rank = m->d_srank; ol.list = m->d_slist;
     be_lin(&m->be, c, ol, cap);
     const size_t chunk_bytes = (size_t)GIE_STREAM_CHUNK * (GIE_STREAM_BLK_BYTES + 12);

@@ -559,7 +559,11 @@ int gie_path_shortcut_dev(gie_mapper *h, const int32_t *d_path_xyz, const int32_
  * (voxmap_utils.cuh:104-109) — and clears their flags.  *n_changed = flagged blocks before the
  * call; at most max_blocks are delivered (the rest stay flagged), in unspecified order; NULL
  * keys/blocks only counts.  One gather kernel + one batched copy per chunk instead of the
- * reference's 20 KB memcpy per block. */
+ * reference's 20 KB memcpy per block.
+ * A delivered block holds what gie_query_global returns for its voxels at the call, whenever the
+ * call comes: flags stay set while the stream is off, and a block flagged in one update may be
+ * drained after later ones — records that those updates left to the pair plane are stored before
+ * the gather (a call that delivers nothing, or only counts, does not pay for that). */
 #define GIE_BLOCK_VOXELS 512
 /* (takes effect with the next gie_fuse: a map update runs in one order of kernels — the fused Mark + commit sweep, or the reference's
  * Mark ... commit with the flags — from its fuse to its merge) */

@@ -4,6 +4,7 @@ emulation) and compares every stage bit for bit."""
 import numpy as np
 
 import gie
+import stream_mirror
 from gie import scenes
 
 
@@ -134,6 +135,15 @@ def probe_left_behind(prev_pvt, pvt, size, rng, n=6000):
     return np.ascontiguousarray(xyz[rng.permutation(len(xyz))[:n]], dtype=np.int32)
 
 
+def set_ext_boxes(*mappers):
+    """the two boxes of the scenarios with ext_boxes=True (one of them inactive)"""
+    ll = np.array([[-100, -100, -100], [0.5, -1.0, -1.0]], np.float32)
+    ur = np.array([[100, 100, 100], [1.0, 1.0, 0.5]], np.float32)
+    act = np.array([0, 1], np.uint8)
+    for m in mappers:
+        m.set_ext_boxes(ll, ur, act)
+
+
 def compare_global(tag, a, b, xyz):
     if len(xyz) == 0:
         return
@@ -173,11 +183,7 @@ def run_and_compare(sc, make_a, make_b, check_stats=True, verbose=False, product
     out = []
     try:
         if sc.ext_boxes:
-            ll = np.array([[-100, -100, -100], [0.5, -1.0, -1.0]], np.float32)
-            ur = np.array([[100, 100, 100], [1.0, 1.0, 0.5]], np.float32)
-            act = np.array([0, 1], np.uint8)
-            a.set_ext_boxes(ll, ur, act)
-            b.set_ext_boxes(ll, ur, act)
+            set_ext_boxes(a, b)
         for k, (pos, q, kind, data, kw) in enumerate(sc.frames_iter()):
             a.set_pose(pos, q)
             b.set_pose(pos, q)
@@ -242,7 +248,8 @@ def run_irregular(sc, make_a, make_b, fuse_only=(), stream_on=(), compare_margin
     without batch EDT and merge -- a node that skips the EDT of a frame, or an update that failed half way) and updates that run
     with the changed-block flags on (`stream_on`: frame numbers; the mapper then uses the reference's order Mark ... commit instead
     of the fused sweep, so the run changes between the two forms).  After every COMPLETE update everything is compared as in
-    run_and_compare; after a fuse-only update the fused types and the stored occupancy."""
+    run_and_compare, and what the two mappers deliver of a stream-on update; after a fuse-only update the fused types and the stored
+    occupancy."""
     cfg = sc.config()
     a, b = make_a(cfg), make_b(cfg)
     rng = np.random.default_rng(sc.seed + 78)
@@ -266,9 +273,10 @@ def run_irregular(sc, make_a, make_b, fuse_only=(), stream_on=(), compare_margin
                 continue
             for m in (a, b):
                 m.batch_edt(); m.merge()
-            if on:
-                for m in (a, b):
-                    m.stream_changed()                       # drain the flags
+            if on:                                           # drain the flags: both mappers deliver the same blocks (stream_mirror I1)
+                ka, ba, _ = a.stream_changed()
+                kb, bb, _ = b.stream_changed()
+                stream_mirror.check_oracle_equal("%s frame %d" % (sc.name, k), (kb, bb), (ka, ba))
             _compare_after_merge(sc, k, a, b, rng, True)
     finally:
         a.close()
