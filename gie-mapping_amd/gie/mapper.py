@@ -298,6 +298,19 @@ class MapperBase:
         entries = np.ascontiguousarray(entries, dtype=HALO_ENTRY_DTYPE)
         self._chk(self._f["halo_import_sparse"](self._h, face, _ptr(entries), int(entries.shape[0])))
 
+    # one face at a time, to / from a raw device address (the HIP library only)
+    def halo_export_sparse_dev(self, face, dptr, dcount):
+        self._chk(self._f["halo_export_sparse_dev"](self._h, face, C.c_void_p(dptr), C.c_void_p(dcount)))
+
+    def halo_import_sparse_dev(self, face, dptr, dcount):
+        self._chk(self._f["halo_import_sparse_dev"](self._h, face, C.c_void_p(dptr), C.c_void_p(dcount)))
+
+    def halo_export_dev(self, face, dptr):
+        self._chk(self._f["halo_export_dev"](self._h, face, C.c_void_p(dptr)))
+
+    def halo_import_dev(self, face, dptr):
+        self._chk(self._f["halo_import_dev"](self._h, face, C.c_void_p(dptr)))
+
     def refine(self):
         n = C.c_int32(0)
         self._chk(self._f["refine"](self._h, C.byref(n)))
@@ -566,18 +579,6 @@ class Mapper(MapperBase):
         p = C.c_void_p()
         self._chk(self._f["get_stream"](self._h, C.byref(p)))
         return p.value or 0
-
-    def halo_export_sparse_dev(self, face, dptr, dcount):
-        self._chk(self._f["halo_export_sparse_dev"](self._h, face, C.c_void_p(dptr), C.c_void_p(dcount)))
-
-    def halo_import_sparse_dev(self, face, dptr, dcount):
-        self._chk(self._f["halo_import_sparse_dev"](self._h, face, C.c_void_p(dptr), C.c_void_p(dcount)))
-
-    def halo_export_dev(self, face, dptr):
-        self._chk(self._f["halo_export_dev"](self._h, face, C.c_void_p(dptr)))
-
-    def halo_import_dev(self, face, dptr):
-        self._chk(self._f["halo_import_dev"](self._h, face, C.c_void_p(dptr)))
 
     # device-resident sensor frames (pointers are raw device addresses, e.g. torch .data_ptr())
     def ogm_depth_dev(self, dptr, rows, cols, cx, cy, fx, fy, valid_nan=False):

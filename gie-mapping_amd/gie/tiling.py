@@ -82,36 +82,49 @@ def neighbours(rank, world_size):
 # Mapper.step_begin_tiled(): fuse, batch EDT and the first half of the merge are done, the face layers hold this update's
 # Mark-time state.  Round 0 exports / imports them and finishes the merge (gie_merge_end: obtainFrontiers + waves with fresh
 # ghosts); the rounds after it are export / import / gie_refine.
+#
+# Each of them picks a topology (_InProcess / _Ranked: where the tiles are, and so what "move" means), one of the topology's three
+# layer forms (host arrays, per-face device tensors ordered by the host, all faces in one call ordered on the mappers' streams)
+# and a stop rule (_until_stable, or _enqueued with or without the device-side gate).  The stop rule loops over _round.
 
-def exchange_until_stable_local(mappers, grid, max_rounds=64, sparse=False, sent=None):
-    """All tiles live in this process (tests, single-GPU checks): export every shared face, hand
-    it to the neighbour, finish the merge (round 0) or refine, repeat until no tile seeded anything.
-    Returns the refinement rounds run.  sparse=True: the layers travel in their sparse form (known voxels only,
-    gie_halo_export_sparse / gie_halo_import_sparse); `sent` (a list) collects the bytes of every layer handed over."""
-    world = grid[0] * grid[1] * grid[2]
-    assert world == len(mappers)
-    rounds = 0
+def _round(exchange, k, refine):
+    """Round k, the Python side of TiledMapper::round (host/gie_tiled.hpp): `exchange(k)` exports the shared faces, moves them and
+    imports them, and yields each mapper once its ghosts are in; round 0 then finishes that mapper's merge, every later round
+    refines.  Returns what the refine calls returned, by tile."""
+    return [m.merge_end() if k == 0 else refine(r, m) for r, m in enumerate(exchange(k))]
+
+
+def _until_stable(topo, exchange, max_rounds):
+    """Stop rule "until no tile seeded anything": the host reads refine() every round (which synchronises the mapper) and the
+    topology totals the counts.  Returns the refinement rounds run."""
     for k in range(max_rounds + 1):
-        layers = {}
-        for r, m in enumerate(mappers):
-            for face, nb in neighbours(r, world).items():
-                layers[(nb, face ^ 1)] = m.halo_export_sparse(face) if sparse else m.halo_export(face)
-                if sent is not None:
-                    sent.append(layers[(nb, face ^ 1)].nbytes)
-        for (r, face), layer in layers.items():
-            if sparse:
-                mappers[r].halo_import_sparse(face, layer)
-            else:
-                mappers[r].halo_import(face, layer)
-        if k == 0:
-            for m in mappers:
-                m.merge_end()
-            continue
-        seeded = sum(m.refine() for m in mappers)
-        rounds += 1
-        if seeded == 0:
+        seeded = _round(exchange, k, lambda r, m: m.refine())
+        if k and topo.total(seeded) == 0:
             break
-    return rounds
+    return k
+
+
+def _enqueued(topo, bufs, rounds, gated):
+    """Stop rules with nobody waiting for the host, over the all-faces form: `rounds` refinement rounds enqueued back to back
+    (refine_async).  gated=True are the same rounds gated on the device: gie_round_gate before every export, gie_refine_dev leaves
+    what each tile seeded in its "changed" word, the topology max-reduces those into "go" — the gate of the NEXT round —, and
+    gie_round_end closes the update."""
+    import torch
+    topo.buffers(bufs)
+    _stream_state(topo, bufs, gated)
+    if gated:
+        go, changed, esz = bufs["go"].data_ptr(), bufs["changed"].data_ptr(), bufs["changed"].element_size()
+    with torch.cuda.stream(bufs["stream"]):               # a rank's transfers and reduce go to the current stream; None: stay
+        for k in range(rounds + 1):
+            if gated:
+                gate, refine = (lambda m: m.round_gate(go if k > 1 else None)), (lambda r, m: m.refine_dev(changed + r * esz))
+            else:
+                gate, refine = None, (lambda r, m: m.refine_async())
+            _round(lambda k: topo.all_faces(bufs, gate), k, refine)
+            if gated and k:
+                topo.reduce_changed(bufs)
+        if gated:
+            topo.round_end(bufs)
 
 
 def _local_face_buffers(mappers, world, device, bufs):
@@ -125,32 +138,232 @@ def _local_face_buffers(mappers, world, device, bufs):
     return bufs["layers"]
 
 
+def _stream_state(topo, bufs, gated):
+    """The stream and event state of the stream-ordered forms, built on first use: every mapper's own stream as a torch stream
+    ("streams"), the events behind the last round's imports ("imported": an exporter may rewrite its layers only after them) and
+    the stream that is current while the rounds are enqueued ("stream": a rank's own, for its transfers and its all-reduce; none
+    in process).  Gated rounds add one "changed" word per tile, the "go" word they are max-reduced into and, in process, the
+    "side" stream that reduction runs on.  With device "cpu" (emulated mappers) the words are host memory and every stream is
+    None: no events."""
+    import torch
+    cuda = getattr(topo.device, "type", str(topo.device)) == "cuda"
+    if "streams" not in bufs:
+        bufs["streams"] = [torch.cuda.ExternalStream(m.stream_handle(), device=topo.device) if cuda else None for m in topo.mappers]
+        bufs["stream"] = bufs["streams"][0] if isinstance(topo, _Ranked) else None
+        bufs["imported"] = []
+    if gated and "go" not in bufs:
+        bufs["side"] = torch.cuda.Stream(device=topo.device) if cuda and bufs["stream"] is None else None
+        bufs["changed"] = torch.zeros(len(topo.mappers), dtype=torch.int32, device=topo.device)
+        bufs["go"] = torch.ones(1, dtype=torch.int32, device=topo.device)
+
+
+class _InProcess:
+    """All tiles live in this process: "move" hands a layer, or the pointer of its tensor, to face f ^ 1 of the neighbour."""
+
+    def __init__(self, mappers, grid, device=None):
+        self.mappers, self.device, self.world = mappers, device, grid[0] * grid[1] * grid[2]
+        assert self.world == len(mappers)
+        self.nbs = [neighbours(r, self.world) for r in range(self.world)]
+        self.go_ready = []
+
+    def total(self, seeded):
+        return sum(seeded)
+
+    def sync(self):
+        for m in self.mappers:
+            m.sync()
+
+    def buffers(self, bufs):
+        """self.out[r] / self.inp[r]: {face: pointer} of the layers tile r exports, and of its neighbours' layers it imports."""
+        lay = _local_face_buffers(self.mappers, self.world, self.device, bufs)
+        self.out = [{face: lay[(r, face)].data_ptr() for face in nbs} for r, nbs in enumerate(self.nbs)]
+        self.inp = [{face: lay[(nb, face ^ 1)].data_ptr() for face, nb in nbs.items()} for nbs in self.nbs]
+
+    def host_layers(self, sparse, sent):
+        layers = {}
+        for r, m in enumerate(self.mappers):
+            for face, nb in self.nbs[r].items():
+                layers[(nb, face ^ 1)] = m.halo_export_sparse(face) if sparse else m.halo_export(face)
+                if sent is not None:
+                    sent.append(layers[(nb, face ^ 1)].nbytes)
+        for (r, face), layer in layers.items():
+            m = self.mappers[r]
+            (m.halo_import_sparse if sparse else m.halo_import)(face, layer)
+        yield from self.mappers
+
+    def face_tensors(self, k):
+        for m, out in zip(self.mappers, self.out):
+            for face, p in out.items():
+                m.halo_export_dev(face, p)
+        self.sync()
+        for m, inp in zip(self.mappers, self.inp):
+            for face, p in inp.items():
+                m.halo_import_dev(face, p)
+        for m in self.mappers:
+            yield m                                       # refine() synchronises its mapper, merge_end does not:
+            if k == 0:
+                m.sync()                                  # either way the layers are free again
+
+    def _record(self, stream):
+        import torch
+        if stream is not None:
+            ev = torch.cuda.Event()
+            ev.record(stream)
+            return ev
+
+    def _wait(self, stream, evs):
+        if stream is not None:
+            for ev in evs:
+                stream.wait_event(ev)
+
+    def all_faces(self, bufs, gate):
+        streams, evs, done = bufs["streams"], [], []
+        for r, m in enumerate(self.mappers):
+            self._wait(streams[r], bufs["imported"] + self.go_ready)   # the layers of the round before have been read; this round's gate is final
+            if gate:
+                gate(m)
+            m.halo_export_all_dev(self.out[r])
+            evs.append(self._record(streams[r]))
+        for r, m in enumerate(self.mappers):
+            self._wait(streams[r], evs)                   # the neighbour's stream waits for the exporter's instead of a transfer
+            m.halo_import_all_dev(self.inp[r])
+            done.append(self._record(streams[r]))
+            yield m
+        bufs["imported"] = done
+
+    def reduce_changed(self, bufs):
+        """The all-reduce(max): one reduction on the side stream, behind every mapper's refinement, that everybody's next round
+        (and round_end) waits for."""
+        import torch
+        side = bufs["side"]
+        for stream in bufs["streams"]:
+            self._wait(side, [self._record(stream)])      # "refined": nothing follows refine_dev on a mapper's stream in this round
+        with torch.cuda.stream(side):
+            torch.amax(bufs["changed"], dim=0, keepdim=True, out=bufs["go"])
+        self.go_ready = [self._record(side)]
+
+    def round_end(self, bufs):
+        for stream, m in zip(bufs["streams"], self.mappers):
+            self._wait(stream, self.go_ready)
+            m.round_end(bufs["go"].data_ptr())
+
+
+class _Ranked:
+    """One tile per rank: "move" is batch_isend_irecv over the P2P ops of the shared faces, in sorted face order."""
+
+    def __init__(self, mapper, dist, rank, world_size, group, device):
+        self.mappers, self.dist, self.group, self.device = [mapper], dist, group, device
+        self.nbs = sorted(neighbours(rank, world_size).items())
+
+    def total(self, seeded):
+        import torch
+        n = torch.tensor(seeded, dtype=torch.int64, device=self.device)
+        self.dist.all_reduce(n, op=self.dist.ReduceOp.SUM, group=self.group)
+        return int(n.item())
+
+    def ops(self, pairs):
+        """The P2P op list over (send tensor, receive tensor) per face of self.nbs; a tensor without elements stays out of it."""
+        d, ops = self.dist, []
+        for (snd, rcv), (_, nb) in zip(pairs, self.nbs):
+            if snd.numel():
+                ops.append(d.P2POp(d.isend, snd, nb, group=self.group))
+            if rcv.numel():
+                ops.append(d.P2POp(d.irecv, rcv, nb, group=self.group))
+        return ops
+
+    def move(self, ops, host_waits=False):
+        import torch
+        if ops:
+            for w in self.dist.batch_isend_irecv(ops):
+                w.wait()                                  # stream-level on RCCL: the current stream waits for the transfer
+            if host_waits:
+                torch.cuda.synchronize(self.device)
+
+    def buffers(self, bufs, sparse=False):
+        """Everything that does not change from round to round, once: bufs[face] = the (send, receive) tensors of a shared face,
+        "out" / "in" their pointers and "ops" the P2P op list over them.  sparse: entries of 24 bytes instead of records of 20,
+        and bufs[("count", face)] = the (sent, received) entry counts."""
+        import torch
+        if "ops" in bufs:
+            return
+        for face, _ in self.nbs:
+            n = self.mappers[0].halo_count(face) * (24 if sparse else 20)
+            bufs[face] = (torch.empty(n, dtype=torch.uint8, device=self.device), torch.empty(n, dtype=torch.uint8, device=self.device))
+            if sparse:
+                bufs[("count", face)] = (torch.zeros(1, dtype=torch.int32, device=self.device), torch.zeros(1, dtype=torch.int32, device=self.device))
+        bufs["out"] = {face: bufs[face][0].data_ptr() for face, _ in self.nbs}
+        bufs["in"] = {face: bufs[face][1].data_ptr() for face, _ in self.nbs}
+        bufs["ops"] = self.ops(bufs[face] for face, _ in self.nbs)
+
+    def host_layers(self, sparse):
+        import torch
+        from .mapper import HALO_DTYPE, HALO_ENTRY_DTYPE
+        m, dtype = self.mappers[0], HALO_ENTRY_DTYPE if sparse else HALO_DTYPE
+        lays = [m.halo_export_sparse(face) if sparse else m.halo_export(face) for face, _ in self.nbs]
+        snd = [torch.from_numpy(lay.view(np.uint8).copy()).to(self.device) for lay in lays]
+        if sparse:                                        # the neighbours tell each other the entry counts first
+            cs = [torch.tensor([lay.shape[0]], dtype=torch.int64, device=self.device) for lay in lays]
+            cr = [torch.zeros(1, dtype=torch.int64, device=self.device) for lay in lays]
+            self.move(self.ops(zip(cs, cr)))
+            rcv = [torch.empty(int(c.item()) * dtype.itemsize, dtype=torch.uint8, device=self.device) for c in cr]
+        else:
+            rcv = [torch.empty_like(t) for t in snd]
+        self.move(self.ops(zip(snd, rcv)))
+        for (face, _), r in zip(self.nbs, rcv):
+            (m.halo_import_sparse if sparse else m.halo_import)(face, r.cpu().numpy().view(dtype))
+        yield m
+
+    def face_tensors(self, bufs, sparse):
+        m, ops = self.mappers[0], bufs["ops"]
+        for face, _ in self.nbs:
+            if sparse:
+                m.halo_export_sparse_dev(face, bufs["out"][face], bufs[("count", face)][0].data_ptr())
+            else:
+                m.halo_export_dev(face, bufs["out"][face])
+        m.sync()                                          # export kernels ran on the mapper's own stream
+        if sparse:                                        # the counts first, read by the host; then only that many entries
+            self.move(self.ops(bufs[("count", face)] for face, _ in self.nbs), host_waits=True)
+            ops = self.ops((bufs[face][i][:int(bufs[("count", face)][i].item()) * 24] for i in (0, 1)) for face, _ in self.nbs)
+        self.move(ops, host_waits=True)
+        for face, _ in self.nbs:
+            if sparse:
+                m.halo_import_sparse_dev(face, bufs["in"][face], bufs[("count", face)][1].data_ptr())
+            else:
+                m.halo_import_dev(face, bufs["in"][face])
+        yield m
+
+    def all_faces(self, bufs, gate):
+        m = self.mappers[0]
+        if gate:
+            gate(m)
+        m.halo_export_all_dev(bufs["out"])
+        self.move(bufs["ops"])                            # on the mapper's stream: the import below is ordered behind the transfer
+        m.halo_import_all_dev(bufs["in"])
+        yield m
+
+    def reduce_changed(self, bufs):
+        bufs["go"].copy_(bufs["changed"])
+        self.dist.all_reduce(bufs["go"], op=self.dist.ReduceOp.MAX, group=self.group)
+
+    def round_end(self, bufs):
+        self.mappers[0].round_end(bufs["go"].data_ptr())
+
+
+def exchange_until_stable_local(mappers, grid, max_rounds=64, sparse=False, sent=None):
+    """All tiles live in this process (tests, single-GPU checks): export every shared face, hand
+    it to the neighbour, finish the merge (round 0) or refine, repeat until no tile seeded anything.
+    Returns the refinement rounds run.  sparse=True: the layers travel in their sparse form (known voxels only,
+    gie_halo_export_sparse / gie_halo_import_sparse); `sent` (a list) collects the bytes of every layer handed over."""
+    topo = _InProcess(mappers, grid)
+    return _until_stable(topo, lambda k: topo.host_layers(sparse, sent), max_rounds)
+
+
 def exchange_until_stable_local_device(mappers, grid, device, max_rounds=64, bufs=None):
     """In-process variant of the device-resident exchange (all tiles on one GPU): the export
     kernel of one mapper writes the tensor the import kernel of its neighbour reads."""
-    world = grid[0] * grid[1] * grid[2]
-    bufs = {} if bufs is None else bufs
-    lay = _local_face_buffers(mappers, world, device, bufs)
-    rounds = 0
-    for k in range(max_rounds + 1):
-        for r, m in enumerate(mappers):
-            for face in neighbours(r, world):
-                m.halo_export_dev(face, lay[(r, face)].data_ptr())
-        for m in mappers:
-            m.sync()
-        for r, m in enumerate(mappers):
-            for face, nb in neighbours(r, world).items():
-                m.halo_import_dev(face, lay[(nb, face ^ 1)].data_ptr())
-        if k == 0:
-            for m in mappers:
-                m.merge_end()
-                m.sync()                                   # the layers are free again
-            continue
-        seeded = sum(m.refine() for m in mappers)          # synchronises every mapper: the layers are free again
-        rounds += 1
-        if seeded == 0:
-            break
-    return rounds
+    topo = _InProcess(mappers, grid, device)
+    topo.buffers({} if bufs is None else bufs)
+    return _until_stable(topo, topo.face_tensors, max_rounds)
 
 
 def exchange_until_stable_device(mapper, dist, rank, world_size, device, bufs=None, max_rounds=64, group=None, sparse=False):
@@ -159,63 +372,9 @@ def exchange_until_stable_device(mapper, dist, rank, world_size, device, bufs=No
     import kernel from the receive tensors; nothing crosses PCIe except the seed count.
     sparse=True: gie_halo_export_sparse_dev compacts the known voxels of a layer; the neighbours exchange the entry counts
     (one more small batch and one host read per round — this form waits for the host anyway), then only that many entries."""
-    import torch
-    nbs = neighbours(rank, world_size)
-    if bufs is None:
-        bufs = {}
-    esz = 24 if sparse else 20
-    for face in nbs:
-        if face not in bufs:
-            n = mapper.halo_count(face) * esz
-            bufs[face] = (torch.empty(n, dtype=torch.uint8, device=device), torch.empty(n, dtype=torch.uint8, device=device))
-            if sparse:
-                bufs[("count", face)] = (torch.zeros(1, dtype=torch.int32, device=device), torch.zeros(1, dtype=torch.int32, device=device))
-    rounds = 0
-    for k in range(max_rounds + 1):
-        ops = []
-        if sparse:
-            cops = []
-            for face, nb in sorted(nbs.items()):
-                cs, cr = bufs[("count", face)]
-                mapper.halo_export_sparse_dev(face, bufs[face][0].data_ptr(), cs.data_ptr())
-                cops.append(dist.P2POp(dist.isend, cs, nb, group=group))
-                cops.append(dist.P2POp(dist.irecv, cr, nb, group=group))
-            mapper.sync()
-            if cops:
-                for w in dist.batch_isend_irecv(cops):
-                    w.wait()
-                torch.cuda.synchronize(device)
-            for face, nb in sorted(nbs.items()):
-                ns, nr = int(bufs[("count", face)][0].item()), int(bufs[("count", face)][1].item())
-                if ns:
-                    ops.append(dist.P2POp(dist.isend, bufs[face][0][:ns * esz], nb, group=group))
-                if nr:
-                    ops.append(dist.P2POp(dist.irecv, bufs[face][1][:nr * esz], nb, group=group))
-        else:
-            for face, nb in sorted(nbs.items()):
-                snd, rcv = bufs[face]
-                mapper.halo_export_dev(face, snd.data_ptr())
-                ops.append(dist.P2POp(dist.isend, snd, nb, group=group))
-                ops.append(dist.P2POp(dist.irecv, rcv, nb, group=group))
-            mapper.sync()                               # export kernels ran on the mapper's own stream
-        if ops:
-            for w in dist.batch_isend_irecv(ops):
-                w.wait()
-            torch.cuda.synchronize(device)
-        for face in sorted(nbs):
-            if sparse:
-                mapper.halo_import_sparse_dev(face, bufs[face][1].data_ptr(), bufs[("count", face)][1].data_ptr())
-            else:
-                mapper.halo_import_dev(face, bufs[face][1].data_ptr())
-        if k == 0:
-            mapper.merge_end()
-            continue
-        n = torch.tensor([mapper.refine()], dtype=torch.int64, device=device)
-        dist.all_reduce(n, op=dist.ReduceOp.SUM, group=group)
-        rounds += 1
-        if int(n.item()) == 0:
-            break
-    return rounds
+    topo, bufs = _Ranked(mapper, dist, rank, world_size, group, device), {} if bufs is None else bufs
+    topo.buffers(bufs, sparse)
+    return _until_stable(topo, lambda k: topo.face_tensors(bufs, sparse), max_rounds)
 
 
 def exchange_rounds_device(mapper, dist, rank, world_size, device, bufs, rounds=1, group=None):
@@ -223,33 +382,7 @@ def exchange_rounds_device(mapper, dist, rank, world_size, device, bufs, rounds=
     send / receive of the face layers, ghost import and refinement are enqueued back to back and
     the host never waits (no seed count comes back, so there is no convergence test: information
     crosses one tile boundary per round, the rest follows with the next map update)."""
-    import torch
-    if "ops" not in bufs:                                 # everything that does not change from round to round, once
-        nbs = neighbours(rank, world_size)
-        for face in nbs:
-            n = mapper.halo_count(face) * 20
-            bufs[face] = (torch.empty(n, dtype=torch.uint8, device=device), torch.empty(n, dtype=torch.uint8, device=device))
-        bufs["stream"] = torch.cuda.ExternalStream(mapper.stream_handle(), device=device)
-        bufs["out"] = {face: bufs[face][0].data_ptr() for face in nbs}
-        bufs["in"] = {face: bufs[face][1].data_ptr() for face in nbs}
-        ops = []
-        for face, nb in sorted(nbs.items()):
-            snd, rcv = bufs[face]
-            ops.append(dist.P2POp(dist.isend, snd, nb, group=group))
-            ops.append(dist.P2POp(dist.irecv, rcv, nb, group=group))
-        bufs["ops"] = ops
-    ops = bufs["ops"]
-    with torch.cuda.stream(bufs["stream"]):
-        for k in range(rounds + 1):
-            mapper.halo_export_all_dev(bufs["out"])
-            if ops:
-                for w in dist.batch_isend_irecv(ops):
-                    w.wait()                              # stream-level: the current (= the mapper's) stream waits for RCCL
-            mapper.halo_import_all_dev(bufs["in"])
-            if k == 0:
-                mapper.merge_end()                        # round 0 finishes the merge with this update's ghosts
-            else:
-                mapper.refine_async()
+    _enqueued(_Ranked(mapper, dist, rank, world_size, group, device), bufs, rounds, gated=False)
     return rounds
 
 
@@ -263,121 +396,17 @@ def exchange_converged_device(mapper, dist, rank, world_size, device, bufs, max_
     bound was too small — tests hold the bench's bound against the tiled oracle.  Works on the CPU too (emulated mappers, gloo):
     `device` "cpu", the "device words" are then host memory.
     Returns nothing the host could know without waiting: the rounds that ran are in round_stats()."""
-    import torch
-    cuda = getattr(device, "type", str(device)) == "cuda"
-    if "go" not in bufs:
-        nbs = neighbours(rank, world_size)
-        for face in nbs:
-            n = mapper.halo_count(face) * 20
-            bufs[face] = (torch.empty(n, dtype=torch.uint8, device=device), torch.empty(n, dtype=torch.uint8, device=device))
-        bufs["stream"] = torch.cuda.ExternalStream(mapper.stream_handle(), device=device) if cuda else None
-        bufs["out"] = {face: bufs[face][0].data_ptr() for face in nbs}
-        bufs["in"] = {face: bufs[face][1].data_ptr() for face in nbs}
-        ops = []
-        for face, nb in sorted(nbs.items()):
-            snd, rcv = bufs[face]
-            ops.append(dist.P2POp(dist.isend, snd, nb, group=group))
-            ops.append(dist.P2POp(dist.irecv, rcv, nb, group=group))
-        bufs["ops"] = ops
-        bufs["changed"] = torch.zeros(1, dtype=torch.int32, device=device)
-        bufs["go"] = torch.ones(1, dtype=torch.int32, device=device)
-    ops, changed, go = bufs["ops"], bufs["changed"], bufs["go"]
-
-    def transfer():
-        if ops:
-            for w in dist.batch_isend_irecv(ops):
-                w.wait()                                  # stream-level on RCCL: the current (= the mapper's) stream waits for the transfer
-
-    def rounds():
-        mapper.round_gate(None)
-        mapper.halo_export_all_dev(bufs["out"])
-        transfer()
-        mapper.halo_import_all_dev(bufs["in"])
-        mapper.merge_end()                                # round 0 finishes the merge with this update's ghosts
-        for k in range(1, max_rounds + 1):
-            mapper.round_gate(go.data_ptr() if k > 1 else None)
-            mapper.halo_export_all_dev(bufs["out"])
-            transfer()
-            mapper.halo_import_all_dev(bufs["in"])
-            mapper.refine_dev(changed.data_ptr())
-            go.copy_(changed)
-            dist.all_reduce(go, op=dist.ReduceOp.MAX, group=group)
-        mapper.round_end(go.data_ptr())
-
-    if cuda:
-        with torch.cuda.stream(bufs["stream"]):
-            rounds()
-    else:
-        rounds()
+    _enqueued(_Ranked(mapper, dist, rank, world_size, group, device), bufs, max_rounds, gated=True)
 
 
 def exchange_converged_local_device(mappers, grid, device, max_rounds=4, bufs=None):
     """exchange_converged_device with all tiles in this process (one GPU, or emulated mappers with device "cpu"): the neighbour's
     stream waits for an event on the exporter's stream instead of an RCCL transfer, and the all-reduce(max) of the "changed" words
     is one reduction on a side stream that waits for every mapper's refinement and that every mapper's next round waits for."""
-    import torch
-    cuda = getattr(device, "type", str(device)) == "cuda"
-    world = grid[0] * grid[1] * grid[2]
-    own = bufs is None
-    bufs = {} if bufs is None else bufs
-    lay = _local_face_buffers(mappers, world, device, bufs)
-    if "go" not in bufs:
-        bufs["streams"] = [torch.cuda.ExternalStream(m.stream_handle(), device=device) for m in mappers] if cuda else [None] * world
-        bufs["side"] = torch.cuda.Stream(device=device) if cuda else None
-        bufs["imported"] = []
-        bufs["changed"] = torch.zeros(world, dtype=torch.int32, device=device)
-        bufs["go"] = torch.ones(1, dtype=torch.int32, device=device)
-    streams, side, changed, go = bufs["streams"], bufs["side"], bufs["changed"], bufs["go"]
-    esz = changed.element_size()
-
-    def record(r):
-        if not cuda:
-            return None
-        ev = torch.cuda.Event()
-        ev.record(streams[r])
-        return ev
-
-    def wait(r, evs):
-        if cuda:
-            for ev in evs:
-                streams[r].wait_event(ev)
-
-    go_ready = []
-    for k in range(max_rounds + 1):
-        evs = []
-        for r, m in enumerate(mappers):
-            wait(r, bufs["imported"] + go_ready)          # the layers of the round before have been read; this round's gate is final
-            m.round_gate(go.data_ptr() if k > 1 else None)
-            m.halo_export_all_dev({face: lay[(r, face)].data_ptr() for face in neighbours(r, world)})
-            evs.append(record(r))
-        done, refined = [], []
-        for r, m in enumerate(mappers):
-            wait(r, evs)
-            m.halo_import_all_dev({face: lay[(nb, face ^ 1)].data_ptr() for face, nb in neighbours(r, world).items()})
-            done.append(record(r))
-            if k == 0:
-                m.merge_end()
-            else:
-                m.refine_dev(changed.data_ptr() + r * esz)
-                refined.append(record(r))
-        bufs["imported"] = done
-        if k > 0:                                         # the all-reduce(max): one reduction everybody's next round waits for
-            if cuda:
-                for ev in refined:
-                    side.wait_event(ev)
-                with torch.cuda.stream(side):
-                    torch.amax(changed, dim=0, keepdim=True, out=go)
-                    ev = torch.cuda.Event()
-                    ev.record(side)
-                go_ready = [ev]
-            else:
-                torch.amax(changed, dim=0, keepdim=True, out=go)
-    for r, m in enumerate(mappers):
-        wait(r, go_ready)
-        m.round_end(go.data_ptr())
-    if own:
-        for m in mappers:
-            m.sync()
+    topo = _InProcess(mappers, grid, device)
+    _enqueued(topo, {} if bufs is None else bufs, max_rounds, gated=True)
+    if bufs is None:                                      # nobody keeps the layers alive after the call: finish before returning
+        topo.sync()
 
 
 def exchange_rounds_local_device(mappers, grid, device, rounds=1, bufs=None):
@@ -385,40 +414,10 @@ def exchange_rounds_local_device(mappers, grid, device, rounds=1, bufs=None):
     stream waits for an event on the exporter's stream instead of an RCCL transfer.  The face layers
     are allocated once (`bufs`, kept by the caller across calls); an exporter rewrites its layers only
     after every import of the round before has finished (events recorded behind the imports)."""
-    import torch
-    world = grid[0] * grid[1] * grid[2]
-    own = bufs is None                                    # nobody keeps the layers alive after the call: finish before returning
-    bufs = {} if bufs is None else bufs
-    lay = _local_face_buffers(mappers, world, device, bufs)
-    if "streams" not in bufs:
-        bufs["streams"] = [torch.cuda.ExternalStream(m.stream_handle(), device=device) for m in mappers]
-        bufs["imported"] = []
-    streams = bufs["streams"]
-    for k in range(rounds + 1):
-        evs = []
-        for r, m in enumerate(mappers):
-            for ev in bufs["imported"]:                   # the layers of the round before have been read
-                streams[r].wait_event(ev)
-            m.halo_export_all_dev({face: lay[(r, face)].data_ptr() for face in neighbours(r, world)})
-            ev = torch.cuda.Event()
-            ev.record(streams[r])
-            evs.append(ev)
-        done = []
-        for r, m in enumerate(mappers):
-            for ev in evs:
-                streams[r].wait_event(ev)
-            m.halo_import_all_dev({face: lay[(nb, face ^ 1)].data_ptr() for face, nb in neighbours(r, world).items()})
-            ev = torch.cuda.Event()
-            ev.record(streams[r])
-            done.append(ev)
-            if k == 0:
-                m.merge_end()
-            else:
-                m.refine_async()
-        bufs["imported"] = done
-    if own:
-        for m in mappers:
-            m.sync()
+    topo = _InProcess(mappers, grid, device)
+    _enqueued(topo, {} if bufs is None else bufs, rounds, gated=False)
+    if bufs is None:                                      # nobody keeps the layers alive after the call: finish before returning
+        topo.sync()
     return rounds
 
 
@@ -427,57 +426,8 @@ def exchange_until_stable(mapper, dist, rank, world_size, device=None, max_round
     xGMI with backend "nccl", gloo on CPU); a 1-int all-reduce(sum) of the seed counts is the
     convergence test.  Returns the refinement rounds run.  sparse=True: only the known voxels of a layer travel
     (gie_halo_export_sparse); the neighbours tell each other the entry counts first, so a round is two batches."""
-    import torch
-    from .mapper import HALO_DTYPE, HALO_ENTRY_DTYPE
-    nbs = neighbours(rank, world_size)
-    rounds = 0
-    for k in range(max_rounds + 1):
-        sends, recvs, ops = {}, {}, []
-        if sparse:
-            lays = {face: mapper.halo_export_sparse(face) for face in sorted(nbs)}
-            cs = {face: torch.tensor([lays[face].shape[0]], dtype=torch.int64) for face in lays}
-            cr = {face: torch.zeros(1, dtype=torch.int64) for face in lays}
-            if device is not None:
-                cs = {f: t.to(device) for f, t in cs.items()}; cr = {f: t.to(device) for f, t in cr.items()}
-            cops = []
-            for face, nb in sorted(nbs.items()):
-                cops.append(dist.P2POp(dist.isend, cs[face], nb, group=group))
-                cops.append(dist.P2POp(dist.irecv, cr[face], nb, group=group))
-            if cops:
-                for w in dist.batch_isend_irecv(cops):
-                    w.wait()
-        for face, nb in sorted(nbs.items()):
-            if sparse:
-                t = torch.from_numpy(lays[face].view(np.uint8).copy())
-                r = torch.empty(int(cr[face].item()) * HALO_ENTRY_DTYPE.itemsize, dtype=torch.uint8)
-            else:
-                lay = mapper.halo_export(face)
-                t = torch.from_numpy(lay.view(np.uint8).copy())
-                r = torch.empty_like(t)
-            if device is not None:
-                t, r = t.to(device), r.to(device)
-            sends[face], recvs[face] = t, r
-            if t.numel():
-                ops.append(dist.P2POp(dist.isend, t, nb, group=group))
-            if r.numel():
-                ops.append(dist.P2POp(dist.irecv, r, nb, group=group))
-        if ops:
-            for w in dist.batch_isend_irecv(ops):
-                w.wait()
-        for face in sorted(nbs):
-            if sparse:
-                mapper.halo_import_sparse(face, recvs[face].cpu().numpy().view(HALO_ENTRY_DTYPE))
-            else:
-                mapper.halo_import(face, recvs[face].cpu().numpy().view(HALO_DTYPE))
-        if k == 0:
-            mapper.merge_end()
-            continue
-        n = torch.tensor([mapper.refine()], dtype=torch.int64, device=device if device is not None else "cpu")
-        dist.all_reduce(n, op=dist.ReduceOp.SUM, group=group)
-        rounds += 1
-        if int(n.item()) == 0:
-            break
-    return rounds
+    topo = _Ranked(mapper, dist, rank, world_size, group, device)
+    return _until_stable(topo, lambda k: topo.host_layers(sparse), max_rounds)
 
 
 def init_transport(torch, dist, rank, world_size, device, want="nccl", preflight_timeout_s=120):

@@ -1,7 +1,8 @@
 """Measurement aid (under rocprofv3 --kernel-trace): one 512^3 tile of a 2x2x2 arrangement, K map
 updates, each followed (argv[1] = 1) or not (0) by the device side of one exchange round with
 three shared faces (export_all -> its own layers back as ghosts -> refine): which kernels does a
-round add, and how long are they?"""
+round add, and how long are they?  The loop below is gie/tiling.py's round step (_round under
+_enqueued, ungated) for one tile whose "move" is the identity: no neighbour, no transport."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "gie-mapping_amd")]

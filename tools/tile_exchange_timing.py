@@ -1,7 +1,10 @@
 """What does the halo exchange cost next to the map update?  Two 512^3 tiles (1024 x 512 x 512
 volume) as two mappers on ONE GPU, device-resident exchange without any transport
-(tiling.exchange_until_stable_local_device): the GPU-side work of a round (export, ghost import,
-refinement), i.e. the floor a multi-GPU run adds RCCL transfers to."""
+(tiling.exchange_until_stable_local_device: the in-process topology, per-face tensors, rounds until
+no tile seeded anything): the GPU-side work of a round (export, ghost import, refinement), i.e. the
+floor a multi-GPU run adds RCCL transfers to.  Then the same frames with the rounds enqueued back
+to back (tiling.exchange_rounds_local_device: the same topology, all faces in one call, a fixed
+number of rounds with nobody waiting) — on small tiles that is the host's cost of a round."""
 import json, math, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "gie-mapping_amd")]

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """What the halo exchange of a tiled C5 run costs on the DEVICE, measured on one GPU: 2x2x2 tiles (default 256^3 each) of the
 hash world as eight mappers of this process, (a) every tile on its own (plain map updates), (b) the tiled sequence — split
-merge, export / import of the face layers between the mappers (device-resident, stream-ordered), `rounds` refinement rounds.
+merge, export / import of the face layers between the mappers (tiling.exchange_rounds_local_device: the in-process topology
+of gie/tiling.py, all faces in one call ordered on the mappers' streams), a fixed number of `rounds` refinement rounds.
 All tiles share the one GPU, so the times are sums over the eight tiles; (b) / (a) is the per-rank overhead a multi-GPU run pays
 on top of the transfers.   python tools/tiled_c5_overhead.py [tile] [rounds] [steps]"""
 import os
