@@ -15,7 +15,7 @@
 #include <unistd.h>
 static const char *const gie_kernel_names[GIE_K_NUM] = { "ogm_classify", "ray_register", "ray_free", "ray_finalize", "block_alloc", "fuse",
        "edt_pass_y", "edt_pass_x", "edt_pass_z", "mark", "frontiers", "wave_a", "wave_b", "waves", "commit", "edt_prep", "mark_commit",
-       "los", "los_query", "sdf", "sdf_query" };
+       "cloud", "los", "los_query", "sdf", "sdf_query" };
 
 #define GIE_REHASH_PERIOD 64                 /* map updates between two rebuilds of the hash table while blocks are being erased */
 static thread_local std::string g_gie_err;
@@ -118,6 +118,7 @@ struct gie_mapper {
     gie_nf1_cache nf1;                    /* the navigation function (HIP backend: gie_nf1.inc.h) */
     gie_frontier_cache fr;                /* the frontier clusters (HIP backend: gie_frontier.inc.h) */
     gie_los_cache los;                    /* line of sight (HIP backend: gie_los.inc.h) */
+    int32_t *cloud_count = nullptr;       /* display clouds (HIP backend: gie_cloud.inc.h): the counter of a _dev call that passes none, allocated at the first such call */
 };
 
 template <class T> static T *gie_dalloc(gie_mapper *m, size_t n, bool zero = true)

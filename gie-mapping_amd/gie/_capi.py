@@ -111,12 +111,27 @@ class ShortcutInfo(C.Structure):
     _fields_ = [("count", C.c_int32), ("forced", C.c_int32), ("length", C.c_float), ("reserved", C.c_int32)]
 
 
+class CloudParam(C.Structure):
+    """gie_cloud_param (include/gie.h): 32 bytes."""
+    _fields_ = [("type_mask", C.c_uint32), ("intensity", C.c_int32), ("z_lo", C.c_int32), ("z_hi", C.c_int32), ("max_points", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
+class CloudPoint(C.Structure):
+    """gie_cloud_point (include/gie.h): 16 bytes."""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("intensity", C.c_float)]
+
+
+assert C.sizeof(CloudParam) == 32 and C.sizeof(CloudPoint) == 16
 assert C.sizeof(ShortcutParam) == 16 and C.sizeof(Waypoint) == 24 and C.sizeof(ShortcutInfo) == 16
 assert C.sizeof(LosHit) == 24 and C.sizeof(View) == 64 and C.sizeof(ViewScore) == 16 and C.sizeof(LosParam) == 16 and C.sizeof(ViewParam) == 16
 
 NF1_UNKNOWN_TRAVERSABLE = 1
 NF1_FROM_FRONTIERS = 2
 LOS_UNKNOWN_OPAQUE = 1
+CLOUD_TYPE = 0
+CLOUD_DIST = 1
+VOX_UNKNOWN, VOX_FREE, VOX_OCCUPIED, VOX_FNT = 0, 1, 2, 3
 
 
 class CostMapHdr(C.Structure):
@@ -242,6 +257,11 @@ DEVICE_ONLY = {
     # path shortcutting over the opaque plane (include/gie.h): device library only
     "path_shortcut": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(ShortcutParam), C.c_void_p, C.c_void_p]),
     "path_shortcut_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(ShortcutParam), C.c_void_p, C.c_void_p]),
+    # display clouds out of the local planes and the block pool (include/gie.h): device library only
+    "cloud_local": (C.c_int, [_H, C.POINTER(CloudParam), C.c_void_p, C.c_void_p]),
+    "cloud_local_dev": (C.c_int, [_H, C.POINTER(CloudParam), C.c_void_p, C.c_void_p]),
+    "cloud_global": (C.c_int, [_H, C.POINTER(CloudParam), C.c_void_p, C.c_void_p]),
+    "cloud_global_dev": (C.c_int, [_H, C.POINTER(CloudParam), C.c_void_p, C.c_void_p]),
 }
 DEVICE_ONLY.update(ROUND_API)
 

@@ -13,8 +13,8 @@ import sys
 import numpy as np
 
 from . import _capi
-from ._capi import LOS_UNKNOWN_OPAQUE, NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE
-from ._capi import CamParam, Config, CostMapHdr, FrameStats, FrontierParam, LosParam, MultiScanParam, Nf1Param, ScanParam, ShortcutParam, ViewParam, Voxel
+from ._capi import CLOUD_DIST, CLOUD_TYPE, LOS_UNKNOWN_OPAQUE, NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE, VOX_FNT, VOX_FREE, VOX_OCCUPIED, VOX_UNKNOWN
+from ._capi import CamParam, CloudParam, Config, CostMapHdr, FrameStats, FrontierParam, LosParam, MultiScanParam, Nf1Param, ScanParam, ShortcutParam, ViewParam, Voxel
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG, "csrc", "libgie_hip.so")
@@ -32,6 +32,9 @@ VIEW_SCORE_DTYPE = np.dtype([("unknown", "<i4"), ("frontier", "<i4"), ("occupied
 # gie_waypoint (24 bytes), gie_shortcut_info (16 bytes)
 WAYPOINT_DTYPE = np.dtype([("xyz", "<i4", (3,)), ("index", "<i4"), ("min_edt", "<f4"), ("forced", "<i4")])
 SHORTCUT_INFO_DTYPE = np.dtype([("count", "<i4"), ("forced", "<i4"), ("length", "<f4"), ("reserved", "<i4")])
+# gie_cloud_point (16 bytes)
+CLOUD_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("intensity", "<f4")])
+CLOUD_NO_BAND = (-2 ** 31, 2 ** 31 - 1)
 VOXEL_DTYPE = np.dtype([("occ_val", "u1"), ("vox_type", "i1"), ("pad", "<i2"), ("dist_sq", "<i4"),
                         ("coc", "<i4", (3,))])
 
@@ -701,3 +704,50 @@ class Mapper(MapperBase):
         p = self.shortcut_param(lookahead, max_wp)
         self._chk(self._f["path_shortcut_dev"](self._h, C.c_void_p(d_path or None), C.c_void_p(d_len or None), int(n), int(max_len), C.byref(p),
                                                C.c_void_p(d_wp or None), C.c_void_p(d_info or None)))
+
+    # --- display clouds (include/gie.h) -------------------------------------------------------
+    def cloud_param(self, type_mask, intensity=CLOUD_TYPE, z_lo=None, z_hi=None, max_points=0):
+        """gie_cloud_param: type_mask = bits 1 << VOX_*; z_lo / z_hi = GLOBAL voxel z, inclusive (None: open on that side)."""
+        p = CloudParam()
+        p.type_mask, p.intensity, p.max_points = int(type_mask), int(intensity), int(max_points)
+        p.z_lo = CLOUD_NO_BAND[0] if z_lo is None else int(z_lo)
+        p.z_hi = CLOUD_NO_BAND[1] if z_hi is None else int(z_hi)
+        return p
+
+    def _cloud(self, name, type_mask, intensity, z_lo, z_hi, max_points, out):
+        n = C.c_int32(0)
+        if max_points is None:                              # count first, then fetch
+            if out is not None:
+                max_points = len(out)
+            else:
+                p = self.cloud_param(type_mask, intensity, z_lo, z_hi, 0)
+                self._chk(self._f[name](self._h, C.byref(p), None, C.byref(n)))
+                max_points = n.value
+        max_points = int(max_points)
+        if out is None:
+            out = np.zeros(max(max_points, 0), CLOUD_DTYPE)
+        elif out.dtype != CLOUD_DTYPE or out.ndim != 1 or len(out) < max_points or not out.flags.c_contiguous:
+            raise ValueError("%s: out must be a contiguous CLOUD_DTYPE array of at least max_points records" % name)
+        p = self.cloud_param(type_mask, intensity, z_lo, z_hi, max_points)
+        self._chk(self._f[name](self._h, C.byref(p), _ptr(out) if out.size else None, C.byref(n)))
+        return out[:min(n.value, max_points)], n.value
+
+    def cloud_local(self, type_mask, intensity=CLOUD_TYPE, z_lo=None, z_hi=None, max_points=None, out=None):
+        """The selected voxels of the local volume -> (points, count): points = the written records (CLOUD_DTYPE, a view of `out`
+        when one is given), count = all selected voxels, also beyond max_points.  max_points=None counts first, then fetches all
+        (or takes len(out)).  Synchronises."""
+        return self._cloud("cloud_local", type_mask, intensity, z_lo, z_hi, max_points, out)
+
+    def cloud_global(self, type_mask, intensity=CLOUD_TYPE, z_lo=None, z_hi=None, max_points=None, out=None):
+        """The same over every live block of the global map."""
+        return self._cloud("cloud_global", type_mask, intensity, z_lo, z_hi, max_points, out)
+
+    def cloud_local_dev(self, d_out, d_count, type_mask, intensity=CLOUD_TYPE, z_lo=None, z_hi=None, max_points=0):
+        """Records (max_points x 16 bytes, 16-byte aligned) and the count (one int32) in DEVICE buffers (raw addresses; 0 = not
+        wanted), on the mapper's stream without a host wait."""
+        p = self.cloud_param(type_mask, intensity, z_lo, z_hi, max_points)
+        self._chk(self._f["cloud_local_dev"](self._h, C.byref(p), C.c_void_p(d_out or None), C.c_void_p(d_count or None)))
+
+    def cloud_global_dev(self, d_out, d_count, type_mask, intensity=CLOUD_TYPE, z_lo=None, z_hi=None, max_points=0):
+        p = self.cloud_param(type_mask, intensity, z_lo, z_hi, max_points)
+        self._chk(self._f["cloud_global_dev"](self._h, C.byref(p), C.c_void_p(d_out or None), C.c_void_p(d_count or None)))

@@ -13,7 +13,8 @@
  *                         src/kernel/par_wave/glb_hash_map.cu:209-247, README.md:163-170
  *   VolumetricMapper      VOLMAPNODE ctor + publishMap, src/volumetric_mapper.cpp:6-224, with
  *                         CostMap = msg/CostMap.msg
- * The ROS transport (subscriptions, message_filters, tf broadcast, RViz clouds) is not part of it.
+ *   DisplayClouds         the four point clouds of VOLMAPNODE::visualize, include/volumetric_mapper.h:181-357
+ * The ROS transport (subscriptions, message_filters, tf broadcast, the RViz publishers) is not part of it.
  * Written from the behaviour described in those files; no reference code is reused (PCL's
  * KD-tree / MomentOfInertia are replaced by plain loops).
  */
@@ -46,6 +47,9 @@ struct Parameters {
     bool for_motion_planner = false;
     float robot_r = 0.4f;
     bool display_loc_edt = false, display_loc_ogm = false, display_glb_edt = true, display_glb_ogm = true;
+    bool cpu_mirror = true;              /* no counterpart in the reference, which always mirrors: the global display flags switch the changed-block stream on and
+                                          * visualize() reads the mirror.  false: the stream stays off (the map update runs its fused sweep) and visualize() takes the
+                                          * global clouds from the device (gie_cloud_global); `mirror` stays empty */
     bool profile_loc_rms = false, profile_glb_rms = false;
     std::string log_name = "GIE_log.csv";
     std::string data_case = "ugv_corridor";
@@ -94,6 +98,7 @@ struct Parameters {
         if (k == "for_motion_planner") for_motion_planner = b(); else if (k == "robot_r") robot_r = fl();
         else if (k == "display_loc_edt") display_loc_edt = b(); else if (k == "display_loc_ogm") display_loc_ogm = b();
         else if (k == "display_glb_edt") display_glb_edt = b(); else if (k == "display_glb_ogm") display_glb_ogm = b();
+        else if (k == "cpu_mirror") cpu_mirror = b();
         else if (k == "profile_loc_rms") profile_loc_rms = b(); else if (k == "profile_glb_rms") profile_glb_rms = b();
         else if (k == "log_name") log_name = v; else if (k == "data_case") data_case = v;
         else if (k == "vis_interval") vis_interval = in(); else if (k == "occupancy_threshold") occupancy_threshold = in();
@@ -355,6 +360,10 @@ struct CostMap {                        /* msg/CostMap.msg */
 
 struct Pose { float pos[3]; float quat_wxyz[4]; };
 
+/* what VOLMAPNODE::visualize publishes (volumetric_mapper.h:181-357): x, y, z in metres; intensity = the type (2) in the two OGM
+ * clouds (the reference's global one is PointXYZ: ignore it there), the distance in metres in the two EDT clouds */
+struct DisplayClouds { std::vector<gie_cloud_point> loc_ogm, loc_edt, glb_ogm, glb_edt; };
+
 class VolumetricMapper {
 public:
     explicit VolumetricMapper(const Parameters &p, int device_id = 0) : param(p), cfg_(p.to_config(device_id))
@@ -362,7 +371,7 @@ public:
         m_ = gie_create(&cfg_);
         if (!m_) throw std::runtime_error(std::string("gie_create: ") + gie_last_error());
         ext.assign_premap(p.obsbbx_ll, p.obsbbx_ur);
-        streaming_ = p.display_glb_edt || p.display_glb_ogm;       /* volumetric_mapper.cpp:182,196-198 */
+        streaming_ = p.cpu_mirror && (p.display_glb_edt || p.display_glb_ogm);       /* volumetric_mapper.cpp:182,196-198 */
         if (streaming_) chk(gie_stream_enable(m_, 1));
         if (p.for_motion_planner) {
             cost_map.x_size = cfg_.local_size[0]; cost_map.y_size = cfg_.local_size[1]; cost_map.z_size = cfg_.local_size[2];
@@ -510,6 +519,41 @@ public:
         chk(gie_view_gain(m_, views.data(), (int)views.size(), &vp, scores.data()));
     }
 
+    /* VOLMAPNODE::visualize without the publishers: the clouds the display flags ask for (the others come back empty), of the map as
+     * it stands.  sensor_pos is the reference's argument: its z is replaced by vis_height before the slice's z is taken
+     * (volumetric_mapper.h:339-341), so only vis_height decides.  The local clouds always come from the device (gie_cloud_local);
+     * the global ones from the mirror (cpu_mirror, the reference's loop over its blocks) or from the device (gie_cloud_global). */
+    const DisplayClouds &visualize(const float sensor_pos[3])
+    {
+        (void)sensor_pos;
+        const float w = cfg_.voxel_width;
+        const uint32_t occ = 1u << GIE_VOX_OCCUPIED, known = (1u << GIE_VOX_FREE) | (1u << GIE_VOX_OCCUPIED) | (1u << GIE_VOX_FNT);
+        const int32_t none_lo = std::numeric_limits<int32_t>::min(), none_hi = std::numeric_limits<int32_t>::max();
+        const int32_t slice = (int32_t)std::floor(param.vis_height / w + 0.5f);      /* gie_pos2coord(vis_height, w), in fp32 */
+        clouds.loc_ogm.clear(); clouds.loc_edt.clear(); clouds.glb_ogm.clear(); clouds.glb_edt.clear();
+        if (param.display_loc_ogm) cloud(gie_cloud_local, occ, GIE_CLOUD_TYPE, none_lo, none_hi, clouds.loc_ogm);
+        if (param.display_loc_edt) cloud(gie_cloud_local, known, GIE_CLOUD_DIST, none_lo, none_hi, clouds.loc_edt);
+        if (!param.cpu_mirror) {
+            if (param.display_glb_ogm) cloud(gie_cloud_global, occ, GIE_CLOUD_TYPE, none_lo, none_hi, clouds.glb_ogm);
+            if (param.display_glb_edt) cloud(gie_cloud_global, known, GIE_CLOUD_DIST, slice, slice, clouds.glb_edt);
+        } else if (param.display_glb_ogm || param.display_glb_edt) {      /* publish_glb_2_rviz */
+            for (size_t b = 0; b < mirror.block_keys.size(); b++) {
+                const BlockMirror::Key k = mirror.block_keys[b];
+                for (int i = 0; i < GIE_BLOCK_VOXELS; i++) {
+                    const gie_voxel &v = mirror.blocks[b * GIE_BLOCK_VOXELS + i];
+                    if (v.vox_type == GIE_VOX_UNKNOWN) continue;
+                    const int g[3] = { k.x * 8 + (i >> 6), k.y * 8 + ((i >> 3) & 7), k.z * 8 + (i & 7) };
+                    const gie_cloud_point pt = { (float)g[0] * w, (float)g[1] * w, (float)g[2] * w, (float)v.vox_type };
+                    if (param.display_glb_ogm && v.vox_type == GIE_VOX_OCCUPIED) clouds.glb_ogm.push_back(pt);
+                    if (!param.display_glb_edt || g[2] != slice || v.dist_sq < 0 || v.dist_sq >= 900000) continue;     /* invalid_dist_glb */
+                    clouds.glb_edt.push_back({ pt.x, pt.y, pt.z, sqrtf((float)v.dist_sq) * w });
+                }
+            }
+        }
+        return clouds;
+    }
+    DisplayClouds clouds;
+
     gie_mapper *handle() { return m_; }
     const gie_config &config() const { return cfg_; }
 
@@ -522,6 +566,18 @@ public:
     int frame = 0;
 private:
     static void chk(int rc) { if (rc != GIE_OK) throw std::runtime_error(std::string("gie: ") + gie_last_error()); }
+    /* one display cloud: count, then fetch */
+    template <class F> void cloud(F fn, uint32_t mask, int intensity, int32_t z_lo, int32_t z_hi, std::vector<gie_cloud_point> &out)
+    {
+        gie_cloud_param p = {};
+        p.type_mask = mask; p.intensity = intensity; p.z_lo = z_lo; p.z_hi = z_hi;
+        int32_t n = 0;
+        chk(fn(m_, &p, nullptr, &n));
+        out.resize((size_t)n);
+        if (n == 0) return;
+        p.max_points = n;
+        chk(fn(m_, &p, out.data(), &n));
+    }
     gie_config cfg_;
     gie_mapper *m_ = nullptr;
     bool streaming_ = false;

@@ -547,6 +547,69 @@ int gie_path_shortcut(gie_mapper *h, const int32_t *path_xyz, const int32_t *len
 int gie_path_shortcut_dev(gie_mapper *h, const int32_t *d_path_xyz, const int32_t *d_len, int n, int max_len,
                           const gie_shortcut_param *p, gie_waypoint *d_wp, gie_shortcut_info *d_info);
 
+/* ---- display clouds: the occupied voxels and the EDT slices a viewer shows, compacted on the device — the ROS-free half of
+ * VOLMAPNODE::visualize (include/volumetric_mapper.h:181-357), which the reference runs every vis_interval map ticks over the local
+ * volume and over every block of its CPU mirror.  Here the clouds come straight out of the local planes and the block pool: a caller
+ * that only displays its map needs neither gie_read_local of the whole volume nor gie_stream_enable(1) and a mirror.
+ *
+ * A cloud is a set of gie_cloud_point records, one per SELECTED voxel; every value is exact and nothing depends on a schedule but
+ * the order of the records.  w = voxel_width.
+ *  local form    over the local volume at the point of the mapper's stream where the call is enqueued.  For local voxel v,
+ *                g = v + pvt (gie_get_pivot); type(v) and edt(v) are exactly what gie_read_local would return there.
+ *                  selected   iff bit type(v) of type_mask is set and z_lo <= g_z <= z_hi;
+ *                  intensity  GIE_CLOUD_TYPE: (float)type(v);  GIE_CLOUD_DIST: edt(v) * w — one fp32 multiply; no voxel is dropped
+ *                             for its distance, as in the reference's local loop.
+ *                GIE_ERR_INVALID before the first gie_set_pose.
+ *  global form   over every voxel g of every LIVE block of the pool: a block gie_query_global finds — its slot below the number
+ *                handed out and its key not erased (gie_config.retain_radius_blocks).  Erased blocks and slots never handed out
+ *                contribute nothing; an empty pool gives count 0.  With r = the record gie_query_global returns for g at that
+ *                point of the stream (the records a fused update has left to the pair plane included; the call itself stores
+ *                nothing: it does not write into the map at all):
+ *                  selected   iff bit r.vox_type of type_mask is set, z_lo <= g_z <= z_hi and, with GIE_CLOUD_DIST,
+ *                             0 <= r.dist_sq < 900000 (the reference's invalid_dist_glb, voxmap_utils.cuh:162-165: that literal,
+ *                             not GIE_EMPTY_VALUE);
+ *                  intensity  GIE_CLOUD_TYPE: (float)r.vox_type;  GIE_CLOUD_DIST: sqrtf((float)r.dist_sq) * w (sqrtf as in
+ *                             gie_read_sdf).
+ *  both          x, y, z = (float)g_k * w: coord2pos (local_batch.h:260-267), the convention of gie_read_frontier_clusters' goals.
+ *                *count = the number of selected voxels, also when it exceeds max_points.  Exactly min(count, max_points) records
+ *                are written: distinct selected voxels in unspecified order — which ones, when the cloud does not fit, is
+ *                unspecified too (the convention of gie_stream_changed); entries beyond them are left as they were.
+ *                max_points == 0 with a NULL out only counts.
+ * GIE_ERR_INVALID: a NULL param; type_mask 0 or with bit 0 (UNKNOWN) or a bit >= 4 set; an intensity other than the two; z_lo > z_hi;
+ * max_points < 0; non-zero reserved; a NULL out with max_points > 0; a NULL count together with a NULL out; a tiled mapper (its pool
+ * holds ghost blocks of other tiles: all four refuse, as every planner section does); in the _dev forms a d_out that is not 16-byte
+ * aligned.  Nothing is written then.
+ * The host forms stage through the two scratch slots of the host forms and synchronise.  The _dev forms take DEVICE buffers and are
+ * enqueued on the mapper's stream with no host wait and no read-back (the number of slots handed out is read on the device):
+ * d_count is zeroed on the stream and accumulated in place; one memset and at most one launch, no grid barrier.  A call is legal
+ * wherever gie_query_global is, also between gie_fuse and gie_merge of one update.  Map updates are not changed by it; a mapper
+ * that never calls it allocates and launches nothing (a _dev call without d_count allocates one counter word).
+ * Cost: GIE_CLOUD_TYPE reads 1 byte per voxel of the live blocks inside the band (a one-layer band: 64 bytes per block of that
+ * block row, a key per block otherwise); GIE_CLOUD_DIST 8 bytes more per voxel that passed mask and band; 16 bytes per record.
+ *
+ * The reference's four clouds (volumetric_mapper.h:181-357; NOBAND = z_lo INT32_MIN, z_hi INT32_MAX):
+ *   local OGM    gie_cloud_local   { 1 << GIE_VOX_OCCUPIED, GIE_CLOUD_TYPE, NOBAND }
+ *   local EDT    gie_cloud_local   { 1 << GIE_VOX_FREE | 1 << GIE_VOX_OCCUPIED | 1 << GIE_VOX_FNT, GIE_CLOUD_DIST, NOBAND }
+ *   global OGM   gie_cloud_global  { 1 << GIE_VOX_OCCUPIED, GIE_CLOUD_TYPE, NOBAND }   (its PointXYZ: ignore the intensity)
+ *   global EDT   gie_cloud_global  { 1 << GIE_VOX_FREE | 1 << GIE_VOX_OCCUPIED | 1 << GIE_VOX_FNT, GIE_CLOUD_DIST,
+ *                                    z_lo = z_hi = gie_pos2coord(vis_height, w) }
+ * and { 1 << GIE_VOX_FNT, GIE_CLOUD_TYPE } is the frontier display.
+ * gie_profile_read: "cloud" = all four, one bracket per call (the entry before "los"). */
+#define GIE_CLOUD_TYPE 0            /* intensity = (float)vox_type                  */
+#define GIE_CLOUD_DIST 1            /* intensity = the voxel's distance, metres     */
+typedef struct gie_cloud_param {    /* 32 bytes */
+    uint32_t type_mask;     /* bit t set: voxels of type t (GIE_VOX_FREE / OCCUPIED / FNT) are selected */
+    int32_t  intensity;     /* GIE_CLOUD_TYPE or GIE_CLOUD_DIST */
+    int32_t  z_lo, z_hi;    /* GLOBAL voxel z, both inclusive; INT32_MIN .. INT32_MAX = no band */
+    int32_t  max_points;    /* >= 0: capacity of `out` */
+    int32_t  reserved[3];   /* 0 */
+} gie_cloud_param;
+typedef struct gie_cloud_point { float x, y, z, intensity; } gie_cloud_point;   /* 16 bytes: PCL's PointXYZI without padding */
+int gie_cloud_local(gie_mapper *h, const gie_cloud_param *p, gie_cloud_point *out, int32_t *count);
+int gie_cloud_local_dev(gie_mapper *h, const gie_cloud_param *p, gie_cloud_point *d_out, int32_t *d_count);
+int gie_cloud_global(gie_mapper *h, const gie_cloud_param *p, gie_cloud_point *out, int32_t *count);
+int gie_cloud_global_dev(gie_mapper *h, const gie_cloud_param *p, gie_cloud_point *d_out, int32_t *d_count);
+
 /* ---- changed-block streaming: the CPU mirror the reference keeps for RViz and CPU planners.
  * GlbHashMap::streamPipeline / streamD2H / getUpdatedAddr (glb_hash_map.cu:209-247,
  * unify_helper.cuh:11-32), fed by the stream_VB_keys_D appends of the fuse / wave / commit kernels
