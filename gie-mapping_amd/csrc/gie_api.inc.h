@@ -1498,6 +1498,18 @@ extern "C" int gie_debug_tile_state(gie_mapper *m, uint8_t *tknown, uint8_t *tsk
     scalars[GIE_DBG_TS_STATE2] = cnt[GIE_CNT_STATE2];
     return be_sync(&m->be) != 0 ? GIE_ERR_DEVICE : GIE_OK;
 }
+/* test hook (not in gie.h): the frame counter as if `ct` map updates had run — the next gie_set_pose counts ct + 1.  Nothing else
+ * changes: the stamp planes keep what earlier updates wrote, so a test can stand right before the stamp wrap of gie_set_pose
+ * (ct + 1 a multiple of 2^18) without 262 144 updates.  Between two map updates only, never inside an open merge.  What remembers
+ * a count keeps it too: the tick of the last early flush of owed pairs (pp.flushed_ct, gie_pp_before_import) is compared with the
+ * counter, so a test must not set ct so that ct + 1 is the count of an update it has already run with a halo import. */
+extern "C" int gie_debug_set_frame(gie_mapper *m, int ct)
+{
+    if (!m || ct < 0) { gie_set_err("gie_debug_set_frame: bad arguments"); return GIE_ERR_INVALID; }
+    if (m->merge_open) { gie_set_err("gie_debug_set_frame: a merge is open (gie_merge_end first)"); return GIE_ERR_INVALID; }
+    m->c.map_ct = ct;
+    return GIE_OK;
+}
 #endif /* GIE_TEST_HOOKS */
 extern "C" int gie_profile_enable(gie_mapper *m, int on)
 {

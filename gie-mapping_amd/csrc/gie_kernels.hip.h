@@ -2905,7 +2905,11 @@ __device__ __forceinline__ void gie_wave_a_block(const gie_ctx &c, gie_gridbar &
             L.prop[v] = GIE_NOPROP;
             L.coc[v] = ncoc;
             L.pair[v] = gie_pair_make((int)(t >> 3), gie_pack_wr(nw[0], nw[1], nw[2]));
-            L.flag[v] = (uint8_t)((L.flag[v] & ~(GIE_WA_RAISED | GIE_WA_VANISHED)) | GIE_WA_DIRTY | GIE_WA_PAIR | GIE_WA_PUSHB);
+            /* (GIE_WA_OK anew: the obstacle is a valid neighbour's now.  A seed of obtainFrontiers was raised to an obstacle inside the
+             * volume, which is invalid when it lies above 900000 — loaded as not OK, the voxel would stay so for the rest of the
+             * block-run and lower no entry, where raise_outside reads the record it has just been given) */
+            L.flag[v] = (uint8_t)((L.flag[v] & ~(GIE_WA_RAISED | GIE_WA_VANISHED | GIE_WA_OK)) | (gie_invalid_dist(c, (int)(t >> 3)) ? 0u : GIE_WA_OK)
+                                  | GIE_WA_DIRTY | GIE_WA_PAIR | GIE_WA_PUSHB);
         }
         if (__ballot(deferred) != 0ull) {
             /* An entry whose nearest offered obstacle lies OUTSIDE the wave range (it cannot be packed into a pair).  The reference
@@ -2950,7 +2954,9 @@ __device__ __forceinline__ void gie_wave_a_block(const gie_ctx &c, gie_gridbar &
                 }
                 L.prop[v] = GIE_NOPROP;
                 L.coc[v] = fin;
-                unsigned f = (L.flag[v] & ~(GIE_WA_RAISED | GIE_WA_VANISHED)) | GIE_WA_DIRTY;
+                int fc[3];
+                gie_unpack_crd(fin, &fc[0], &fc[1], &fc[2]);
+                unsigned f = (L.flag[v] & ~(GIE_WA_RAISED | GIE_WA_VANISHED | GIE_WA_OK)) | ((gie_invalid_coc(fc[0], fc[1], fc[2]) || gie_invalid_dist(c, cd)) ? 0u : GIE_WA_OK) | GIE_WA_DIRTY;
                 if (spair != GIE_NOPROP) { L.pair[v] = spair; f |= GIE_WA_PAIR | GIE_WA_PUSHB; }
                 L.flag[v] = (uint8_t)f;
             }
@@ -3214,6 +3220,10 @@ __device__ __forceinline__ void gie_wave_b_block(const gie_ctx &c, gie_gridbar &
     unsigned done = 0, chg = 0;                           /* my voxels committed in this round / whose pair has changed */
     int nvis = 0;
     const int emax = c.empty_value;
+    /* lower_outside reads a neighbour's stored obstacle when it proposes to it (wave_core.cuh:286-290: a coordinate above 900000 is
+     * invalid), so a voxel that this block-run has committed to such an obstacle takes no proposal from then on: its GIE_WB_OK goes
+     * with the commit.  Only a wave range that reaches beyond 900000 holds such obstacles: poses within 1023 voxels of the limit. */
+    const bool far_edge = c.upvt[0] + c.wr[0] > 900000 || c.upvt[1] + c.wr[1] > 900000 || c.upvt[2] + c.wr[2] > 900000;
     bool first = round == 0;                              /* round 0, first level: the seeds enter with the pair they hold */
     for (;;) {
         unsigned tk = 0;                                  /* my voxels that become entries in this level */
@@ -3238,7 +3248,15 @@ __device__ __forceinline__ void gie_wave_b_block(const gie_ctx &c, gie_gridbar &
                     nvis++;
                     /* the distance stored before the commit: the one loaded with the block, or — the voxel has been committed in this
                      * block-run before — the one that commit stored: its pair's until now */
-                    if (((done >> j) & 1u) ? od <= c.cutoff_sq : ((sdok >> j) & 1u) != 0u) { done |= 1u << j; tk |= 1u << j; }
+                    if (((done >> j) & 1u) ? od <= c.cutoff_sq : ((sdok >> j) & 1u) != 0u) {
+                        done |= 1u << j; tk |= 1u << j;
+                        if (far_edge) {                   /* the commit: the pair's parent is the voxel's obstacle from here on */
+                            const int cell = GIE_WB_P((la - j) & 7, (lb - j) & 7, j);
+                            int cw[3];
+                            gie_unpack_wr(gie_pair_par(first ? L.pair[cell] : cd[j]), &cw[0], &cw[1], &cw[2]);
+                            if (gie_invalid_coc(cw[0] + c.upvt[0], cw[1] + c.upvt[1], cw[2] + c.upvt[2])) L.flag[cell] = 0u;
+                        }
+                    }
                 }
             }
         }

@@ -147,7 +147,20 @@ gie_mapper *gie_create(const gie_config *cfg);
 void gie_destroy(gie_mapper *h);
 
 /* odom2trans/trans2proj (projection.h:14-33) + LocMap::calculate_pivot_origin /
- * calculate_update_pivot (local_batch.h:129-166).  Also advances the map tick (_time++). */
+ * calculate_update_pivot (local_batch.h:129-166).  Also advances the map tick (_time++).
+ * Limits (GIE_ERR_INVALID beyond them; a refused pose changes nothing: no tick, no pivot):
+ *  position   every component finite with |pos_k| <= 1.0e6 m, AND its voxel gie_pos2coord(pos_k) = floor(pos_k / w + 0.5) within
+ *             +-900000: at w = 0.125 m that is +-112.5 km; above w = 10/9 m the limit in metres is the nearer one.  Both ends are
+ *             accepted.  Out there one float32 ulp of a world coordinate is 1/128 m (>= 65536 m): poses, sensor points and query
+ *             points are rounded to that before the library sees them, and results are bit for bit the oracle's all the same.
+ *  900000     the reference calls a closest obstacle with a coordinate ABOVE 900000 invalid (invalid_coc_glb,
+ *             voxmap_utils.cuh:167-172; its "no obstacle" key is 999999) and so does this library: stored records of voxels
+ *             outside the local volume whose obstacle lies above +900000 on an axis are never propagated by the waves.  The rule
+ *             is one-sided (nothing happens at -900000), and it only matters for poses within half a volume of +900000, where a
+ *             map differs from the same drive elsewhere in such records.
+ *  tick       the 18 low bits of the tick stamp the wave planes; at every multiple of 2^18 updates (7.3 h at 10 Hz) gie_set_pose
+ *             clears the stamps once.  Nothing observable changes there: maps and statistics go on as the oracle's do, and
+ *             gie_frame_stats.frame keeps counting. */
 int gie_set_pose(gie_mapper *h, const float pos[3], const float quat_wxyz[4]);
 
 /* PntcldMapMaker::updateLocalOGM (pntcld_map_maker.cpp:63-73) →

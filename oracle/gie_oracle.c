@@ -1393,6 +1393,15 @@ int go_stream_changed(gie_oracle *o, int32_t *keys, gie_voxel *vox, int max_bloc
     return 0;
 }
 int go_get_pivot(gie_oracle *o, int32_t p[3]) { p[0] = o->pvt[0]; p[1] = o->pvt[1]; p[2] = o->pvt[2]; return 0; }
+/* test hook, the twin of the library's gie_debug_set_frame: _time as if `ct` map updates had run (the next go_set_pose counts
+ * ct + 1); nothing else changes.  The oracle's stamps are full-width integers (wave_layer = -_time, update_ct = +-_time): there is
+ * nothing to wrap here, which is what the library's 18-bit stamps are compared with. */
+int go_debug_set_frame(gie_oracle *o, int ct)
+{
+    if (!o || ct < 0) return 1;
+    o->map_ct = ct;
+    return 0;
+}
 
 /* ------------------------------------------------------------------ ground truth for the EDT stage */
 /* Exact EDT by definition: for every voxel the minimum squared distance to any occupied voxel

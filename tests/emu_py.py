@@ -29,6 +29,7 @@ def load():
                 os.replace(tmp, EMU_SO)
         global _lib
         lib = _lib = C.CDLL(EMU_SO)
+        lib.gie_debug_set_frame.argtypes = [C.c_void_p, C.c_int]
         _fns = _capi.bind(lib, "gie_", {**_capi.ROUND_API, "last_error": (C.c_char_p, []), "sync": (C.c_int, [C.c_void_p]),
                                         "halo_export_sparse": _capi.DEVICE_ONLY["halo_export_sparse"],
                                         "halo_import_sparse": _capi.DEVICE_ONLY["halo_import_sparse"]})
@@ -58,3 +59,8 @@ class EmuMapper(MapperBase):
         """the per-tile state the last map update leaves to the next one (gie_debug_tile_state, test hook)"""
         from hooks_py import read_tile_state
         return read_tile_state(_lib, self)
+
+    def debug_set_frame(self, ct):
+        """the frame counter as if `ct` map updates had run (gie_debug_set_frame, test hook): the next set_pose counts ct + 1"""
+        if _lib.gie_debug_set_frame(self._h, int(ct)):
+            raise RuntimeError(self._err())

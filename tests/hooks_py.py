@@ -31,6 +31,7 @@ def load():
         _lib.gie_debug_fault_barrier.argtypes = [C.c_void_p, C.c_int]
         _lib.gie_debug_place_probe.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float)]
         _lib.gie_debug_nbr_check.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        _lib.gie_debug_set_frame.argtypes = [C.c_void_p, C.c_int]
     return _fns
 
 
@@ -60,6 +61,11 @@ class HooksMapper(Mapper):
     def debug_tile_state(self):
         """the per-tile state the last map update leaves to the next one (gie_debug_tile_state); call it before read_batch_edt"""
         return read_tile_state(_lib, self)
+
+    def debug_set_frame(self, ct):
+        """the frame counter as if `ct` map updates had run (gie_debug_set_frame): the next set_pose counts ct + 1"""
+        if _lib.gie_debug_set_frame(self._h, int(ct)):
+            raise RuntimeError(self._err())
 
 
 # gie_debug_tile_state's scalars, in order (gie_api.inc.h GIE_DBG_TS_*)

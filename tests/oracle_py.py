@@ -33,6 +33,8 @@ def load():
         _lib.go_edt_mt.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _lib.go_edt_only.restype = C.c_int
         _lib.go_edt_only.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.go_debug_set_frame.restype = C.c_int
+        _lib.go_debug_set_frame.argtypes = [C.c_void_p, C.c_int]
     return _fns
 
 
@@ -47,6 +49,11 @@ class OracleMapper(MapperBase):
         _lib.go_edt_only(self._h, t.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p),
                          c.ctypes.data_as(C.c_void_p))
         return d, c
+
+    def debug_set_frame(self, ct):
+        """_time as if `ct` map updates had run (go_debug_set_frame): the next set_pose counts ct + 1"""
+        if _lib.go_debug_set_frame(self._h, int(ct)):
+            raise RuntimeError("go_debug_set_frame: bad arguments")
 
 
 def brute_force_edt(occ):

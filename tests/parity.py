@@ -12,9 +12,20 @@ class Scenario:
     def __init__(self, name, size, voxel=0.1, sensor="depth", frames=6, delta_vox=5, yaw_deg=40.0, seed=2,
                  cutoff_dist=2.0, fast_mode=False, n_boxes=30, extent=(4.0, 4.0, 1.5), for_motion_planner=False,
                  img=(120, 160, 130.0), toggle=0.25, lidar_az=360, ext_boxes=False, min_h=-1000.0, max_h=1000.0,
-                 max_depth=6.0, p_occ=0.01, retain=0, max_blocks=0, probe_margin=12, turn=0, steps=None):
+                 max_depth=6.0, p_occ=0.01, retain=0, max_blocks=0, probe_margin=12, turn=0, steps=None, base_vox=(0, 0, 0)):
         self.__dict__.update(locals())
         del self.__dict__["self"]
+
+    def shift(self):
+        """base_vox in metres: what every pose of the drive is moved by (exact in float32 where the voxel width is a power of two)"""
+        return tuple(int(b) * float(self.voxel) for b in self.base_vox)
+
+    def _shifted(self, pos):
+        # the scene is made at the unshifted pose (sensor data are in the sensor frame, a label plane is the hash world at the unshifted
+        # pivot); only the pose the mappers are given moves: the run is the translation twin of the one at base_vox = (0, 0, 0)
+        if not any(self.base_vox):
+            return pos
+        return tuple(np.float32(float(pos[i]) + d) for i, d in enumerate(self.shift()))
 
     def config(self):
         return gie.make_config(self.voxel, self.size, cutoff_dist=self.cutoff_dist, fast_mode=self.fast_mode,
@@ -22,6 +33,10 @@ class Scenario:
                                retain_radius_blocks=self.retain, max_blocks=self.max_blocks)
 
     def frames_iter(self):
+        for pos, q, kind, data, kw in self._frames_unshifted():
+            yield self._shifted(pos), q, kind, data, kw
+
+    def _frames_unshifted(self):
         world = scenes.BoxWorld(self.seed, extent=self.extent, n_boxes=self.n_boxes, toggle_frac=self.toggle)
         rows, cols, f = self.img
         cx, cy = (cols - 1) / 2.0, (rows - 1) / 2.0
@@ -135,10 +150,10 @@ def probe_left_behind(prev_pvt, pvt, size, rng, n=6000):
     return np.ascontiguousarray(xyz[rng.permutation(len(xyz))[:n]], dtype=np.int32)
 
 
-def set_ext_boxes(*mappers):
-    """the two boxes of the scenarios with ext_boxes=True (one of them inactive)"""
-    ll = np.array([[-100, -100, -100], [0.5, -1.0, -1.0]], np.float32)
-    ur = np.array([[100, 100, 100], [1.0, 1.0, 0.5]], np.float32)
+def set_ext_boxes(*mappers, shift=(0.0, 0.0, 0.0)):
+    """the two boxes of the scenarios with ext_boxes=True (one of them inactive), moved by `shift` metres"""
+    ll = (np.array([[-100, -100, -100], [0.5, -1.0, -1.0]], np.float64) + np.asarray(shift, np.float64)).astype(np.float32)
+    ur = (np.array([[100, 100, 100], [1.0, 1.0, 0.5]], np.float64) + np.asarray(shift, np.float64)).astype(np.float32)
     act = np.array([0, 1], np.uint8)
     for m in mappers:
         m.set_ext_boxes(ll, ur, act)
@@ -170,21 +185,24 @@ def _compare_after_merge(sc, k, a, b, rng, check_stats):
             assert sa[key] == sb[key], "%s frame %d: stat %s %d != %d" % (sc.name, k, key, sa[key], sb[key])
 
 
-def run_and_compare(sc, make_a, make_b, check_stats=True, verbose=False, production=False):
+def run_and_compare(sc, make_a, make_b, check_stats=True, verbose=False, production=False, before_frame=None, after_frame=None):
     """make_a: reference mapper factory (oracle); make_b: mapper under test. Raises on mismatch.
     Returns a list of per-frame stats dicts of the reference mapper.
     production=True drives both mappers with set_pose / ogm / step() only — the sequence a node runs — and compares
     what is left after the map update.  (The stage-by-stage form reads the scan and the batch EDT in between, and
     those readers complete what the update itself leaves out: scan labels of a ray-cast scan, pass Z of tiles nobody
-    reads.)"""
+    reads.)  before_frame(k, a, b), if given, runs ahead of frame k's set_pose (tests that set the frame counter: debug_set_frame),
+    after_frame(k, a, b) when frame k has been compared."""
     cfg = sc.config()
     a, b = make_a(cfg), make_b(cfg)
     rng = np.random.default_rng(sc.seed + 77)
     out = []
     try:
         if sc.ext_boxes:
-            set_ext_boxes(a, b)
+            set_ext_boxes(a, b, shift=sc.shift())
         for k, (pos, q, kind, data, kw) in enumerate(sc.frames_iter()):
+            if before_frame is not None:
+                before_frame(k, a, b)
             a.set_pose(pos, q)
             b.set_pose(pos, q)
             assert a.pivot() == b.pivot()
@@ -195,6 +213,8 @@ def run_and_compare(sc, make_a, make_b, check_stats=True, verbose=False, product
                 b.step()
                 _compare_after_merge(sc, k, a, b, rng, check_stats)
                 out.append(a.stats())
+                if after_frame is not None:
+                    after_frame(k, a, b)
                 continue
             oa, ob = a.read_ogm(), b.read_ogm()
             for key in ("inst_type", "ray_count"):
@@ -237,19 +257,21 @@ def run_and_compare(sc, make_a, make_b, check_stats=True, verbose=False, product
                                                          "visits_c", "levels_a", "levels_b", "levels_c")},
                       "known", int((ra["type"] != 0).sum()))
             out.append(sa)
+            if after_frame is not None:
+                after_frame(k, a, b)
     finally:
         a.close()
         b.close()
     return out
 
 
-def run_irregular(sc, make_a, make_b, fuse_only=(), stream_on=(), compare_margin=None):
+def run_irregular(sc, make_a, make_b, fuse_only=(), stream_on=(), compare_margin=None, before_frame=None, after_frame=None):
     """The staged ABI driven off the beaten path: map updates that stop after gie_fuse (`fuse_only`: frame numbers
     without batch EDT and merge -- a node that skips the EDT of a frame, or an update that failed half way) and updates that run
     with the changed-block flags on (`stream_on`: frame numbers; the mapper then uses the reference's order Mark ... commit instead
     of the fused sweep, so the run changes between the two forms).  After every COMPLETE update everything is compared as in
     run_and_compare, and what the two mappers deliver of a stream-on update; after a fuse-only update the fused types and the stored
-    occupancy."""
+    occupancy.  before_frame(k, a, b), after_frame(k, a, b): as in run_and_compare (after complete updates only)."""
     cfg = sc.config()
     a, b = make_a(cfg), make_b(cfg)
     rng = np.random.default_rng(sc.seed + 78)
@@ -257,6 +279,8 @@ def run_irregular(sc, make_a, make_b, fuse_only=(), stream_on=(), compare_margin
     try:
         for k, (pos, q, kind, data, kw) in enumerate(sc.frames_iter()):
             on = k in stream_on
+            if before_frame is not None:
+                before_frame(k, a, b)
             for m in (a, b):
                 m.stream_enable(on)
                 m.set_pose(pos, q)
@@ -278,6 +302,8 @@ def run_irregular(sc, make_a, make_b, fuse_only=(), stream_on=(), compare_margin
                 kb, bb, _ = b.stream_changed()
                 stream_mirror.check_oracle_equal("%s frame %d" % (sc.name, k), (kb, bb), (ka, ba))
             _compare_after_merge(sc, k, a, b, rng, True)
+            if after_frame is not None:
+                after_frame(k, a, b)
     finally:
         a.close()
         b.close()

@@ -31,7 +31,11 @@ SCENES = [
 ]
 
 
-def run_scene(sc, make_mapper):
+def run_scene(sc, make_mapper, before_frame=None, equal_seeds=True):
+    """before_frame(k, mapper, checker), if given, runs ahead of frame k's set_pose (tests that set the frame counter).
+    equal_seeds=False: for scenes dense enough that the two schedules leave different (witness) records right next to the volume.
+    Such a record is the neighbour of one face voxel, which the next update's obtainFrontiers may then sort into another wave's
+    seeds or none: each of the three counts may differ by one per stored record that differed when the update before ended."""
     cfg = sc.config()
     m = make_mapper(cfg)
     frames = list(sc.frames_iter())
@@ -50,6 +54,8 @@ def run_scene(sc, make_mapper):
     stats = {"voxels": 0, "inside_diff": 0, "outside_diff": 0, "outside_cmp": 0, "waves": [0, 0, 0]}
     try:
         for k, (pos, q, kind, data, kw) in enumerate(frames):
+            if before_frame is not None:
+                before_frame(k, m, chk)
             m.set_pose(pos, q)
             parity._feed(m, kind, data, kw)
             m.fuse()
@@ -62,8 +68,13 @@ def run_scene(sc, make_mapper):
             upvt = crd - wr // 2
             pd, seeds = chk.update(pvt, upvt, T, e["dist_sq"], e["coc"])
             st = m.stats()
-            assert seeds == (st["seeds_a"], st["seeds_b"], st["seeds_c"]), "%s frame %d: seeds %s vs %s" % (
-                sc.name, k, seeds, (st["seeds_a"], st["seeds_b"], st["seeds_c"]))
+            got = (st["seeds_a"], st["seeds_b"], st["seeds_c"])
+            if equal_seeds:
+                assert seeds == got, "%s frame %d: seeds %s vs %s" % (sc.name, k, seeds, got)
+            else:
+                assert max(abs(a - b) for a, b in zip(seeds, got)) <= stats.get("differing_records", 0), "%s frame %d: seeds %s vs %s with %d differing records" % (
+                    sc.name, k, seeds, got, stats.get("differing_records", 0))
+                stats["seed_diff"] = stats.get("seed_diff", 0) + sum(abs(a - b) for a, b in zip(seeds, got))
             for i, key in enumerate(("visits_a", "visits_b", "visits_c")):
                 stats["waves"][i] += st[key]
             r = m.read_local()
@@ -97,6 +108,7 @@ def run_scene(sc, make_mapper):
             diff = gv["dist_sq"].astype(np.int64) != chk.g_dist[zz, yy, xx]
             assert (diff & ~outside).sum() <= bad.sum(), "%s frame %d: stored distances inside the volume differ where the pairs do not" % (sc.name, k)
             stats["outside_cmp"] += int(outside.sum()); stats["outside_diff"] += int((diff & outside).sum())
+            stats["differing_records"] = int(diff.sum())                       # as this update leaves them
             od = diff & outside & valid
             if od.any():
                 dd = np.sqrt(gv["dist_sq"][od].astype(np.float64)) - np.sqrt(chk.g_dist[zz, yy, xx][od].astype(np.float64))
