@@ -15,7 +15,7 @@
 #include <unistd.h>
 static const char *const gie_kernel_names[GIE_K_NUM] = { "ogm_classify", "ray_register", "ray_free", "ray_finalize", "block_alloc", "fuse",
        "edt_pass_y", "edt_pass_x", "edt_pass_z", "mark", "frontiers", "wave_a", "wave_b", "waves", "commit", "edt_prep", "mark_commit",
-       "cloud", "los", "los_query", "sdf", "sdf_query" };
+       "ground", "ground_query", "cloud", "los", "los_query", "sdf", "sdf_query" };
 
 #define GIE_REHASH_PERIOD 64                 /* map updates between two rebuilds of the hash table while blocks are being erased */
 static thread_local std::string g_gie_err;
@@ -81,6 +81,17 @@ struct gie_los_cache {
     int valid = 0;                        /* a prepare has been enqueued */
     int pvt[3] = { 0, 0, 0 };             /* the pivot at that prepare */
 };
+/* the ground costmap (gie_ground.inc.h): allocated at its first compute through gie_dalloc, kept until the next compute */
+struct gie_ground_cache {
+    uint64_t *obs = nullptr;              /* the bit rows of obstacle columns */
+    int32_t *cells = nullptr;             /* three planes of X * Y: top, dist_sq, the closest column */
+    int8_t *type = nullptr;               /* the column types */
+    int32_t *cnt = nullptr;               /* the four counts */
+    int valid = 0;                        /* a compute has been enqueued */
+    int flags = 0, z_lo = 0;              /* of that compute */
+    int pvt[3] = { 0, 0, 0 };             /* the pivot and CostMap origin at that compute */
+    float origin[3] = { 0.f, 0.f, 0.f };
+};
 struct gie_mapper {
     gie_config cfg;
     gie_ctx c;
@@ -118,6 +129,7 @@ struct gie_mapper {
     gie_nf1_cache nf1;                    /* the navigation function (HIP backend: gie_nf1.inc.h) */
     gie_frontier_cache fr;                /* the frontier clusters (HIP backend: gie_frontier.inc.h) */
     gie_los_cache los;                    /* line of sight (HIP backend: gie_los.inc.h) */
+    gie_ground_cache ground;              /* the ground costmap (HIP backend: gie_ground.inc.h) */
     int32_t *cloud_count = nullptr;       /* display clouds (HIP backend: gie_cloud.inc.h): the counter of a _dev call that passes none, allocated at the first such call */
 };
 

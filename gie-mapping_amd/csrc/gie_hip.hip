@@ -593,3 +593,4 @@ static void be_waves(be_state *b, const gie_ctx &c, int with_ab, int record_seed
 #include "gie_los.inc.h"
 #include "gie_path.inc.h"
 #include "gie_cloud.inc.h"
+#include "gie_ground.inc.h"

@@ -122,6 +122,17 @@ class CloudPoint(C.Structure):
     _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("intensity", C.c_float)]
 
 
+class GroundParam(C.Structure):
+    """gie_ground_param (include/gie.h): 32 bytes."""
+    _fields_ = [("z_lo", C.c_int32), ("z_hi", C.c_int32), ("min_known", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class GroundCell(C.Structure):
+    """gie_ground_cell (include/gie.h): 16 bytes."""
+    _fields_ = [("dist_sq", C.c_int32), ("coc_x", C.c_int32), ("coc_y", C.c_int32), ("type", C.c_int8), ("inside", C.c_uint8), ("pad", C.c_uint8 * 2)]
+
+
+assert C.sizeof(GroundParam) == 32 and C.sizeof(GroundCell) == 16
 assert C.sizeof(CloudParam) == 32 and C.sizeof(CloudPoint) == 16
 assert C.sizeof(ShortcutParam) == 16 and C.sizeof(Waypoint) == 24 and C.sizeof(ShortcutInfo) == 16
 assert C.sizeof(LosHit) == 24 and C.sizeof(View) == 64 and C.sizeof(ViewScore) == 16 and C.sizeof(LosParam) == 16 and C.sizeof(ViewParam) == 16
@@ -131,6 +142,7 @@ NF1_FROM_FRONTIERS = 2
 LOS_UNKNOWN_OPAQUE = 1
 CLOUD_TYPE = 0
 CLOUD_DIST = 1
+GROUND_UNKNOWN_BLOCKS = 1
 VOX_UNKNOWN, VOX_FREE, VOX_OCCUPIED, VOX_FNT = 0, 1, 2, 3
 
 
@@ -262,6 +274,15 @@ DEVICE_ONLY = {
     "cloud_local_dev": (C.c_int, [_H, C.POINTER(CloudParam), C.c_void_p, C.c_void_p]),
     "cloud_global": (C.c_int, [_H, C.POINTER(CloudParam), C.c_void_p, C.c_void_p]),
     "cloud_global_dev": (C.c_int, [_H, C.POINTER(CloudParam), C.c_void_p, C.c_void_p]),
+    # ground costmap of a height band of the local volume (include/gie.h): device library only
+    "ground_compute": (C.c_int, [_H, C.POINTER(GroundParam), C.c_void_p]),
+    "ground_compute_dev": (C.c_int, [_H, C.POINTER(GroundParam), C.c_void_p]),
+    "read_ground": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "read_ground_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "read_costmap_ground": (C.c_int, [_H, C.c_void_p, C.POINTER(CostMapHdr)]),
+    "read_costmap_ground_dev": (C.c_int, [_H, C.c_void_p, C.POINTER(CostMapHdr)]),
+    "ground_query": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p]),
+    "ground_query_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p]),
 }
 DEVICE_ONLY.update(ROUND_API)
 

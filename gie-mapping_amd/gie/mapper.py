@@ -13,8 +13,8 @@ import sys
 import numpy as np
 
 from . import _capi
-from ._capi import CLOUD_DIST, CLOUD_TYPE, LOS_UNKNOWN_OPAQUE, NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE, VOX_FNT, VOX_FREE, VOX_OCCUPIED, VOX_UNKNOWN
-from ._capi import CamParam, CloudParam, Config, CostMapHdr, FrameStats, FrontierParam, LosParam, MultiScanParam, Nf1Param, ScanParam, ShortcutParam, ViewParam, Voxel
+from ._capi import CLOUD_DIST, CLOUD_TYPE, GROUND_UNKNOWN_BLOCKS, LOS_UNKNOWN_OPAQUE, NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE, VOX_FNT, VOX_FREE, VOX_OCCUPIED, VOX_UNKNOWN
+from ._capi import CamParam, CloudParam, Config, CostMapHdr, FrameStats, FrontierParam, GroundParam, LosParam, MultiScanParam, Nf1Param, ScanParam, ShortcutParam, ViewParam, Voxel
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG, "csrc", "libgie_hip.so")
@@ -35,6 +35,8 @@ SHORTCUT_INFO_DTYPE = np.dtype([("count", "<i4"), ("forced", "<i4"), ("length", 
 # gie_cloud_point (16 bytes)
 CLOUD_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("intensity", "<f4")])
 CLOUD_NO_BAND = (-2 ** 31, 2 ** 31 - 1)
+# gie_ground_cell (16 bytes)
+GROUND_CELL_DTYPE = np.dtype([("dist_sq", "<i4"), ("coc", "<i4", (2,)), ("type", "i1"), ("inside", "u1"), ("pad", "u1", (2,))])
 VOXEL_DTYPE = np.dtype([("occ_val", "u1"), ("vox_type", "i1"), ("pad", "<i2"), ("dist_sq", "<i4"),
                         ("coc", "<i4", (3,))])
 
@@ -751,3 +753,58 @@ class Mapper(MapperBase):
     def cloud_global_dev(self, d_out, d_count, type_mask, intensity=CLOUD_TYPE, z_lo=None, z_hi=None, max_points=0):
         p = self.cloud_param(type_mask, intensity, z_lo, z_hi, max_points)
         self._chk(self._f["cloud_global_dev"](self._h, C.byref(p), C.c_void_p(d_out or None), C.c_void_p(d_count or None)))
+
+    # --- ground costmap of a height band (include/gie.h) ---------------------------------------
+    def ground_param(self, z_lo, z_hi, min_known=1, unknown_blocks=False):
+        """gie_ground_param: z_lo / z_hi = GLOBAL voxel z, both inclusive."""
+        p = GroundParam()
+        p.z_lo, p.z_hi, p.min_known, p.flags = int(z_lo), int(z_hi), int(min_known), GROUND_UNKNOWN_BLOCKS if unknown_blocks else 0
+        return p
+
+    def ground_compute(self, z_lo, z_hi, min_known=1, unknown_blocks=False):
+        """The column types of the band and their 2-D distance transform; returns the counts [UNKNOWN, FREE, OCCUPIED, FNT] (synchronises)."""
+        p = self.ground_param(z_lo, z_hi, min_known, unknown_blocks)
+        counts = np.zeros(4, np.int32)
+        self._chk(self._f["ground_compute"](self._h, C.byref(p), _ptr(counts)))
+        return counts
+
+    def ground_compute_dev(self, z_lo, z_hi, min_known=1, unknown_blocks=False, d_counts=0):
+        """The same on the mapper's stream without a host wait; the counts (4 int32; 0 = not wanted) in a DEVICE buffer."""
+        p = self.ground_param(z_lo, z_hi, min_known, unknown_blocks)
+        self._chk(self._f["ground_compute_dev"](self._h, C.byref(p), C.c_void_p(d_counts or None)))
+
+    def read_ground(self):
+        """{"type": int8, "dist_sq": int32, "coc": int32 (.., 2) global x y, "top": int32 global z}, shaped [Y][X] (synchronises)."""
+        s = (self.size[1], self.size[0])
+        out = {"type": np.empty(s, np.int8), "dist_sq": np.empty(s, np.int32), "coc": np.empty(s + (2,), np.int32), "top": np.empty(s, np.int32)}
+        self._chk(self._f["read_ground"](self._h, _ptr(out["type"]), _ptr(out["dist_sq"]), _ptr(out["coc"]), _ptr(out["top"])))
+        return out
+
+    def read_ground_dev(self, d_type, d_dist_sq, d_coc_xy, d_top):
+        """The same planes into device buffers (raw device addresses, 0 = not wanted), asynchronous on the mapper's stream."""
+        self._chk(self._f["read_ground_dev"](self._h, C.c_void_p(d_type or None), C.c_void_p(d_dist_sq or None), C.c_void_p(d_coc_xy or None),
+                                             C.c_void_p(d_top or None)))
+
+    def read_costmap_ground(self):
+        """The one-layer TYPE_EDT CostMap of the ground field: (SeenDist payload [Y][X], header) (synchronises)."""
+        pay = np.empty((self.size[1], self.size[0]), SEENDIST_DTYPE)
+        hdr = CostMapHdr()
+        self._chk(self._f["read_costmap_ground"](self._h, _ptr(pay), C.byref(hdr)))
+        return pay, hdr
+
+    def read_costmap_ground_dev(self, dptr):
+        """That payload into a device buffer (raw address), asynchronous on the mapper's stream; returns the header."""
+        hdr = CostMapHdr()
+        self._chk(self._f["read_costmap_ground_dev"](self._h, C.c_void_p(dptr or None), C.byref(hdr)))
+        return hdr
+
+    def ground_query(self, xy):
+        """n points (n x 2 metres, world frame) -> their cells' records (GROUND_CELL_DTYPE) (synchronises)."""
+        xy = np.ascontiguousarray(np.asarray(xy, dtype=np.float32).reshape(-1, 2))
+        out = np.zeros(xy.shape[0], GROUND_CELL_DTYPE)
+        self._chk(self._f["ground_query"](self._h, _ptr(xy) if len(xy) else None, len(xy), _ptr(out) if len(xy) else None))
+        return out
+
+    def ground_query_dev(self, d_xy, n, d_out):
+        """n queries with points (n x 2 float32) and records (n x 16 bytes) in DEVICE buffers, on the mapper's stream."""
+        self._chk(self._f["ground_query_dev"](self._h, C.c_void_p(d_xy or None), int(n), C.c_void_p(d_out or None)))

@@ -50,6 +50,9 @@ struct Parameters {
     bool cpu_mirror = true;              /* no counterpart in the reference, which always mirrors: the global display flags switch the changed-block stream on and
                                           * visualize() reads the mirror.  false: the stream stays off (the map update runs its fused sweep) and visualize() takes the
                                           * global clouds from the device (gie_cloud_global); `mirror` stays empty */
+    float ground_min_height = 0.f, ground_max_height = -1.f;   /* no counterpart in the reference: the band of world z (metres) a ground robot's body occupies, for ground_costmap();
+                                                                 * "ground/min_height", "ground/max_height"; off while max < min (the default) */
+    int ground_min_known = 1;            /* "ground/min_known": gie_ground_param.min_known */
     bool profile_loc_rms = false, profile_glb_rms = false;
     std::string log_name = "GIE_log.csv";
     std::string data_case = "ugv_corridor";
@@ -106,6 +109,8 @@ struct Parameters {
         else if (k == "voxel_width") voxel_width = fl();
         else if (k == "local_size_x") local_size_x = fl(); else if (k == "local_size_y") local_size_y = fl(); else if (k == "local_size_z") local_size_z = fl();
         else if (k == "ogm/min_height") ogm_min_h = fl(); else if (k == "ogm/max_height") ogm_max_h = fl();
+        else if (k == "ground/min_height") ground_min_height = fl(); else if (k == "ground/max_height") ground_max_height = fl();
+        else if (k == "ground/min_known") ground_min_known = in();
         else if (k == "wave/fast_mode") fast_mode = b(); else if (k == "wave/cutoff_dist") cutoff_dist = fl();
         else if (k == "hash/bucket_max") max_bucket = in(); else if (k == "hash/block_max") max_block = in();
         else if (k == "gpu/wave_workgroups") wave_workgroups = in(); else if (k == "gpu/place_tries") place_tries = in();
@@ -518,6 +523,24 @@ public:
         scores.resize(views.size());
         chk(gie_view_gain(m_, views.data(), (int)views.size(), &vp, scores.data()));
     }
+
+    /* The 2-D CostMap a ground planner takes beside ugv_height (include/gie.h "ground costmap"): the columns of the band
+     * [ground_min_height, ground_max_height] of the map as it stands and their exact distance transform, as a one-layer TYPE_EDT
+     * map of X * Y elements.  Returns false, and leaves both arguments alone, while the band is not set. */
+    bool ground_costmap(std::vector<gie_seendist> &payload, gie_costmap_hdr &hdr)
+    {
+        if (param.ground_max_height < param.ground_min_height) return false;
+        const float w = cfg_.voxel_width;
+        gie_ground_param p = {};
+        p.z_lo = (int32_t)std::floor(param.ground_min_height / w + 0.5f);      /* gie_pos2coord, in fp32 */
+        p.z_hi = (int32_t)std::floor(param.ground_max_height / w + 0.5f);
+        p.min_known = param.ground_min_known;
+        chk(gie_ground_compute(m_, &p, ground_counts));
+        payload.resize((size_t)cfg_.local_size[0] * cfg_.local_size[1]);
+        chk(gie_read_costmap_ground(m_, payload.data(), &hdr));
+        return true;
+    }
+    int32_t ground_counts[4] = { 0, 0, 0, 0 };   /* columns of the last ground_costmap(): UNKNOWN, FREE, OCCUPIED, FNT */
 
     /* VOLMAPNODE::visualize without the publishers: the clouds the display flags ask for (the others come back empty), of the map as
      * it stands.  sensor_pos is the reference's argument: its z is replaced by vis_height before the slice's z is taken

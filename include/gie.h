@@ -623,6 +623,75 @@ int gie_cloud_local_dev(gie_mapper *h, const gie_cloud_param *p, gie_cloud_point
 int gie_cloud_global(gie_mapper *h, const gie_cloud_param *p, gie_cloud_point *out, int32_t *count);
 int gie_cloud_global_dev(gie_mapper *h, const gie_cloud_param *p, gie_cloud_point *d_out, int32_t *d_count);
 
+/* ---- ground costmap: the footprint of a height band of the local volume and its exact 2-D distance transform, for ground and
+ * planar robots (the reference's ugv_height set-ups: cfg/ugv_laser3D_params.yaml, cfg/scan2D_params.yaml).  A body that occupies a
+ * band of z needs a 2-D grid — which cells are blocked, how far each is from the nearest blocked one — and neither the 3-D EDT nor
+ * a z slice of it is that: the floor under the robot and a beam above it are obstacles one voxel away everywhere.  No counterpart
+ * in the reference's code.
+ *
+ * Everything is over the local volume at the point of the mapper's stream where gie_ground_compute* is enqueued: type(v) is what
+ * gie_read_local would return there, pvt what gie_get_pivot returns there.  The result is kept until the next compute and refers
+ * to that pivot (as NF1's field); map updates do not change it.  Every value is an integer and exact.
+ *  band          B = [max(z_lo, pvt_z), min(z_hi, pvt_z + Z - 1)] in GLOBAL z.  It may be empty: every column is then UNKNOWN.
+ *  type(x, y)    from the voxels (x, y, z) with z in B: GIE_VOX_OCCUPIED if any of them is OCCUPIED; otherwise GIE_VOX_UNKNOWN if
+ *                fewer than min_known of them are known (FREE, FNT or OCCUPIED); otherwise GIE_VOX_FNT if any of them is FNT;
+ *                otherwise GIE_VOX_FREE.
+ *  top(x, y)     the highest GLOBAL z in B at which the column is OCCUPIED, INT32_MIN for a column that is not OCCUPIED: a wall
+ *                and a low kerb differ here.
+ *  obstacle columns   the OCCUPIED columns; with GIE_GROUND_UNKNOWN_BLOCKS the UNKNOWN columns too.
+ *  dist_sq(x, y) the exact squared Euclidean distance in the X x Y plane, in voxels, to the nearest obstacle column: 0 on obstacle
+ *                columns, -1 when the rectangle holds no obstacle column.
+ *  coc(x, y)     GLOBAL x, y of an obstacle column at exactly that distance (which one of several equally near is unspecified; an
+ *                obstacle column is its own); GIE_EMPTY_VALUE each when there is none.
+ *  counts        four int32, the number of columns of each type in GIE_VOX_* order (UNKNOWN, FREE, OCCUPIED, FNT).
+ * CostMap (TYPE_EDT): hdr as gie_read_costmap fills it at the field's pivot, with z_size = 1 and z_origin = (float)z_lo * width (the
+ *  caller's z_lo, converted as gie_read_costmap converts the pivot); payload of X * Y elements: d = sqrtf((float)dist_sq) in voxel
+ *  units (sqrtf as in gie_read_sdf), (float)max_loc_dist_sq where dist_sq = -1 (gie_read_costmap's value for "no obstacle");
+ *  o = type != UNKNOWN; s and the padding 0.  A consumer of the reference's cost_map topic takes it as a one-layer map.
+ * Query at a point (metres, world frame): its cell is gie_pos2coord(p_k, w) - pvt_k for k = x, y (include/gie_math.h, the mapping
+ *  of NF1's goals).  Inside the rectangle the record is the cell's, with inside = 1; outside it, or for a point that is not finite,
+ *  dist_sq = -1, coc = GIE_EMPTY_VALUE, type = GIE_VOX_UNKNOWN, inside = 0.  n == 0 is valid.
+ * Arguments: the planes of gie_read_ground* hold X * Y values each, x fastest (coc_xy two per cell); any may be NULL, not all.
+ *  counts / d_counts may be NULL.  The host forms synchronise; the _dev forms take DEVICE buffers and are enqueued on the mapper's
+ *  stream (gie_get_stream) with no host wait and no read-back.
+ * GIE_ERR_INVALID, nothing written: a NULL handle or param; z_lo > z_hi; min_known < 1; an unknown flag bit or non-zero reserved;
+ *  a compute before the first gie_set_pose; a tiled mapper (all eight refuse, as every planner section does); gie_read_ground*,
+ *  gie_read_costmap_ground* or gie_ground_query* before the first compute; all four outputs of gie_read_ground* NULL; a NULL
+ *  payload in gie_read_costmap_ground_dev; n < 0, or n > 0 with a NULL xy or out.
+ * Memory: a mapper that never calls the section allocates and launches nothing.  The first compute allocates per CELL (x, y), not
+ *  per voxel (gie_dalloc, freed by gie_destroy): dist_sq, top and the closest column (4 bytes each; the column as local x | y << 16),
+ *  the type (1 byte), one bit row of obstacle columns per y padded to 64-bit words (8 * ceil(X/64) / X bytes per cell) and four
+ *  counters: 13.125 bytes per cell when X is a multiple of 64, 3.4 MB for 512 x 512.  Whether a column is known or FNT is in its
+ *  type byte, which every reader wants per cell; pass X's result is recomputed from the bit row where pass Y needs it.
+ * Cost: a compute is one memset of the counters and two launches, without a grid barrier (it does not join the chain of
+ *  grid-barrier launches).  The projection reads the type plane once over the band, 1 byte per voxel of X x Y x |B|, and nothing
+ *  else of the map; the transform reads the bit rows and writes 8 bytes per cell.  With no obstacle column the transform returns at
+ *  once on a device-side count and the readers write -1.
+ * gie_profile_read: "ground" = compute and the exports, "ground_query" = the queries (the two entries before "cloud": a section's
+ *  entries go in front of those of the sections before it; the map update's keep their indices). */
+#define GIE_GROUND_UNKNOWN_BLOCKS 1      /* UNKNOWN columns are obstacles of the distance transform too */
+typedef struct gie_ground_param {        /* 32 bytes */
+    int32_t z_lo, z_hi;     /* GLOBAL voxel z, both inclusive (gie_cloud_param's convention); z_lo <= z_hi */
+    int32_t min_known;      /* >= 1: a column with fewer known voxels inside the band is UNKNOWN */
+    int32_t flags;          /* GIE_GROUND_* */
+    int32_t reserved[4];    /* 0 */
+} gie_ground_param;
+typedef struct gie_ground_cell {         /* 16 bytes */
+    int32_t dist_sq;
+    int32_t coc_x, coc_y;   /* GLOBAL voxel x, y of a closest obstacle column; GIE_EMPTY_VALUE each when there is none */
+    int8_t  type;           /* column type */
+    uint8_t inside;         /* gie_ground_query only: the point lies inside the field's X x Y rectangle */
+    uint8_t pad[2];         /* 0 */
+} gie_ground_cell;
+int gie_ground_compute(gie_mapper *h, const gie_ground_param *p, int32_t counts[4]);
+int gie_ground_compute_dev(gie_mapper *h, const gie_ground_param *p, int32_t *d_counts);
+int gie_read_ground(gie_mapper *h, int8_t *type, int32_t *dist_sq, int32_t *coc_xy, int32_t *top);
+int gie_read_ground_dev(gie_mapper *h, int8_t *d_type, int32_t *d_dist_sq, int32_t *d_coc_xy, int32_t *d_top);
+int gie_read_costmap_ground(gie_mapper *h, gie_seendist *payload, gie_costmap_hdr *hdr);
+int gie_read_costmap_ground_dev(gie_mapper *h, gie_seendist *d_payload, gie_costmap_hdr *hdr);
+int gie_ground_query(gie_mapper *h, const float *xy, int n, gie_ground_cell *out);
+int gie_ground_query_dev(gie_mapper *h, const float *d_xy, int n, gie_ground_cell *d_out);
+
 /* ---- changed-block streaming: the CPU mirror the reference keeps for RViz and CPU planners.
  * GlbHashMap::streamPipeline / streamD2H / getUpdatedAddr (glb_hash_map.cu:209-247,
  * unify_helper.cuh:11-32), fed by the stream_VB_keys_D appends of the fuse / wave / commit kernels
