@@ -92,6 +92,12 @@ struct gie_ground_cache {
     int pvt[3] = { 0, 0, 0 };             /* the pivot and CostMap origin at that compute */
     float origin[3] = { 0.f, 0.f, 0.f };
 };
+/* the goal-to-goal cost matrix (gie_costmat.inc.h): scratch only, allocated at the first compute through gie_dalloc; no result is kept */
+struct gie_costmat_cache {
+    uint64_t *masks = nullptr;            /* two planes of one 64-bit mask per voxel */
+    uint64_t *trav = nullptr;             /* the traversable bit plane */
+    int32_t *words = nullptr;             /* control words, tile stamps, two tile lists */
+};
 struct gie_mapper {
     gie_config cfg;
     gie_ctx c;
@@ -130,6 +136,7 @@ struct gie_mapper {
     gie_frontier_cache fr;                /* the frontier clusters (HIP backend: gie_frontier.inc.h) */
     gie_los_cache los;                    /* line of sight (HIP backend: gie_los.inc.h) */
     gie_ground_cache ground;              /* the ground costmap (HIP backend: gie_ground.inc.h) */
+    gie_costmat_cache costmat;            /* the cost matrix's scratch (HIP backend: gie_costmat.inc.h) */
     int32_t *cloud_count = nullptr;       /* display clouds (HIP backend: gie_cloud.inc.h): the counter of a _dev call that passes none, allocated at the first such call */
 };
 
@@ -952,7 +959,7 @@ static int gie_fetch_counters(gie_mapper *m)
                          m->h_cnt[GIE_CNT_TL_FRONT], m->h_cnt[GIE_CNT_TL_FUSE], m->h_cnt[GIE_CNT_SEED_A], m->h_cnt[GIE_CNT_SEED_B], m->h_cnt[GIE_CNT_SEED_C], m->h_cnt[GIE_CNT_TSKIP],
                          m->h_cnt[GIE_CNT_STATE1], m->h_cnt[GIE_CNT_STATE2], m->h_cnt[GIE_CNT_ZSTREAM], m->h_cnt[GIE_CNT_ZWIDE], m->h_cnt[GIE_CNT_ZFAIL]);
     }
-    if (e & ~(GIE_ERRF_BARRIER | GIE_ERRF_NF1_BARRIER)) {
+    if (e & ~(GIE_ERRF_BARRIER | GIE_ERRF_NF1_BARRIER | GIE_ERRF_COSTMAT_BARRIER)) {
         std::string s = "device capacity exceeded:";
         if (e & GIE_ERRF_POOL) s += " block pool (raise gie_config.max_blocks)";
         if (e & GIE_ERRF_QUEUE) s += " frontier queue";
@@ -960,7 +967,7 @@ static int gie_fetch_counters(gie_mapper *m)
         gie_set_err(s);
         return GIE_ERR_CAPACITY;
     }
-    if (e & (GIE_ERRF_BARRIER | GIE_ERRF_NF1_BARRIER)) {
+    if (e & (GIE_ERRF_BARRIER | GIE_ERRF_NF1_BARRIER | GIE_ERRF_COSTMAT_BARRIER)) {
         /* not sticky: reported once, then cleared (the per-frame clear leaves the error word alone) */
         be_memset(&m->be, &m->c.cnt[GIE_CNT_ERR], 0, sizeof(int32_t));
         be_sync(&m->be);
@@ -971,6 +978,9 @@ static int gie_fetch_counters(gie_mapper *m)
         if (e & GIE_ERRF_NF1_BARRIER)
             s += std::string(s.empty() ? "" : "; ") + "grid barrier of the navigation function's propagation timed out (its workgroups were not "
                  "all resident: another process is holding the device); the NF1 field is incomplete until the next gie_nf1_compute, the map is not affected";
+        if (e & GIE_ERRF_COSTMAT_BARRIER)
+            s += std::string(s.empty() ? "" : "; ") + "grid barrier of the cost matrix's propagation timed out (its workgroups were not all "
+                 "resident: another process is holding the device); the matrix of that gie_costmat_compute is incomplete, the map is not affected";
         gie_set_err(s);
         return GIE_ERR_TIMEOUT;
     }

@@ -559,7 +559,7 @@ static void be_edt(be_state *b, const gie_ctx &c, int full)
  * different mappers on the same device at the same time need not be.  Waves launches of one
  * device are therefore chained through an event: a launch waits for the previous one, whichever
  * mapper (stream) it came from. */
-/* every grid-barrier launch of the library joins that chain (the waves; the navigation function's propagation, gie_nf1.inc.h):
+/* every grid-barrier launch of the library joins that chain (the waves; the navigation function's propagation, gie_nf1.inc.h; the cost matrix's, gie_costmat.inc.h):
  * `enqueue` puts the chained work on b->stream */
 template <class F> static void be_chained(be_state *b, const F &enqueue)
 {
@@ -589,6 +589,7 @@ static void be_waves(be_state *b, const gie_ctx &c, int with_ab, int record_seed
 #include "gie_api.inc.h"
 #include "gie_sdf.inc.h"
 #include "gie_nf1.inc.h"
+#include "gie_costmat.inc.h"
 #include "gie_frontier.inc.h"
 #include "gie_los.inc.h"
 #include "gie_path.inc.h"

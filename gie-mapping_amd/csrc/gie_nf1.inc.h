@@ -32,6 +32,13 @@ struct gie_nf1_dev {
     int W, TY, TZ, ntiles;
 };
 
+/* traversable(v) of include/gie.h for the voxel `id` of type ty (shared with the cost matrix, gie_costmat.inc.h) */
+GIE_DEV bool gie_nf1_traversable(const gie_ctx &c, const int id, const int8_t ty, const float clearance, const int flags)
+{
+    const bool open = ty == GIE_VOX_FREE || ty == GIE_VOX_FNT || (ty == GIE_VOX_UNKNOWN && (flags & GIE_NF1_UNKNOWN_TRAVERSABLE));
+    return open && gie_edt_value(c, id) >= clearance;
+}
+
 /* prep (a): one lane per voxel, a wave per 64-voxel word: the bit planes, the field at -1 and the FNT sources at 0 */
 __global__ __launch_bounds__(256) void k_nf1_prep(const gie_ctx c, const gie_nf1_dev s, const int nwords, const float clearance, const int flags)
 {
@@ -43,8 +50,7 @@ __global__ __launch_bounds__(256) void k_nf1_prep(const gie_ctx c, const gie_nf1
         const int id = row * c.X + x;
         const int8_t ty = c.glb_type[id];
         kn = ty != GIE_VOX_UNKNOWN;
-        const bool open = ty == GIE_VOX_FREE || ty == GIE_VOX_FNT || (ty == GIE_VOX_UNKNOWN && (flags & GIE_NF1_UNKNOWN_TRAVERSABLE));
-        tr = open && gie_edt_value(c, id) >= clearance;
+        tr = gie_nf1_traversable(c, id, ty, clearance, flags);
         src = tr && ty == GIE_VOX_FNT && (flags & GIE_NF1_FROM_FRONTIERS);
         s.f[id] = src ? 0 : -1;
     }
@@ -128,8 +134,9 @@ __global__ __launch_bounds__(256) void k_nf1_seed(const gie_ctx c, const gie_nf1
 /* the grid barrier of k_nf1_bfs: gie_grid_sync's protocol (every shared word is read and written with agent-scope accesses), but
  * a timeout sets only its own bit of the error word (GIE_ERRF_NF1_BARRIER, reported as GIE_ERR_TIMEOUT by the next sync): the map
  * update's barrier-failure word is left alone.  The arrival count wraps (one round per BFS level: a winding 512^3 field has tens of
- * millions): it is compared by the sign of the 32-bit difference, exact while fewer than 2^31 arrivals separate count and target. */
-GIE_DEV bool gie_nf1_sync(const gie_ctx &c, int32_t *word, uint32_t &epoch, int *s_fail)
+ * millions): it is compared by the sign of the 32-bit difference, exact while fewer than 2^31 arrivals separate count and target.
+ * errf: the caller's bit (the cost matrix's propagation, gie_costmat.inc.h, has its own). */
+GIE_DEV bool gie_nf1_sync(const gie_ctx &c, int32_t *word, uint32_t &epoch, int *s_fail, const int errf = GIE_ERRF_NF1_BARRIER)
 {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -140,7 +147,7 @@ GIE_DEV bool gie_nf1_sync(const gie_ctx &c, int32_t *word, uint32_t &epoch, int 
         int spins = 0;
         while ((int32_t)((uint32_t)__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) < 0) {
             __builtin_amdgcn_s_sleep(2);
-            if (++spins > GIE_BAR_SPIN_LIMIT) { gie_aor32(&c.cnt[GIE_CNT_ERR], GIE_ERRF_NF1_BARRIER); *s_fail = 1; break; }
+            if (++spins > GIE_BAR_SPIN_LIMIT) { gie_aor32(&c.cnt[GIE_CNT_ERR], errf); *s_fail = 1; break; }
         }
     }
     __syncthreads();

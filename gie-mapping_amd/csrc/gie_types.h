@@ -238,6 +238,7 @@ enum { GIE_K_CLASSIFY = 0, GIE_K_RAY_REGISTER, GIE_K_RAY_FREE, GIE_K_RAY_FINAL, 
 #define GIE_ERRF_HASH 4
 #define GIE_ERRF_BARRIER 8
 #define GIE_ERRF_NF1_BARRIER 16    /* a grid barrier of the navigation function's propagation timed out (gie_nf1.inc.h): the field is incomplete, the map is not */
+#define GIE_ERRF_COSTMAT_BARRIER 32   /* the same of the cost matrix's propagation (gie_costmat.inc.h): the matrix is incomplete, the map is not */
 
 /* regions zeroed by one launch at the start of a map update */
 #define GIE_CLEAR_MAX 16

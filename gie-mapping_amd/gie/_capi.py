@@ -283,6 +283,9 @@ DEVICE_ONLY = {
     "read_costmap_ground_dev": (C.c_int, [_H, C.c_void_p, C.POINTER(CostMapHdr)]),
     "ground_query": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p]),
     "ground_query_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p]),
+    # goal-to-goal cost matrix of the local volume (include/gie.h): device library only
+    "costmat_compute": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(Nf1Param), C.c_void_p, C.c_void_p]),
+    "costmat_compute_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(Nf1Param), C.c_void_p, C.c_void_p]),
 }
 DEVICE_ONLY.update(ROUND_API)
 

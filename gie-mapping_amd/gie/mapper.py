@@ -529,6 +529,26 @@ class Mapper(MapperBase):
         self._chk(self._f["read_costmap_nf1_dev"](self._h, C.c_void_p(dptr or None), C.byref(hdr)))
         return hdr
 
+    # --- goal-to-goal cost matrix of the local volume (include/gie.h) ------------------------
+    def costmat(self, points, clearance=0.0, unknown_traversable=False):
+        """Path lengths among n <= 64 points (n x 3 metres, world frame), clearance in METRES (as nf1_param):
+        (cost [n, n] int32, valid [n] bool) (synchronises)."""
+        xyz = np.ascontiguousarray(np.asarray(points, dtype=np.float32).reshape(-1, 3))
+        n = xyz.shape[0]
+        p = self.nf1_param(clearance, unknown_traversable)
+        cost = np.empty((n, n), np.int32)
+        valid = np.zeros(n, np.uint8)
+        self._chk(self._f["costmat_compute"](self._h, _ptr(xyz) if n else None, n, C.byref(p), _ptr(cost) if n else None,
+                                             _ptr(valid) if n else None))
+        return cost, valid.astype(bool)
+
+    def costmat_dev(self, d_points, n, d_cost, d_valid=0, clearance=0.0, unknown_traversable=False):
+        """The same with points (n x 3 float32), the matrix (n x n int32) and valid (n uint8; 0 = not wanted) in DEVICE buffers,
+        on the mapper's stream; the host does not wait."""
+        p = self.nf1_param(clearance, unknown_traversable)
+        self._chk(self._f["costmat_compute_dev"](self._h, C.c_void_p(d_points or None), int(n), C.byref(p), C.c_void_p(d_cost or None),
+                                                 C.c_void_p(d_valid or None)))
+
     # --- frontier clusters of the local volume (include/gie.h) ------------------------------
     def frontier_param(self, clearance=0.0, min_size=1, connectivity=26, max_clusters=256):
         """gie_frontier_param for a clearance in METRES: float32(clearance) / float32(voxel_width) voxels (as nf1_param)."""

@@ -38,6 +38,16 @@
 
 #include "../../include/gie.h"
 
+/* exploration_costs chains device-side calls and needs a device buffer of its own: it exists where this header is compiled with the
+ * HIP runtime's headers at hand (hipcc, or any compiler with -DGIE_HOST_WITH_HIP and the include path); the rest needs none */
+#if defined(__HIPCC__) || defined(__HIP_PLATFORM_AMD__) || defined(GIE_HOST_WITH_HIP)
+#ifndef __HIP_PLATFORM_AMD__
+#define __HIP_PLATFORM_AMD__ 1
+#endif
+#include <hip/hip_runtime_api.h>
+#define GIE_HOST_HAS_HIP 1
+#endif
+
 namespace gie_host {
 
 struct Vec3 { float x, y, z; };
@@ -383,7 +393,13 @@ public:
             cost_map.payload8.resize((size_t)cfg_.local_size[0] * cfg_.local_size[1] * cfg_.local_size[2]);
         }
     }
-    ~VolumetricMapper() { if (m_) gie_destroy(m_); }
+    ~VolumetricMapper()
+    {
+#ifdef GIE_HOST_HAS_HIP
+        if (explore_dev_) (void)hipFree(explore_dev_);
+#endif
+        if (m_) gie_destroy(m_);
+    }
     VolumetricMapper(const VolumetricMapper &) = delete;
     VolumetricMapper &operator=(const VolumetricMapper &) = delete;
 
@@ -401,6 +417,7 @@ public:
         if (param.ugv_height > 0) pose.pos[2] = param.ugv_height;
         auto t0 = clk::now();
         chk(gie_set_pose(m_, pose.pos, pose.quat_wxyz));
+        for (int i = 0; i < 3; i++) robot_pos_[i] = pose.pos[i];
         switch (f.kind) {
         case DEPTH: chk(gie_ogm_depth(m_, f.data, &f.cam)); break;
         case SCAN2D: chk(gie_ogm_scan2d(m_, f.data, &f.scan)); break;
@@ -495,6 +512,49 @@ public:
         labels.resize((size_t)cfg_.local_size[0] * cfg_.local_size[1] * cfg_.local_size[2]);
         chk(gie_read_frontier_labels(m_, labels.data()));
     }
+
+#ifdef GIE_HOST_HAS_HIP
+    /* What a tour planner needs to order the frontier clusters (include/gie.h "cost matrix"): the path lengths, in voxel steps
+     * through space with clearance_m of free room, among the robot (point 0: the position of the last publishMap) and the goals of
+     * at most max_clusters (<= 63) frontier clusters of at least min_size voxels (connectivity 26).  Three device-side calls
+     * chained on the mapper's stream — the clusters, their goals into one buffer behind the robot's position, the matrix of that
+     * buffer — and ONE copy back; the host learns no count in between.
+     *   goals  3 * (max_clusters + 1) floats, metres: the robot, then the goals in ascending label order, NaN beyond the clusters;
+     *   cost   (max_clusters + 1)^2, row-major: -1 for a NaN entry, a goal the robot cannot reach, or a robot outside free space.
+     * Returns the number of kept clusters (which may exceed max_clusters). */
+    int exploration_costs(int max_clusters, float clearance_m, int min_size, std::vector<int32_t> &cost, std::vector<float> &goals)
+    {
+        if (max_clusters < 0 || max_clusters + 1 > GIE_COSTMAT_MAX_POINTS) throw std::invalid_argument("exploration_costs: 0 <= max_clusters <= 63");
+        const size_t n = (size_t)max_clusters + 1, off_cost = n * 12, off_counts = off_cost + n * n * 4, bytes = off_counts + 8;
+        if (bytes > explore_cap_) {
+            if (explore_dev_) (void)hipFree(explore_dev_);
+            explore_dev_ = nullptr; explore_cap_ = 0;
+            if (hipMalloc(&explore_dev_, bytes) != hipSuccess) throw std::runtime_error("exploration_costs: device allocation failed");
+            explore_cap_ = bytes;
+        }
+        void *stream = nullptr;
+        chk(gie_get_stream(m_, &stream));
+        char *d = static_cast<char *>(explore_dev_);
+        explore_host_.resize(bytes);
+        if (hipMemcpyAsync(d, robot_pos_, 12, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess) throw std::runtime_error("exploration_costs: copy failed");
+        gie_frontier_param fp = {};
+        fp.clearance = clearance_m / cfg_.voxel_width;
+        fp.min_size = min_size; fp.connectivity = 26; fp.max_clusters = max_clusters;
+        chk(gie_frontier_compute_dev(m_, &fp, reinterpret_cast<int32_t *>(d + off_counts)));
+        if (max_clusters > 0) chk(gie_read_frontier_clusters_dev(m_, nullptr, reinterpret_cast<float *>(d) + 3, nullptr));
+        gie_nf1_param np = {};
+        np.clearance = fp.clearance;
+        chk(gie_costmat_compute_dev(m_, reinterpret_cast<const float *>(d), (int)n, &np, reinterpret_cast<int32_t *>(d + off_cost), nullptr));
+        if (hipMemcpyAsync(explore_host_.data(), d, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess) throw std::runtime_error("exploration_costs: copy failed");
+        chk(gie_sync(m_));
+        goals.resize(3 * n); cost.resize(n * n);
+        std::memcpy(goals.data(), explore_host_.data(), off_cost);
+        std::memcpy(cost.data(), explore_host_.data() + off_cost, n * n * 4);
+        int32_t counts[2];
+        std::memcpy(counts, explore_host_.data() + off_counts, 8);
+        return counts[0];
+    }
+#endif
 
     /* line of sight (include/gie.h gie_los_prepare): the opaque plane of the current map — OCCUPIED, UNKNOWN too with
      * GIE_LOS_UNKNOWN_OPAQUE, and everything closer than clearance_m to an obstacle; returns the number of opaque voxels.
@@ -603,6 +663,9 @@ private:
     }
     gie_config cfg_;
     gie_mapper *m_ = nullptr;
+    float robot_pos_[3] = { 0.f, 0.f, 0.f };      /* of the last publishMap (after ugv_height) */
+    void *explore_dev_ = nullptr; size_t explore_cap_ = 0;     /* exploration_costs' device buffer and its host copy */
+    std::vector<char> explore_host_;
     bool streaming_ = false;
 };
 

@@ -692,6 +692,46 @@ int gie_read_costmap_ground_dev(gie_mapper *h, gie_seendist *d_payload, gie_cost
 int gie_ground_query(gie_mapper *h, const float *xy, int n, gie_ground_cell *out);
 int gie_ground_query_dev(gie_mapper *h, const float *d_xy, int n, gie_ground_cell *d_out);
 
+/* ---- goal-to-goal cost matrix: the path lengths among up to 64 points (the robot and the goals of the frontier clusters, say), the
+ * input of every tour-based explorer — in which order to visit the clusters.  n fields of gie_nf1_compute would give the same
+ * numbers with n persistent launches and n whole fields; here ONE level-synchronous pass advances all searches, a 64-bit mask per
+ * voxel.  No counterpart in the reference's code.
+ *
+ * Everything is over the local volume at the point of the mapper's stream where gie_costmat_compute* is enqueued; type(v) and
+ * edt(v) are exactly what gie_read_local would return there.
+ *  traversable(v)  NF1's rule: type(v) is FREE or FNT (or UNKNOWN, with GIE_NF1_UNKNOWN_TRAVERSABLE) and edt(v) >= clearance (a
+ *                  float comparison; clearance in voxel units).  GIE_NF1_FROM_FRONTIERS has no meaning here: GIE_ERR_INVALID.
+ *  voxel(i)        of point i (metres, world frame), as NF1's goals: gie_pos2coord(p_k, w) - pvt_k.  The point is VALID when it is
+ *                  finite, inside the volume and its voxel traversable.  valid[i] = 1 or 0 (valid may be NULL).
+ *  cost            n x n int32, row-major.  cost[i][j] = the number of steps of the shortest 6-connected path from voxel(i) to
+ *                  voxel(j) whose every voxel is traversable and inside the volume; 0 when the voxels coincide (i = j included);
+ *                  -1 when either point is invalid or there is no such path.  The matrix is symmetric, the rows of invalid points
+ *                  are all -1, two points on one voxel have identical rows.  By definition cost[i][j] is the value at voxel(i) of
+ *                  the field gie_nf1_compute gives for the single goal j with the same clearance and flags.
+ * Arguments: 0 <= n <= GIE_COSTMAT_MAX_POINTS, otherwise GIE_ERR_INVALID; n == 0 is valid and writes nothing.  A NULL p, a NULL
+ *  xyz or cost with n > 0, a clearance that is negative or not finite, an unknown flag and a tiled mapper (as NF1: the searches
+ *  would stop at the tile's faces) get GIE_ERR_INVALID.
+ * The host form synchronises.  The _dev form takes DEVICE buffers and is enqueued on the mapper's stream without a host wait; the
+ *  host needs neither the number of valid points nor the number of levels.  The goal array gie_read_frontier_clusters_dev writes
+ *  (NaN in its unused entries) can stand behind a robot position in one buffer and be handed over as it is: max_clusters + 1
+ *  points, the NaN ones invalid.
+ * The result is complete when the call's work is done; nothing is kept for later readers.
+ * Propagation: one persistent launch of gie_config.wave_workgroups workgroups with a grid barrier per BFS level, as NF1's, and
+ *  like it a member of the device's chain of grid-barrier launches.  Level k computes seen_{k+1}(v) = seen_k(v) | the seen_k of
+ *  the six neighbours from level k's masks only, on the tiles (64 x 8 x 8 voxels) in which something changed in level k - 1 and
+ *  their face neighbours.  It ends when a level changes nothing, or earlier once every valid point's voxel holds the mask of all
+ *  valid points; the matrix is the same either way.  The number of levels is the largest finite distance from a valid point to any
+ *  voxel it reaches (with the early end: the largest entry of the matrix, when all valid points are connected).
+ * If a grid barrier times out (the workgroups were kept off the device by another process), the next sync reports
+ *  GIE_ERR_TIMEOUT through the error word the map update uses, with a message that says the matrix is incomplete (entries -1 that
+ *  should be finite); the map itself is not affected.
+ * Memory: scratch allocated at the first call (gie_dalloc, freed by gie_destroy): two planes of one 64-bit mask per voxel (16 bytes
+ *  per voxel), one bit plane with rows padded to 64-bit words (0.125 bytes per voxel when X is a multiple of 64) and 12 bytes per
+ *  tile of 64 x 8 x 8 voxels: 16.13 bytes per voxel in all, 2.2 GB at 512^3.  NF1's field and the map update do not read it. */
+#define GIE_COSTMAT_MAX_POINTS 64
+int gie_costmat_compute(gie_mapper *h, const float *xyz, int n, const gie_nf1_param *p, int32_t *cost, uint8_t *valid);
+int gie_costmat_compute_dev(gie_mapper *h, const float *d_xyz, int n, const gie_nf1_param *p, int32_t *d_cost, uint8_t *d_valid);
+
 /* ---- changed-block streaming: the CPU mirror the reference keeps for RViz and CPU planners.
  * GlbHashMap::streamPipeline / streamD2H / getUpdatedAddr (glb_hash_map.cu:209-247,
  * unify_helper.cuh:11-32), fed by the stream_VB_keys_D appends of the fuse / wave / commit kernels
