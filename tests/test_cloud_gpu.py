@@ -2,7 +2,6 @@
 over Mapper.read_local / Mapper.query_global.  Every comparison is exact: two clouds are sorted by the bit patterns of their four
 words and must be byte-equal."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
@@ -11,10 +10,9 @@ import pytest
 import cloud_ref as R
 import gie
 from gie import _capi, scenes
-from los_common import BoxDrive, mapper, probe, scene, update
+from stage_common import BoxDrive, build_host_probe, lidar_frames, mapper, scene, stage_calls_change_nothing, update
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID = 1                                                     # GIE_ERR_INVALID
 FNT_T = R.param(1 << R.FNT, R.TYPE)
 SIX = {"ogm": R.param(1 << R.OCCUPIED, R.TYPE), "edt": R.param(R.KNOWN, R.DIST), "fnt": FNT_T,
@@ -402,28 +400,13 @@ def _all_four(m, slice_z):
 def test_cloud_calls_change_nothing_of_the_map_update():
     size = (48, 40, 33)
     d = BoxDrive(size, seed=5)
-    a, b = mapper(size), mapper(size)
-    try:
-        for k in range(10):
-            pos, q, lab = d.frame(k)
-            for m in (a, b):
-                m.set_pose(pos, q)
-                m.ogm_labels(lab)
-                m.fuse()
-                if m is a:
-                    _all_four(a, 2)                              # between fuse and merge
-                m.batch_edt()
-                m.merge()
-                if m is a:
-                    _all_four(a, -3)
-            la, lb = a.read_local(), b.read_local()
-            for key in la:
-                assert np.array_equal(la[key], lb[key]), (k, key)
-            assert a.stats() == b.stats()
-            assert np.array_equal(probe(a, size, np.random.default_rng(k)), probe(b, size, np.random.default_rng(k)))
-    finally:
-        a.close()
-        b.close()
+
+    def calls(a, k, phase, pos):
+        if phase == "fuse":
+            _all_four(a, 2)                                      # between fuse and merge
+        elif phase == "merge":
+            _all_four(a, -3)
+    stage_calls_change_nothing(size, (d.frame(k) for k in range(10)), mapper, calls)
 
 
 # ---------------------------------------------------------------------------------------------------------- 9. profile
@@ -449,21 +432,9 @@ def test_profile_counts_the_calls():
 
 # ---------------------------------------------------------------------------------------------------------- 10. host layer
 def test_host_layer_visualize_matches_the_mapper(tmp_path):
-    import __graft_entry__ as ge
-    ge.build_hip()
-    exe = str(tmp_path / "cloud_host_probe")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", os.path.join(ROOT, "tests", "gpu_helpers", "cloud_host_probe.cpp"), "-o", exe,
-                           "-L" + ge.CSRC, "-lgie_hip", "-Wl,-rpath," + ge.CSRC])
+    exe = build_host_probe(tmp_path, "cloud_host_probe")
     size, w, cutoff, vis_height = (48, 40, 33), 0.1, 3.0, -0.3
-    world = scenes.BoxWorld(4, extent=(2.5, 2.5, 1.0), n_boxes=30)
-    frames, words = [], [np.float32(4)]
-    for k in range(4):
-        pos, q = scenes.pose(k, w, delta_vox=3, yaw_deg=5.0)
-        pts, _ = scenes.lidar_frame(world, k, pos, q, az=360, max_range=6.0)
-        frames.append((pos, q, pts))
-        words += [np.array(list(pos) + list(q) + [len(pts)], np.float32), pts.ravel()]
-    fpath = str(tmp_path / "frames.f32")
-    np.concatenate([np.atleast_1d(x) for x in words]).astype(np.float32).tofile(fpath)
+    frames, fpath = lidar_frames(tmp_path)
     m = mapper(size, voxel=w, cutoff_dist=cutoff)
     try:
         for pos, q, pts in frames:

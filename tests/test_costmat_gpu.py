@@ -7,32 +7,11 @@ import numpy as np
 import pytest
 
 import costmat_ref
-import gie
 import nf1_ref
 from gie import scenes
+from stage_common import W, box_labels, mapper as _mapper, serpentine_labels, stage_calls_change_nothing, update as _update, world as _world
 
 pytestmark = pytest.mark.gpu
-
-W = 0.1
-
-
-def _mapper(size, voxel=W, **kw):
-    kw.setdefault("cutoff_dist", 3.0)
-    return gie.Mapper(gie.make_config(voxel, size, fast_mode=False, **kw))
-
-
-def _update(m, pos, q, labels):
-    m.set_pose(pos, q)
-    m.ogm_labels(labels)
-    m.step()
-
-
-def _world(m, local_xyz, jitter=None):
-    """world points (metres) of local voxels [n, 3] (x, y, z) at the mapper's pivot"""
-    v = (np.asarray(local_xyz, np.float64).reshape(-1, 3) + np.array(m.pivot())).astype(np.float32)
-    if jitter is not None:
-        v = v + jitter.astype(np.float32)
-    return (v * np.float32(m.cfg.voxel_width)).astype(np.float32)
 
 
 def _reference(m, loc, pts, clearance=0.0, unknown=False):
@@ -199,29 +178,6 @@ def test_n_at_its_limits(small):
 
 
 # ---- 3. serpentine maze -----------------------------------------------------------------------------------------------------------
-def _serpentine(size, pitch=2):
-    """labels of a walled volume with ONE corridor of free voxels snaking along x, rows `pitch` apart in y, layers in z; the
-    corridor's voxels in order"""
-    X, Y, Z = size
-    lab = np.full((Z, Y, X), 2, np.int8)
-    ys, zs = list(range(1, Y - 1, pitch)), list(range(1, Z - 1, pitch))
-    cells, d = [], 0
-    for li, z in enumerate(zs):
-        yo = ys if li % 2 == 0 else ys[::-1]
-        for yi, y in enumerate(yo):
-            xs = list(range(1, X - 1)) if d % 2 == 0 else list(range(X - 2, 0, -1))
-            d += 1
-            cells += [(x, y, z) for x in xs]
-            if yi + 1 < len(yo):
-                st = 1 if yo[yi + 1] > y else -1
-                cells += [(xs[-1], yy, z) for yy in range(y + st, yo[yi + 1], st)]
-        if li + 1 < len(zs):
-            cells += [(xs[-1], yo[-1], zz) for zz in range(z + 1, zs[li + 1])]
-    c = np.array(cells)
-    lab[c[:, 2], c[:, 1], c[:, 0]] = 1
-    return lab, c
-
-
 def test_serpentine_maze_thousands_of_levels():
     """one corridor of more than 2000 steps across the 64-voxel words in x and the 8-voxel tiles in y and z; a pocket walled off
     beside it.  Three point sets out of ONE reference: points close together in the middle (the propagation may leave early), the
@@ -230,7 +186,7 @@ def test_serpentine_maze_thousands_of_levels():
     m = _mapper(size, voxel=w)
     try:
         pos, q = scenes.pose(0, w, delta_vox=0, yaw_deg=0.0)
-        serp, cells = _serpentine(inner)
+        serp, cells = serpentine_labels(inner)
         lab = np.full((size[2], size[1], size[0]), 2, np.int8)
         lab[:, :, :inner[0]] = serp
         pocket = (72, 10, 5)
@@ -359,45 +315,24 @@ def test_costmat_calls_change_nothing_of_the_map_update():
     rng0 = np.random.default_rng(5)
     boxes = [(lo, lo + rng0.integers(6, 26, size=3)) for lo in rng0.integers(-60, 60, size=(24, 3))]
 
-    def frame(k):
-        pos, q = scenes.pose(k, W, delta_vox=3, yaw_deg=0.0)
-        pvt = scenes.local_pivot(pos, W, size)
-        X, Y, Z = size
-        gx = np.arange(X)[None, None, :] + pvt[0]
-        gy = np.arange(Y)[None, :, None] + pvt[1]
-        gz = np.arange(Z)[:, None, None] + pvt[2]
-        lab = np.ones((Z, Y, X), np.int8)
-        for i, (lo, hi) in enumerate(boxes):
-            if (k + i) % 4 != 3:
-                lab[(gx >= lo[0]) & (gx < hi[0]) & (gy >= lo[1]) & (gy < hi[1]) & (gz >= lo[2]) & (gz < hi[2])] = 2
-        lab[:, :, :4] = 0
-        return pos, q, lab
+    def pose(k):
+        return scenes.pose(k, W, delta_vox=3, yaw_deg=0.0)
 
-    a, b = _mapper(size), _mapper(size)
-    try:
-        for k in range(8):
-            pos, q, lab = frame(k)
-            rng = np.random.default_rng(k)
-            pts = (np.array([pos], np.float32) + rng.uniform(-3.0, 3.0, (16, 3)).astype(np.float32)).astype(np.float32)
-            for m in (a, b):
-                m.set_pose(pos, q)
-                m.ogm_labels(lab)
-                if m is a:
-                    a.costmat(pts, 0.1, k % 2 == 0)
-                m.fuse()
-                if m is a:
-                    a.costmat(pts[:3], 0.0)
-                m.batch_edt()
-                if m is a:
-                    a.costmat(pts, 0.0, True)
-                m.merge()
-            la, lb = a.read_local(), b.read_local()
-            for key in la:
-                assert np.array_equal(la[key], lb[key]), (k, key)
-            assert a.stats() == b.stats()
-            xyz = (np.array(a.pivot()) + rng.integers(-4, np.array(size) + 4, size=(500, 3))).astype(np.int32)
-            assert np.array_equal(a.query_global(xyz), b.query_global(xyz))
-            _check(a, la, pts, 0.1, k % 2 == 1)                   # and the matrix of the finished update is exact
-    finally:
-        a.close()
-        b.close()
+    def frame(k):
+        pos, q = pose(k)
+        return pos, q, box_labels(scenes.local_pivot(pos, W, size), size, k, boxes, unknown_slab=4)
+
+    def points(k):
+        return (np.array([pose(k)[0]], np.float32) + np.random.default_rng(k).uniform(-3.0, 3.0, (16, 3)).astype(np.float32)).astype(np.float32)
+
+    def calls(a, k, phase, pos):
+        if phase == "labels":
+            a.costmat(points(k), 0.1, k % 2 == 0)
+        elif phase == "fuse":
+            a.costmat(points(k)[:3], 0.0)
+        elif phase == "edt":
+            a.costmat(points(k), 0.0, True)
+
+    def after(k, a, la):
+        _check(a, la, points(k), 0.1, k % 2 == 1)                 # and the matrix of the finished update is exact
+    stage_calls_change_nothing(size, (frame(k) for k in range(8)), _mapper, calls, after=after)

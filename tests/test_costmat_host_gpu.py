@@ -7,32 +7,17 @@ import numpy as np
 import pytest
 
 import gie
-from gie import scenes
+from stage_common import build_host_probe, lidar_frames
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 
 def test_host_layer_exploration_costs_match_the_mapper(tmp_path):
-    import __graft_entry__ as ge
-    ge.build_hip()
-    exe = str(tmp_path / "costmat_host_probe")
     rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-DGIE_HOST_WITH_HIP", "-I" + os.path.join(rocm, "include"),
-                           "-Wno-unused-result", os.path.join(ROOT, "tests", "gpu_helpers", "costmat_host_probe.cpp"), "-o", exe,
-                           "-L" + ge.CSRC, "-lgie_hip", "-L" + os.path.join(rocm, "lib"), "-lamdhip64",
-                           "-Wl,-rpath," + ge.CSRC, "-Wl,-rpath," + os.path.join(rocm, "lib")])
+    exe = build_host_probe(tmp_path, "costmat_host_probe", ["-DGIE_HOST_WITH_HIP", "-I" + os.path.join(rocm, "include"), "-Wno-unused-result",
+                                                            "-L" + os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath," + os.path.join(rocm, "lib")])
     size, w, cutoff, cap, clearance, min_size = (48, 40, 33), 0.1, 3.0, 20, 0.1, 3
-    world = scenes.BoxWorld(4, extent=(2.5, 2.5, 1.0), n_boxes=30)
-    frames, words = [], [np.float32(4)]
-    for k in range(4):
-        pos, q = scenes.pose(k, w, delta_vox=3, yaw_deg=5.0)
-        pts, _ = scenes.lidar_frame(world, k, pos, q, az=360, max_range=6.0)
-        frames.append((pos, q, pts))
-        words += [np.array(list(pos) + list(q) + [len(pts)], np.float32), pts.ravel()]
-    fpath = str(tmp_path / "frames.f32")
-    np.concatenate([np.atleast_1d(x) for x in words]).astype(np.float32).tofile(fpath)
+    frames, fpath = lidar_frames(tmp_path)
     m = gie.Mapper(gie.make_config(w, size, fast_mode=False, cutoff_dist=cutoff))
     try:
         for pos, q, pts in frames:

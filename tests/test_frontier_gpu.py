@@ -8,48 +8,12 @@ import numpy as np
 import pytest
 
 import frontier_ref as fr
-import gie
 import planner_scenes as ps
 from gie import scenes
+from stage_common import BoxDrive as _BoxDrive, bits as _bits, box_labels as _box_labels, mapper as _mapper, random_boxes as _random_boxes
+from stage_common import serpentine_cells, stage_calls_change_nothing, update as _update
 
 pytestmark = pytest.mark.gpu
-
-
-def _mapper(size, voxel=0.1, **kw):
-    kw.setdefault("cutoff_dist", 3.0)
-    return gie.Mapper(gie.make_config(voxel, size, fast_mode=False, **kw))
-
-
-def _update(m, pos, q, labels):
-    m.set_pose(pos, q)
-    m.ogm_labels(labels)
-    m.step()
-
-
-def _random_boxes(rng, n, extent, smin, smax):
-    out = []
-    for _ in range(n):
-        s = rng.integers(smin, smax, size=3)
-        lo = rng.integers(-extent, extent, size=3)
-        out.append((lo, lo + s))
-    return out
-
-
-def _box_labels(pvt, size, frame, boxes, unknown_slab=0):
-    """label plane [Z][Y][X]: 2 inside the active boxes (global voxels, lo inclusive / hi exclusive), 1 elsewhere; box k is off
-    when (frame + k) % 4 == 3; optional unknown x-slab"""
-    X, Y, Z = size
-    gx = np.arange(X)[None, None, :] + pvt[0]
-    gy = np.arange(Y)[None, :, None] + pvt[1]
-    gz = np.arange(Z)[:, None, None] + pvt[2]
-    lab = np.ones((Z, Y, X), np.int8)
-    for k, (lo, hi) in enumerate(boxes):
-        if (frame + k) % 4 == 3:
-            continue
-        lab[(gx >= lo[0]) & (gx < hi[0]) & (gy >= lo[1]) & (gy < hi[1]) & (gz >= lo[2]) & (gz < hi[2])] = 2
-    if unknown_slab:
-        lab[:, :, :unknown_slab] = 0
-    return lab
 
 
 def _pocket(lab, x0, y0, z0, inner, unknown):
@@ -64,21 +28,6 @@ def _pocket(lab, x0, y0, z0, inner, unknown):
     ux, uy, uz = unknown
     cx, cy, cz = x0 + 1 + (ix - ux) // 2, y0 + 1 + (iy - uy) // 2, zi0 + (zi1 - zi0 - min(uz, zi1 - zi0)) // 2
     lab[cz:cz + min(uz, zi1 - zi0), cy:cy + uy, cx:cx + ux] = 0
-
-
-class _BoxDrive:
-    def __init__(self, size, seed=3, w=0.1, delta=3):
-        self.size, self.w, self.delta = size, w, delta
-        self.boxes = _random_boxes(np.random.default_rng(seed), 24, 60, 6, 26)
-
-    def frame(self, k):
-        pos, q = scenes.pose(k if k < 15 else 30 - k, self.w, delta_vox=self.delta, yaw_deg=0.0)
-        pvt = scenes.local_pivot(pos, self.w, self.size)
-        return pos, q, _box_labels(pvt, self.size, k, self.boxes, unknown_slab=4)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint8)
 
 
 def _check(m, clearance=0.0, conn=26, min_size=1, cap=256, loc=None):
@@ -145,25 +94,6 @@ def test_exact_on_solid_scenes_at_flat_thin_and_long_shapes(size):
         m.close()
 
 
-def _serpentine(size, pitch=4):
-    """the voxels of ONE one-voxel-wide tube snaking along x, rows `pitch` apart in y, layers `pitch` apart in z, in order"""
-    X, Y, Z = size
-    ys, zs = list(range(2, Y - 2, pitch)), list(range(2, Z - 2, pitch))
-    cells, d = [], 0
-    for li, z in enumerate(zs):
-        yo = ys if li % 2 == 0 else ys[::-1]
-        for yi, y in enumerate(yo):
-            xs = list(range(2, X - 2)) if d % 2 == 0 else list(range(X - 3, 1, -1))
-            d += 1
-            cells += [(x, y, z) for x in xs]
-            if yi + 1 < len(yo):
-                st = 1 if yo[yi + 1] > y else -1
-                cells += [(xs[-1], yy, z) for yy in range(y + st, yo[yi + 1], st)]
-        if li + 1 < len(zs):
-            cells += [(xs[-1], yo[-1], zz) for zz in range(z + 1, zs[li + 1])]
-    return np.array(cells)
-
-
 def _free_space(size):
     """labels of a free volume with a lattice of single occupied voxels (z and y multiples of 4, x of 8): obtainFrontiers marks a
     free voxel FNT only when its closest obstacle lies inside the volume, so free space needs obstacles within the cutoff; the
@@ -187,7 +117,7 @@ def test_serpentine_tube_is_one_component_across_every_border():
     size, w = (128, 128, 24), 0.125
     m = _mapper(size, voxel=w)
     try:
-        cells = _serpentine(size)
+        cells = serpentine_cells(size, 4, 2)
         loc = _shape_scene(m, size, w, cells)
         assert (loc["type"][cells[:, 2], cells[:, 1], cells[:, 0]] == fr.UNKNOWN).all()
         ref = _check(m, 0.0, 26, 1, 16, loc=loc)
@@ -385,42 +315,21 @@ def test_result_stays_with_its_pivot_and_two_computes_in_a_row():
         m.close()
 
 
-def _probe(m, size, rng):
-    pvt = np.array(m.pivot())
-    xyz = (pvt + rng.integers(-4, np.array(size) + 4, size=(500, 3))).astype(np.int32)
-    return m.query_global(xyz)
-
-
 def test_frontier_calls_change_nothing_of_the_map_update():
     size = (80, 64, 64)
     d = _BoxDrive(size, seed=5)
-    a, b = _mapper(size), _mapper(size)
-    try:
-        for k in range(12):
-            pos, q, lab = d.frame(k)
-            for m in (a, b):
-                m.set_pose(pos, q)
-                m.ogm_labels(lab)
-                if m is a:
-                    a.frontier_compute(0.1, 2, 26, 16)
-                m.fuse()
-                if m is a:
-                    a.read_frontier_clusters()
-                    a.frontier_compute(0.0, 1, 6, 300)
-                m.batch_edt()
-                if m is a:
-                    a.read_frontier_labels()
-                m.merge()
-                if m is a:
-                    a.frontier_compute(0.2, 8, 26, 0)
-            la, lb = a.read_local(), b.read_local()
-            for key in la:
-                assert np.array_equal(la[key], lb[key]), (k, key)
-            assert a.stats() == b.stats()
-            assert np.array_equal(_probe(a, size, np.random.default_rng(k)), _probe(b, size, np.random.default_rng(k)))
-    finally:
-        a.close()
-        b.close()
+
+    def calls(a, k, phase, pos):
+        if phase == "labels":
+            a.frontier_compute(0.1, 2, 26, 16)
+        elif phase == "fuse":
+            a.read_frontier_clusters()
+            a.frontier_compute(0.0, 1, 6, 300)
+        elif phase == "edt":
+            a.read_frontier_labels()
+        else:
+            a.frontier_compute(0.2, 8, 26, 0)
+    stage_calls_change_nothing(size, (d.frame(k) for k in range(12)), _mapper, calls)
 
 
 def test_dev_forms_through_torch():

@@ -2,7 +2,6 @@
 tests/ground_ref.py on the types Mapper.read_local returns at the same point of the mapper's stream.  Every comparison is exact;
 the closest column is checked as a witness (in range, an obstacle column, at exactly dist_sq)."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
@@ -11,43 +10,15 @@ import pytest
 import gie
 import ground_ref as R
 from gie import _capi, scenes
+from stage_common import W, box_labels as _box_labels, build_host_probe, lidar_frames, mapper as _mapper, stage_calls_change_nothing
+from stage_common import update as _update
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID = 1                                                     # GIE_ERR_INVALID
-W = 0.1
 HDR_FIELDS = ("x_size", "y_size", "z_size", "x_origin", "y_origin", "z_origin", "width", "type")
 
 
-def _mapper(size, voxel=W, **kw):
-    kw.setdefault("cutoff_dist", 3.0)
-    return gie.Mapper(gie.make_config(voxel, size, fast_mode=False, **kw))
-
-
-def _update(m, pos, q, labels):
-    m.set_pose(pos, q)
-    m.ogm_labels(labels)
-    m.step()
-
-
-def _box_labels(pvt, size, frame, boxes, unknown_slab=0):
-    """label plane [Z][Y][X]: 2 inside the active boxes (global voxel coords, lo inclusive / hi exclusive), 1 elsewhere;
-    box k is active unless (frame + k) % 4 == 3 (a quarter of the world toggles every update); optional unknown x-slab"""
-    X, Y, Z = size
-    gx = np.arange(X)[None, None, :] + pvt[0]
-    gy = np.arange(Y)[None, :, None] + pvt[1]
-    gz = np.arange(Z)[:, None, None] + pvt[2]
-    lab = np.ones((Z, Y, X), np.int8)
-    for k, (lo, hi) in enumerate(boxes):
-        if (frame + k) % 4 == 3:
-            continue
-        lab[(gx >= lo[0]) & (gx < hi[0]) & (gy >= lo[1]) & (gy < hi[1]) & (gz >= lo[2]) & (gz < hi[2])] = 2
-    if unknown_slab:
-        lab[:, :, :unknown_slab] = 0
-    return lab
-
-
-def _random_boxes(rng, n, lo, hi, smin, smax):
+def _boxes_between(rng, n, lo, hi, smin, smax):
     """n boxes (global voxel coords) of sides smin .. smax - 1 with their low corners in [lo, hi)"""
     out = []
     for _ in range(n):
@@ -58,7 +29,7 @@ def _random_boxes(rng, n, lo, hi, smin, smax):
 
 
 def _boxes_in(rng, n, pvt, size, smin, smax):
-    return _random_boxes(rng, n, np.asarray(pvt) - smin, np.asarray(pvt) + np.asarray(size), smin, smax)
+    return _boxes_between(rng, n, np.asarray(pvt) - smin, np.asarray(pvt) + np.asarray(size), smin, smax)
 
 
 def _settle(m, lab, pos=(0.0, 0.0, 0.0)):
@@ -247,7 +218,7 @@ def test_no_obstacle_only_obstacles_and_one_voxel():
 # ---------------------------------------------------------------------------------------------------------- 7. a drive
 def test_a_drive_keeps_each_field_at_its_own_pivot():
     size = (64, 48, 16)
-    boxes = _random_boxes(np.random.default_rng(7), 40, (-40, -28, -10), (60, 24, 8), 3, 10)
+    boxes = _boxes_between(np.random.default_rng(7), 40, (-40, -28, -10), (60, 24, 8), 3, 10)
     m = _mapper(size)
     try:
         prev = None
@@ -343,41 +314,24 @@ def test_query_and_dev_forms():
 
 
 # ---------------------------------------------------------------------------------------------------------- 9. the update does not notice
-def _probe(m, size, rng):
-    xyz = (np.array(m.pivot()) + rng.integers(-4, np.array(size) + 4, size=(2000, 3))).astype(np.int32)
-    return m.query_global(xyz)
-
-
 def test_ground_calls_change_nothing_of_the_map_update():
     size = (48, 40, 16)
-    boxes = _random_boxes(np.random.default_rng(5), 40, (-30, -24, -10), (50, 20, 8), 3, 10)
-    a, b = _mapper(size), _mapper(size)
-    try:
-        for k in range(8):
-            pos, q = scenes.pose(k, W, delta_vox=3, yaw_deg=0.0)
-            pvt = scenes.local_pivot(pos, W, size)
-            lab = _box_labels(pvt, size, k, boxes, unknown_slab=3)
-            for m in (a, b):
-                m.set_pose(pos, q)
-                m.ogm_labels(lab)
-                m.fuse()
-                if m is a:                                       # between fuse and merge
-                    a.ground_compute(pvt[2] + 2, pvt[2] + 9, 2, k % 2 == 1)
-                    a.read_ground()
-                m.batch_edt()
-                m.merge()
-                if m is a:
-                    a.ground_compute(pvt[2], pvt[2] + 15)
-                    a.read_costmap_ground()
-                    a.ground_query(np.random.default_rng(k).uniform(-4, 4, (300, 2)).astype(np.float32))
-            la, lb = a.read_local(), b.read_local()
-            for key in la:
-                assert np.array_equal(la[key], lb[key]), (k, key)
-            assert a.stats() == b.stats()
-            assert np.array_equal(_probe(a, size, np.random.default_rng(k)), _probe(b, size, np.random.default_rng(k)))
-    finally:
-        a.close()
-        b.close()
+    boxes = _boxes_between(np.random.default_rng(5), 40, (-30, -24, -10), (50, 20, 8), 3, 10)
+
+    def frame(k):
+        pos, q = scenes.pose(k, W, delta_vox=3, yaw_deg=0.0)
+        return pos, q, _box_labels(scenes.local_pivot(pos, W, size), size, k, boxes, unknown_slab=3)
+
+    def calls(a, k, phase, pos):
+        z = scenes.local_pivot(pos, W, size)[2]
+        if phase == "fuse":                                  # between fuse and merge
+            a.ground_compute(z + 2, z + 9, 2, k % 2 == 1)
+            a.read_ground()
+        elif phase == "merge":
+            a.ground_compute(z, z + 15)
+            a.read_costmap_ground()
+            a.ground_query(np.random.default_rng(k).uniform(-4, 4, (300, 2)).astype(np.float32))
+    stage_calls_change_nothing(size, (frame(k) for k in range(8)), _mapper, calls, n_probe=2000)
 
 
 # ---------------------------------------------------------------------------------------------------------- 10. refusals
@@ -500,21 +454,9 @@ def test_at_size_512x512x24():
 
 # ---------------------------------------------------------------------------------------------------------- 13. host layer
 def test_host_layer_ground_costmap_matches_the_mapper(tmp_path):
-    import __graft_entry__ as ge
-    ge.build_hip()
-    exe = str(tmp_path / "ground_host_probe")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", os.path.join(ROOT, "tests", "gpu_helpers", "ground_host_probe.cpp"), "-o", exe,
-                           "-L" + ge.CSRC, "-lgie_hip", "-Wl,-rpath," + ge.CSRC])
+    exe = build_host_probe(tmp_path, "ground_host_probe")
     size, w, cutoff, gmin, gmax, min_known = (48, 40, 33), 0.1, 3.0, -0.72, 0.43, 2
-    world = scenes.BoxWorld(4, extent=(2.5, 2.5, 1.0), n_boxes=30)
-    frames, words = [], [np.float32(4)]
-    for k in range(4):
-        pos, q = scenes.pose(k, w, delta_vox=3, yaw_deg=5.0)
-        pts, _ = scenes.lidar_frame(world, k, pos, q, az=360, max_range=6.0)
-        frames.append((pos, q, pts))
-        words += [np.array(list(pos) + list(q) + [len(pts)], np.float32), pts.ravel()]
-    fpath = str(tmp_path / "frames.f32")
-    np.concatenate([np.atleast_1d(x) for x in words]).astype(np.float32).tofile(fpath)
+    frames, fpath = lidar_frames(tmp_path)
     m = _mapper(size, voxel=w, cutoff_dist=cutoff)
     try:
         for pos, q, pts in frames:

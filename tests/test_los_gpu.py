@@ -9,8 +9,8 @@ import pytest
 import gie
 import los_ref as lr
 from gie import scenes
-from los_common import W, BoxDrive as _BoxDrive, bits as _bits, cv as _cv, mapper as _mapper, probe as _probe, scene as _scene
-from los_common import update as _update, world as _world
+from stage_common import W, BoxDrive as _BoxDrive, bits as _bits, cv as _cv, mapper as _mapper, scene as _scene
+from stage_common import stage_calls_change_nothing, update as _update, world as _world
 
 pytestmark = pytest.mark.gpu
 
@@ -76,8 +76,9 @@ def _segment_cases(rng, size, opq, n=20000):
 
 
 def _check_segments(m, loc, opq, a, b, pvt=None):
-    got = m.los_segments(_world(m, a, pvt), _world(m, b, pvt))
-    ref = lr.segments(loc["edt"], opq, _world(m, a, pvt), _world(m, b, pvt), m.cfg.voxel_width, m.pivot() if pvt is None else pvt)
+    a, b = _world(m, np.float32(a), pvt=pvt), _world(m, np.float32(b), pvt=pvt)      # (fractional voxels: to float32 before the pivot is added)
+    got = m.los_segments(a, b)
+    ref = lr.segments(loc["edt"], opq, a, b, m.cfg.voxel_width, m.pivot() if pvt is None else pvt)
     assert got.dtype == lr.HIT_DTYPE
     for k in got.dtype.names:
         assert np.array_equal(_bits(got[k]), _bits(ref[k])), (k, int((got[k] != ref[k]).sum()))
@@ -336,7 +337,7 @@ def _whole_feature(m, rng, size, cl, fl, loc=None, check=True):
     pvt = m.pivot()
     n = m.los_prepare(cl, fl)
     plane = m.read_los_opaque()
-    a, b = rng.uniform(-1, np.array(size), (2000, 3)), rng.uniform(-1, np.array(size), (2000, 3))
+    a, b = np.float32(rng.uniform(-1, np.array(size), (2000, 3))), np.float32(rng.uniform(-1, np.array(size), (2000, 3)))
     views = gie.make_views(_world(m, rng.integers(0, size, (8, 3))))
     seg = m.los_segments(_world(m, a), _world(m, b))
     sc = m.view_gain(views, 0.0, 1.2, 0.7)
@@ -485,31 +486,17 @@ def test_dev_forms_through_torch():
 def test_los_calls_change_nothing_of_the_map_update():
     size = (80, 64, 64)
     d = _BoxDrive(size, seed=5)
-    a, b = _mapper(size), _mapper(size)
-    try:
-        for k in range(12):
-            pos, q, lab = d.frame(k)
-            rng = np.random.default_rng(k)
-            for m in (a, b):
-                m.set_pose(pos, q)
-                m.ogm_labels(lab)
-                if m is a:
-                    _whole_feature(a, rng, size, 0.1, 0, check=False)
-                m.fuse()
-                if m is a:
-                    _whole_feature(a, rng, size, 0.0, gie.LOS_UNKNOWN_OPAQUE, check=False)
-                m.batch_edt()
-                if m is a:
-                    a.read_los_opaque()
-                    a.view_gain(gie.make_views(_world(a, [(40, 32, 32)])), 0.0, 2.0)
-                m.merge()
-                if m is a:
-                    _whole_feature(a, rng, size, 0.2, 0, check=(k % 4 == 3))
-            la, lb = a.read_local(), b.read_local()
-            for key in la:
-                assert np.array_equal(la[key], lb[key]), (k, key)
-            assert a.stats() == b.stats()
-            assert np.array_equal(_probe(a, size, np.random.default_rng(k)), _probe(b, size, np.random.default_rng(k)))
-    finally:
-        a.close()
-        b.close()
+    rngs = {}
+
+    def calls(a, k, phase, pos):
+        rng = rngs.setdefault(k, np.random.default_rng(k))       # one generator per frame, through its four phases
+        if phase == "labels":
+            _whole_feature(a, rng, size, 0.1, 0, check=False)
+        elif phase == "fuse":
+            _whole_feature(a, rng, size, 0.0, gie.LOS_UNKNOWN_OPAQUE, check=False)
+        elif phase == "edt":
+            a.read_los_opaque()
+            a.view_gain(gie.make_views(_world(a, [(40, 32, 32)])), 0.0, 2.0)
+        else:
+            _whole_feature(a, rng, size, 0.2, 0, check=(k % 4 == 3))
+    stage_calls_change_nothing(size, (d.frame(k) for k in range(12)), _mapper, calls)

@@ -12,7 +12,7 @@ import gie
 import los_exact as lx
 import los_ref as lr
 from gie import scenes
-from los_common import W, mapper, scene, update, world
+from stage_common import W, mapper, scene, update, world
 
 pytestmark = pytest.mark.gpu
 

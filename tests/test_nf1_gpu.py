@@ -5,73 +5,18 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import gie
 import nf1_ref
 import planner_scenes as ps
 from gie import scenes
 from gie._capi import CostMapHdr
+from stage_common import BoxDrive as _BoxDrive, box_labels as _box_labels, mapper as _mapper, random_boxes as _random_boxes
+from stage_common import serpentine_labels, stage_calls_change_nothing, update as _update, world as _world
 
 pytestmark = pytest.mark.gpu
 
 
-def _mapper(size, voxel=0.1, **kw):
-    kw.setdefault("cutoff_dist", 3.0)
-    return gie.Mapper(gie.make_config(voxel, size, fast_mode=False, **kw))
-
-
-def _update(m, pos, q, labels):
-    m.set_pose(pos, q)
-    m.ogm_labels(labels)
-    m.step()
-
-
-def _random_boxes(rng, n, extent, smin, smax):
-    out = []
-    for _ in range(n):
-        s = rng.integers(smin, smax, size=3)
-        lo = rng.integers(-extent, extent, size=3)
-        out.append((lo, lo + s))
-    return out
-
-
-def _box_labels(pvt, size, frame, boxes, unknown_slab=0):
-    """label plane [Z][Y][X]: 2 inside the active boxes (global voxels, lo inclusive / hi exclusive), 1 elsewhere; box k is off
-    when (frame + k) % 4 == 3; optional unknown x-slab"""
-    X, Y, Z = size
-    gx = np.arange(X)[None, None, :] + pvt[0]
-    gy = np.arange(Y)[None, :, None] + pvt[1]
-    gz = np.arange(Z)[:, None, None] + pvt[2]
-    lab = np.ones((Z, Y, X), np.int8)
-    for k, (lo, hi) in enumerate(boxes):
-        if (frame + k) % 4 == 3:
-            continue
-        lab[(gx >= lo[0]) & (gx < hi[0]) & (gy >= lo[1]) & (gy < hi[1]) & (gz >= lo[2]) & (gz < hi[2])] = 2
-    if unknown_slab:
-        lab[:, :, :unknown_slab] = 0
-    return lab
-
-
-class _BoxDrive:
-    def __init__(self, size, seed=3, w=0.1, delta=3):
-        self.size, self.w, self.delta = size, w, delta
-        self.boxes = _random_boxes(np.random.default_rng(seed), 24, 60, 6, 26)
-
-    def frame(self, k):
-        pos, q = scenes.pose(k if k < 15 else 30 - k, self.w, delta_vox=self.delta, yaw_deg=0.0)
-        pvt = scenes.local_pivot(pos, self.w, self.size)
-        return pos, q, _box_labels(pvt, self.size, k, self.boxes, unknown_slab=4)
-
-
 def _flags(unknown, frontiers):
     return (nf1_ref.UNKNOWN_TRAVERSABLE if unknown else 0) | (nf1_ref.FROM_FRONTIERS if frontiers else 0)
-
-
-def _world(m, local_xyz, jitter=None):
-    """world points (metres) of local voxels [n, 3] (x, y, z) at the mapper's pivot"""
-    v = (np.asarray(local_xyz, np.float64) + np.array(m.pivot())).astype(np.float32)
-    if jitter is not None:
-        v = v + jitter.astype(np.float32)
-    return (v * np.float32(m.cfg.voxel_width)).astype(np.float32)
 
 
 def _goals(m, size, rng, k=4):
@@ -172,35 +117,12 @@ def test_exact_on_solid_scenes_at_flat_thin_and_long_shapes(size):
         m.close()
 
 
-def _serpentine(size, pitch=2):
-    """labels of a walled volume with ONE corridor of free voxels snaking along x, rows `pitch` apart in y, layers in z; the
-    corridor's voxels in order"""
-    X, Y, Z = size
-    lab = np.full((Z, Y, X), 2, np.int8)
-    ys, zs = list(range(1, Y - 1, pitch)), list(range(1, Z - 1, pitch))
-    cells, d = [], 0
-    for li, z in enumerate(zs):
-        yo = ys if li % 2 == 0 else ys[::-1]
-        for yi, y in enumerate(yo):
-            xs = list(range(1, X - 1)) if d % 2 == 0 else list(range(X - 2, 0, -1))
-            d += 1
-            cells += [(x, y, z) for x in xs]
-            if yi + 1 < len(yo):
-                st = 1 if yo[yi + 1] > y else -1
-                cells += [(xs[-1], yy, z) for yy in range(y + st, yo[yi + 1], st)]
-        if li + 1 < len(zs):
-            cells += [(xs[-1], yo[-1], zz) for zz in range(z + 1, zs[li + 1])]
-    c = np.array(cells)
-    lab[c[:, 2], c[:, 1], c[:, 0]] = 1
-    return lab, c
-
-
 def test_serpentine_maze_thousands_of_levels():
     size, w = (150, 36, 20), 0.125                # corridors cross the 64-voxel words in x and the 8-voxel tiles in y and z
     m = _mapper(size, voxel=w)
     try:
         pos, q = scenes.pose(0, w, delta_vox=0, yaw_deg=0.0)
-        lab, cells = _serpentine(size)
+        lab, cells = serpentine_labels(size)
         for _ in range(2):
             _update(m, pos, q, lab)
         loc = m.read_local(dist_sq=False, coc=False)
@@ -424,42 +346,21 @@ def test_refusals():
         t.close()
 
 
-def _probe(m, size, rng):
-    pvt = np.array(m.pivot())
-    xyz = (pvt + rng.integers(-4, np.array(size) + 4, size=(500, 3))).astype(np.int32)
-    return m.query_global(xyz)
-
-
 def test_nf1_calls_change_nothing_of_the_map_update():
     size = (80, 64, 64)
     d = _BoxDrive(size, seed=5)
-    a, b = _mapper(size), _mapper(size)
-    try:
-        for k in range(12):
-            pos, q, lab = d.frame(k)
-            for m in (a, b):
-                m.set_pose(pos, q)
-                m.ogm_labels(lab)
-                if m is a:
-                    a.nf1_compute(np.array([pos], np.float32), 0.1, k % 2 == 0, True)
-                m.fuse()
-                if m is a:
-                    a.nf1_path(np.array([pos], np.float32), 20)
-                    a.read_costmap_nf1()
-                m.batch_edt()
-                if m is a:
-                    a.nf1_compute(np.zeros((3, 3), np.float32), 0.0)
-                m.merge()
-                if m is a:
-                    a.read_nf1()
-            la, lb = a.read_local(), b.read_local()
-            for key in la:
-                assert np.array_equal(la[key], lb[key]), (k, key)
-            assert a.stats() == b.stats()
-            assert np.array_equal(_probe(a, size, np.random.default_rng(k)), _probe(b, size, np.random.default_rng(k)))
-    finally:
-        a.close()
-        b.close()
+
+    def calls(a, k, phase, pos):
+        if phase == "labels":
+            a.nf1_compute(np.array([pos], np.float32), 0.1, k % 2 == 0, True)
+        elif phase == "fuse":
+            a.nf1_path(np.array([pos], np.float32), 20)
+            a.read_costmap_nf1()
+        elif phase == "edt":
+            a.nf1_compute(np.zeros((3, 3), np.float32), 0.0)
+        else:
+            a.read_nf1()
+    stage_calls_change_nothing(size, (d.frame(k) for k in range(12)), _mapper, calls)
 
 
 def test_compute_dev_and_another_mappers_updates_on_one_device():
@@ -475,7 +376,7 @@ def test_compute_dev_and_another_mappers_updates_on_one_device():
     b, c = _mapper(size, wave_workgroups=ncu), _mapper(size)
     try:
         pos, q = scenes.pose(0, w, delta_vox=0, yaw_deg=0.0)
-        lab, cells = _serpentine(msize)
+        lab, cells = serpentine_labels(msize)
         for _ in range(2):
             _update(a, pos, q, lab)
         goal = _world(a, cells[:1])

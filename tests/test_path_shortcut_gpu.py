@@ -12,7 +12,7 @@ import nf1_ref
 import path_cases as pc
 import path_ref as pr
 from gie import scenes
-from los_common import W, BoxDrive, bits, cv, mapper, probe, update, world
+from stage_common import W, BoxDrive, bits, cv, mapper, probe, update, world
 
 pytestmark = pytest.mark.gpu
 

@@ -15,7 +15,7 @@ import los_ref as lr
 import nf1_ref
 import sdf_ref
 from gie import scenes
-from los_common import BoxDrive, bits, cv, mapper, probe, update
+from stage_common import BoxDrive, bits, cv, mapper, probe, update
 
 pytestmark = pytest.mark.gpu
 

@@ -487,7 +487,7 @@ def _planner_stages(base):
     import path_ref
     import planner_scenes as ps
     import sdf_ref
-    from los_common import bits, closed_room
+    from stage_common import bits, closed_room
     off = np.array(base, np.int64)
     w = np.float32(W)
     m = gie.Mapper(gie.make_config(W, P_SIZE, fast_mode=False, cutoff_dist=3.0))

@@ -3,10 +3,11 @@ statement of tests/sdf_ref.py, on what read_local returns at the same point of t
 import numpy as np
 import pytest
 
-import gie
 import planner_scenes as ps
 import sdf_ref
 from gie import scenes
+from stage_common import BoxDrive, box_labels as _box_labels, mapper as _mapper, random_boxes as _random_boxes
+from stage_common import stage_calls_change_nothing, update as _update
 
 pytestmark = pytest.mark.gpu
 
@@ -24,44 +25,6 @@ def _check(m, size, loc=None, ids=None):
     assert np.array_equal(r["sdf"][shallow].view(np.uint32), loc["edt"][shallow].view(np.uint32))
     assert np.allclose(r["sdf"], sdf_ref.sdf(ids, loc["edt"], size), rtol=1e-6, atol=0)
     return r["sdf"], ids, loc
-
-
-def _box_labels(pvt, size, frame, boxes, unknown_slab=0):
-    """label plane [Z][Y][X]: 2 inside the active boxes (global voxel coords, lo inclusive / hi exclusive), 1 elsewhere;
-    box k is active unless (frame + k) % 4 == 3 (a quarter of the world toggles every update); optional unknown x-slab"""
-    X, Y, Z = size
-    gx = np.arange(X)[None, None, :] + pvt[0]
-    gy = np.arange(Y)[None, :, None] + pvt[1]
-    gz = np.arange(Z)[:, None, None] + pvt[2]
-    lab = np.ones((Z, Y, X), np.int8)
-    for k, (lo, hi) in enumerate(boxes):
-        if (frame + k) % 4 == 3:
-            continue
-        inb = (gx >= lo[0]) & (gx < hi[0]) & (gy >= lo[1]) & (gy < hi[1]) & (gz >= lo[2]) & (gz < hi[2])
-        lab[inb] = 2
-    if unknown_slab:
-        lab[:, :, :unknown_slab] = 0
-    return lab
-
-
-def _random_boxes(rng, n, extent, smin, smax):
-    out = []
-    for _ in range(n):
-        s = rng.integers(smin, smax, size=3)
-        lo = rng.integers(-extent, extent, size=3)
-        out.append((lo, lo + s))
-    return out
-
-
-def _update(m, pos, q, labels):
-    m.set_pose(pos, q)
-    m.ogm_labels(labels)
-    m.step()
-
-
-def _mapper(size, voxel=0.1, **kw):
-    kw.setdefault("cutoff_dist", 3.0)
-    return gie.Mapper(gie.make_config(voxel, size, fast_mode=False, **kw))
 
 
 @pytest.mark.parametrize("size", [(96, 80, 72), (97, 61, 45), (77, 53, 1)])
@@ -115,19 +78,6 @@ def test_all_occupied_volume():
         m.close()
 
 
-def _interior(occ):
-    """occupied voxels without an in-volume non-occupied face neighbour"""
-    inner = occ.copy()
-    for ax in range(3):
-        for sh in (1, -1):
-            nb = np.roll(occ, sh, axis=ax)
-            edge = [slice(None)] * 3
-            edge[ax] = 0 if sh == 1 else -1
-            nb[tuple(edge)] = True                            # out of the volume counts as occupied
-            inner &= nb
-    return inner
-
-
 @pytest.mark.parametrize("n", [256, 512])
 def test_c5_hash_world(n):
     size, w = (n, n, n), 0.05
@@ -140,7 +90,7 @@ def test_c5_hash_world(n):
         loc = m.read_local(dist_sq=False, coc=False)
         r = m.read_sdf()
         occ = loc["type"] == 2
-        assert not _interior(occ).any()                      # the device-gated skip of the exact pass
+        assert not ps.interior(occ).any()                      # the device-gated skip of the exact pass
         ids = occ.astype(np.int32)
         if n <= 256:
             assert np.array_equal(ids, sdf_ref.inside_dist_sq(loc["type"]))
@@ -150,20 +100,9 @@ def test_c5_hash_world(n):
         m.close()
 
 
-class _BoxDrive:
-    def __init__(self, size, seed=3, w=0.1, delta=3):
-        self.size, self.w, self.delta = size, w, delta
-        self.boxes = _random_boxes(np.random.default_rng(seed), 24, 60, 6, 26)
-
-    def frame(self, k):
-        pos, q = scenes.pose(k if k < 15 else 30 - k, self.w, delta_vox=self.delta, yaw_deg=0.0)     # out and back
-        pvt = scenes.local_pivot(pos, self.w, self.size)
-        return pos, q, _box_labels(pvt, self.size, k, self.boxes)
-
-
 def test_drive_moving_toggling_boxes():
     size = (96, 80, 64)
-    d = _BoxDrive(size)
+    d = BoxDrive(size, unknown_slab=0)
     m = _mapper(size)
     try:
         deep = 0
@@ -179,7 +118,7 @@ def test_drive_moving_toggling_boxes():
 
 def test_stream_enabled_update_and_ray_cast_update():
     size = (80, 72, 64)
-    d = _BoxDrive(size, seed=4)
+    d = BoxDrive(size, seed=4, unknown_slab=0)
     m = _mapper(size)
     try:
         m.stream_enable(True)
@@ -199,40 +138,18 @@ def test_stream_enabled_update_and_ray_cast_update():
         m.close()
 
 
-def _probe(m, size, rng):
-    pvt = np.array(m.pivot())
-    xyz = (pvt + rng.integers(-4, np.array(size) + 4, size=(500, 3))).astype(np.int32)
-    return m.query_global(xyz)
-
-
 def test_sdf_calls_change_nothing_of_the_map_update():
     size = (80, 64, 64)
-    d = _BoxDrive(size, seed=5)
-    a, b = _mapper(size), _mapper(size)
-    try:
-        for k in range(12):
-            pos, q, lab = d.frame(k)
-            for m in (a, b):
-                m.set_pose(pos, q)
-                m.ogm_labels(lab)
-                if m is a:
-                    a.query_sdf(np.zeros((7, 3), np.float32))
-                m.fuse()
-                if m is a:
-                    a.read_sdf()
-                m.batch_edt()
-                m.merge()
-                if m is a:
-                    a.query_sdf(np.random.default_rng(k).uniform(-5, 5, (1000, 3)).astype(np.float32))
-            la, lb = a.read_local(), b.read_local()
-            for key in la:
-                assert np.array_equal(la[key], lb[key]), (k, key)
-            assert a.stats() == b.stats()
-            pa, pb = _probe(a, size, np.random.default_rng(k)), _probe(b, size, np.random.default_rng(k))
-            assert np.array_equal(pa, pb)
-    finally:
-        a.close()
-        b.close()
+    d = BoxDrive(size, seed=5, unknown_slab=0)
+
+    def calls(a, k, phase, pos):
+        if phase == "labels":
+            a.query_sdf(np.zeros((7, 3), np.float32))
+        elif phase == "fuse":
+            a.read_sdf()
+        elif phase == "merge":
+            a.query_sdf(np.random.default_rng(k).uniform(-5, 5, (1000, 3)).astype(np.float32))
+    stage_calls_change_nothing(size, (d.frame(k) for k in range(12)), _mapper, calls)
 
 
 def _points(rng, m, size, w, n):
@@ -252,7 +169,7 @@ def _points(rng, m, size, w, n):
 def test_queries_match_the_reference_and_the_dev_form(size):
     import torch
     w = 0.125                                                  # a power of two: u = p / w - pvt is exact on the faces
-    d = _BoxDrive(size, seed=6, w=w)
+    d = BoxDrive(size, seed=6, w=w, unknown_slab=0)
     m = _mapper(size, voxel=w)
     try:
         for k in range(3):
@@ -296,7 +213,7 @@ def test_queries_match_the_reference_and_the_dev_form(size):
 
 def test_cache_follows_the_map():
     size = (64, 64, 48)
-    d = _BoxDrive(size, seed=7)
+    d = BoxDrive(size, seed=7, unknown_slab=0)
     a, b = _mapper(size), _mapper(size)
     xyz = _points(np.random.default_rng(2), a, size, 0.1, 20000)
     try:

@@ -13,7 +13,7 @@ import path_ref as pr
 import sdf_ref
 import test_planner_loop_gpu as pl
 from gie import scenes
-from los_common import bits, mapper, update
+from stage_common import bits, mapper, update
 
 pytestmark = pytest.mark.gpu
 
