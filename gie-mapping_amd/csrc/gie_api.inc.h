@@ -15,7 +15,7 @@
 #include <unistd.h>
 static const char *const gie_kernel_names[GIE_K_NUM] = { "ogm_classify", "ray_register", "ray_free", "ray_finalize", "block_alloc", "fuse",
        "edt_pass_y", "edt_pass_x", "edt_pass_z", "mark", "frontiers", "wave_a", "wave_b", "waves", "commit", "edt_prep", "mark_commit",
-       "ground", "ground_query", "cloud", "los", "los_query", "sdf", "sdf_query" };
+       "ground_nf1", "ground", "ground_query", "cloud", "los", "los_query", "sdf", "sdf_query" };
 
 #define GIE_REHASH_PERIOD 64                 /* map updates between two rebuilds of the hash table while blocks are being erased */
 static thread_local std::string g_gie_err;
@@ -92,6 +92,14 @@ struct gie_ground_cache {
     int pvt[3] = { 0, 0, 0 };             /* the pivot and CostMap origin at that compute */
     float origin[3] = { 0.f, 0.f, 0.f };
 };
+/* the ground navigation function (gie_ground_nf1.inc.h): allocated at its first compute through gie_dalloc, kept until the next
+ * compute; it refers to the ground field's pivot and is invalidated by the next gie_ground_compute* */
+struct gie_gnf1_cache {
+    int32_t *f = nullptr;                 /* the field, X * Y */
+    uint64_t *bits = nullptr;             /* two bit planes */
+    int32_t *words = nullptr;             /* control words */
+    int valid = 0;                        /* a compute has been enqueued on the current ground field */
+};
 /* the goal-to-goal cost matrix (gie_costmat.inc.h): scratch only, allocated at the first compute through gie_dalloc; no result is kept */
 struct gie_costmat_cache {
     uint64_t *masks = nullptr;            /* two planes of one 64-bit mask per voxel */
@@ -136,6 +144,7 @@ struct gie_mapper {
     gie_frontier_cache fr;                /* the frontier clusters (HIP backend: gie_frontier.inc.h) */
     gie_los_cache los;                    /* line of sight (HIP backend: gie_los.inc.h) */
     gie_ground_cache ground;              /* the ground costmap (HIP backend: gie_ground.inc.h) */
+    gie_gnf1_cache gnf1;                  /* the ground navigation function (HIP backend: gie_ground_nf1.inc.h) */
     gie_costmat_cache costmat;            /* the cost matrix's scratch (HIP backend: gie_costmat.inc.h) */
     int32_t *cloud_count = nullptr;       /* display clouds (HIP backend: gie_cloud.inc.h): the counter of a _dev call that passes none, allocated at the first such call */
 };

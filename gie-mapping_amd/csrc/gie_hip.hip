@@ -595,3 +595,4 @@ static void be_waves(be_state *b, const gie_ctx &c, int with_ab, int record_seed
 #include "gie_path.inc.h"
 #include "gie_cloud.inc.h"
 #include "gie_ground.inc.h"
+#include "gie_ground_nf1.inc.h"

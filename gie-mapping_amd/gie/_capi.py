@@ -132,7 +132,12 @@ class GroundCell(C.Structure):
     _fields_ = [("dist_sq", C.c_int32), ("coc_x", C.c_int32), ("coc_y", C.c_int32), ("type", C.c_int8), ("inside", C.c_uint8), ("pad", C.c_uint8 * 2)]
 
 
-assert C.sizeof(GroundParam) == 32 and C.sizeof(GroundCell) == 16
+class GroundNf1Param(C.Structure):
+    """gie_ground_nf1_param (include/gie.h): 32 bytes."""
+    _fields_ = [("clearance_sq", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+assert C.sizeof(GroundParam) == 32 and C.sizeof(GroundCell) == 16 and C.sizeof(GroundNf1Param) == 32
 assert C.sizeof(CloudParam) == 32 and C.sizeof(CloudPoint) == 16
 assert C.sizeof(ShortcutParam) == 16 and C.sizeof(Waypoint) == 24 and C.sizeof(ShortcutInfo) == 16
 assert C.sizeof(LosHit) == 24 and C.sizeof(View) == 64 and C.sizeof(ViewScore) == 16 and C.sizeof(LosParam) == 16 and C.sizeof(ViewParam) == 16
@@ -143,6 +148,8 @@ LOS_UNKNOWN_OPAQUE = 1
 CLOUD_TYPE = 0
 CLOUD_DIST = 1
 GROUND_UNKNOWN_BLOCKS = 1
+GROUND_NF1_UNKNOWN_TRAVERSABLE = 1
+GROUND_NF1_FROM_FRONTIERS = 2
 VOX_UNKNOWN, VOX_FREE, VOX_OCCUPIED, VOX_FNT = 0, 1, 2, 3
 
 
@@ -283,6 +290,15 @@ DEVICE_ONLY = {
     "read_costmap_ground_dev": (C.c_int, [_H, C.c_void_p, C.POINTER(CostMapHdr)]),
     "ground_query": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p]),
     "ground_query_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p]),
+    # NF1 navigation function of the ground costmap and its paths (include/gie.h): device library only
+    "ground_nf1_compute": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(GroundNf1Param), C.c_void_p]),
+    "ground_nf1_compute_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(GroundNf1Param), C.c_void_p]),
+    "read_ground_nf1": (C.c_int, [_H, C.c_void_p]),
+    "read_ground_nf1_dev": (C.c_int, [_H, C.c_void_p]),
+    "ground_nf1_path": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "ground_nf1_path_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "read_costmap_ground_nf1": (C.c_int, [_H, C.c_void_p, C.POINTER(CostMapHdr)]),
+    "read_costmap_ground_nf1_dev": (C.c_int, [_H, C.c_void_p, C.POINTER(CostMapHdr)]),
     # goal-to-goal cost matrix of the local volume (include/gie.h): device library only
     "costmat_compute": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(Nf1Param), C.c_void_p, C.c_void_p]),
     "costmat_compute_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(Nf1Param), C.c_void_p, C.c_void_p]),

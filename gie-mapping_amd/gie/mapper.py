@@ -13,8 +13,8 @@ import sys
 import numpy as np
 
 from . import _capi
-from ._capi import CLOUD_DIST, CLOUD_TYPE, GROUND_UNKNOWN_BLOCKS, LOS_UNKNOWN_OPAQUE, NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE, VOX_FNT, VOX_FREE, VOX_OCCUPIED, VOX_UNKNOWN
-from ._capi import CamParam, CloudParam, Config, CostMapHdr, FrameStats, FrontierParam, GroundParam, LosParam, MultiScanParam, Nf1Param, ScanParam, ShortcutParam, ViewParam, Voxel
+from ._capi import CLOUD_DIST, CLOUD_TYPE, GROUND_NF1_FROM_FRONTIERS, GROUND_NF1_UNKNOWN_TRAVERSABLE, GROUND_UNKNOWN_BLOCKS, LOS_UNKNOWN_OPAQUE, NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE, VOX_FNT, VOX_FREE, VOX_OCCUPIED, VOX_UNKNOWN
+from ._capi import CamParam, CloudParam, Config, CostMapHdr, FrameStats, FrontierParam, GroundNf1Param, GroundParam, LosParam, MultiScanParam, Nf1Param, ScanParam, ShortcutParam, ViewParam, Voxel
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG, "csrc", "libgie_hip.so")
@@ -828,3 +828,68 @@ class Mapper(MapperBase):
     def ground_query_dev(self, d_xy, n, d_out):
         """n queries with points (n x 2 float32) and records (n x 16 bytes) in DEVICE buffers, on the mapper's stream."""
         self._chk(self._f["ground_query_dev"](self._h, C.c_void_p(d_xy or None), int(n), C.c_void_p(d_out or None)))
+
+    # --- NF1 navigation function of the ground costmap (include/gie.h) --------------------------
+    def ground_nf1_param(self, clearance_sq=0, unknown_traversable=False, from_frontiers=False):
+        """gie_ground_nf1_param: clearance_sq in squared CELLS, compared with the ground field's dist_sq."""
+        p = GroundNf1Param()
+        p.clearance_sq = int(clearance_sq)
+        p.flags = (GROUND_NF1_UNKNOWN_TRAVERSABLE if unknown_traversable else 0) | (GROUND_NF1_FROM_FRONTIERS if from_frontiers else 0)
+        return p
+
+    def ground_nf1_compute(self, goals=(), clearance_sq=0, unknown_traversable=False, from_frontiers=False):
+        """NF1 of the current ground field from goal points (n x 2 metres, world frame) and / or its FNT cells; returns the number
+        of sources (synchronises)."""
+        g = np.ascontiguousarray(np.asarray(goals, dtype=np.float32).reshape(-1, 2))
+        p = self.ground_nf1_param(clearance_sq, unknown_traversable, from_frontiers)
+        ns = C.c_int32(0)
+        self._chk(self._f["ground_nf1_compute"](self._h, _ptr(g) if g.shape[0] else None, g.shape[0], C.byref(p), C.byref(ns)))
+        return ns.value
+
+    def ground_nf1_compute_dev(self, d_goals, n, clearance_sq=0, unknown_traversable=False, from_frontiers=False, d_n_sources=0):
+        """The same on the mapper's stream without a host wait; goals (n x 2 float32) and the source count (one int32; 0 = not
+        wanted) in DEVICE buffers (raw addresses)."""
+        p = self.ground_nf1_param(clearance_sq, unknown_traversable, from_frontiers)
+        self._chk(self._f["ground_nf1_compute_dev"](self._h, C.c_void_p(d_goals or None), int(n), C.byref(p), C.c_void_p(d_n_sources or None)))
+
+    def read_ground_nf1(self):
+        """int32 field [Y][X]: steps to the nearest source, -1 where none is reachable (synchronises)."""
+        out = np.empty((self.size[1], self.size[0]), np.int32)
+        self._chk(self._f["read_ground_nf1"](self._h, _ptr(out)))
+        return out
+
+    def read_ground_nf1_dev(self, d_nf1):
+        """The field into a device buffer (X * Y int32, raw address), asynchronous on the mapper's stream."""
+        self._chk(self._f["read_ground_nf1_dev"](self._h, C.c_void_p(d_nf1 or None)))
+
+    def ground_nf1_path(self, starts, max_len, path=None):
+        """Descents from n start points (n x 2 metres): (path [n, max_len, 2] int32 GLOBAL x y, len [n] int32 = nf1(start) + 1, 0
+        without a path).  Only the first min(len, max_len) points of a path are written: the rest is zero, or what the caller's
+        `path` held (synchronises)."""
+        xy = np.ascontiguousarray(np.asarray(starts, dtype=np.float32).reshape(-1, 2))
+        n, max_len = xy.shape[0], int(max_len)
+        if path is None:
+            path = np.zeros((n, max(max_len, 1), 2), np.int32)
+        elif path.dtype != np.int32 or path.shape != (n, max_len, 2) or not path.flags.c_contiguous:
+            raise ValueError("ground_nf1_path: path must be a contiguous (n, max_len, 2) int32 array")
+        ln = np.zeros(n, np.int32)
+        self._chk(self._f["ground_nf1_path"](self._h, _ptr(xy) if n else None, n, max_len, _ptr(path) if n else None, _ptr(ln) if n else None))
+        return path, ln
+
+    def ground_nf1_path_dev(self, d_starts, n, max_len, d_path, d_len):
+        """n starts (n x 2 float32), points (n x max_len x 2 int32) and lengths (n int32) in DEVICE buffers, on the mapper's stream."""
+        self._chk(self._f["ground_nf1_path_dev"](self._h, C.c_void_p(d_starts or None), int(n), int(max_len), C.c_void_p(d_path or None),
+                                                 C.c_void_p(d_len or None)))
+
+    def read_costmap_ground_nf1(self):
+        """The one-layer TYPE_NF1 CostMap of the ground navigation function: (SeenDist payload [Y][X], header) (synchronises)."""
+        pay = np.empty((self.size[1], self.size[0]), SEENDIST_DTYPE)
+        hdr = CostMapHdr()
+        self._chk(self._f["read_costmap_ground_nf1"](self._h, _ptr(pay), C.byref(hdr)))
+        return pay, hdr
+
+    def read_costmap_ground_nf1_dev(self, dptr):
+        """That payload into a device buffer (raw address), asynchronous on the mapper's stream; returns the header."""
+        hdr = CostMapHdr()
+        self._chk(self._f["read_costmap_ground_nf1_dev"](self._h, C.c_void_p(dptr or None), C.byref(hdr)))
+        return hdr

@@ -63,6 +63,7 @@ struct Parameters {
     float ground_min_height = 0.f, ground_max_height = -1.f;   /* no counterpart in the reference: the band of world z (metres) a ground robot's body occupies, for ground_costmap();
                                                                  * "ground/min_height", "ground/max_height"; off while max < min (the default) */
     int ground_min_known = 1;            /* "ground/min_known": gie_ground_param.min_known */
+    float ground_robot_radius = 0.f;     /* "ground/robot_radius" (metres): ground_plan() keeps ceil(radius / voxel_width) cells away from every obstacle column */
     bool profile_loc_rms = false, profile_glb_rms = false;
     std::string log_name = "GIE_log.csv";
     std::string data_case = "ugv_corridor";
@@ -121,6 +122,7 @@ struct Parameters {
         else if (k == "ogm/min_height") ogm_min_h = fl(); else if (k == "ogm/max_height") ogm_max_h = fl();
         else if (k == "ground/min_height") ground_min_height = fl(); else if (k == "ground/max_height") ground_max_height = fl();
         else if (k == "ground/min_known") ground_min_known = in();
+        else if (k == "ground/robot_radius") ground_robot_radius = fl();
         else if (k == "wave/fast_mode") fast_mode = b(); else if (k == "wave/cutoff_dist") cutoff_dist = fl();
         else if (k == "hash/bucket_max") max_bucket = in(); else if (k == "hash/block_max") max_block = in();
         else if (k == "gpu/wave_workgroups") wave_workgroups = in(); else if (k == "gpu/place_tries") place_tries = in();
@@ -601,6 +603,36 @@ public:
         return true;
     }
     int32_t ground_counts[4] = { 0, 0, 0, 0 };   /* columns of the last ground_costmap(): UNKNOWN, FREE, OCCUPIED, FNT */
+
+    /* gie_ground_nf1_param.clearance_sq of ground_robot_radius: cells = ceil(radius / voxel_width), squared */
+    int ground_clearance_sq() const { const int cells = (int)ceilf(param.ground_robot_radius / cfg_.voxel_width); return cells * cells; }
+    /* A ground robot's plan on the map as it stands (include/gie.h "ground navigation function"): the ground field of the band as
+     * ground_costmap() computes it, its NF1 from n goals (metres, world frame, two floats each) or, with from_frontiers, from the
+     * field's FNT cells too, at the clearance of ground_robot_radius, and ONE descent from the robot's position of the last
+     * publishMap: at most max_len points, GLOBAL cell x, y, the robot's cell first; empty when no source can be reached.
+     * ground_plan_len = the descent's full length (steps + 1; it exceeds path.size() when max_len cut it), ground_plan_sources =
+     * the number of sources.  Returns false, and leaves everything alone, while the band is not set. */
+    bool ground_plan(const float *goal_xy, int n, bool from_frontiers, int max_len, std::vector<std::array<int32_t, 2>> &path)
+    {
+        if (param.ground_max_height < param.ground_min_height) return false;
+        const float w = cfg_.voxel_width;
+        gie_ground_param g = {};
+        g.z_lo = (int32_t)std::floor(param.ground_min_height / w + 0.5f);      /* as ground_costmap() */
+        g.z_hi = (int32_t)std::floor(param.ground_max_height / w + 0.5f);
+        g.min_known = param.ground_min_known;
+        chk(gie_ground_compute(m_, &g, ground_counts));
+        gie_ground_nf1_param p = {};
+        p.clearance_sq = ground_clearance_sq();
+        p.flags = from_frontiers ? GIE_GROUND_NF1_FROM_FRONTIERS : 0;
+        chk(gie_ground_nf1_compute(m_, goal_xy, n, &p, &ground_plan_sources));
+        std::vector<int32_t> xy((size_t)std::max(max_len, 1) * 2);
+        ground_plan_len = 0;
+        chk(gie_ground_nf1_path(m_, robot_pos_, 1, max_len, xy.data(), &ground_plan_len));
+        path.resize((size_t)std::min(ground_plan_len, max_len));
+        for (size_t i = 0; i < path.size(); i++) path[i] = { xy[2 * i], xy[2 * i + 1] };
+        return true;
+    }
+    int32_t ground_plan_len = 0, ground_plan_sources = 0;      /* of the last ground_plan() */
 
     /* VOLMAPNODE::visualize without the publishers: the clouds the display flags ask for (the others come back empty), of the map as
      * it stands.  sensor_pos is the reference's argument: its z is replaced by vis_height before the slice's z is taken

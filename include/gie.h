@@ -692,6 +692,66 @@ int gie_read_costmap_ground_dev(gie_mapper *h, gie_seendist *d_payload, gie_cost
 int gie_ground_query(gie_mapper *h, const float *xy, int n, gie_ground_cell *out);
 int gie_ground_query_dev(gie_mapper *h, const float *d_xy, int n, gie_ground_cell *d_out);
 
+/* ---- ground navigation function: NF1 and its descent paths on the ground costmap — the planner of the configurations that set
+ * ugv_height.  gie_nf1_compute is no use to them for the reason the ground costmap exists: in the volume the floor is an obstacle
+ * one voxel away everywhere, so no useful clearance leaves anything traversable at floor level.  No counterpart in the reference.
+ *
+ * Everything is over the ground field that is valid where gie_ground_nf1_compute* is enqueued: type(c), dist_sq(c) and the pivot
+ * are that field's (gie_read_ground*).  Every value is an integer and exact.
+ *  traversable(c)  type(c) is FREE or FNT (or UNKNOWN, with GIE_GROUND_NF1_UNKNOWN_TRAVERSABLE), and dist_sq(c) == -1 or
+ *                  dist_sq(c) >= clearance_sq (squared cells).  dist_sq is the field's own: computed with GIE_GROUND_UNKNOWN_BLOCKS
+ *                  an UNKNOWN column is an obstacle column at distance 0 and is traversable at clearance_sq == 0 only.
+ *  sources         the traversable cells among: the cell of each goal (metres, world frame, two floats per goal), which is
+ *                  gie_pos2coord(g_k, w) - pvt_k for k = x, y — gie_ground_query's mapping; goals outside the rectangle or not
+ *                  finite are ignored — and, with GIE_GROUND_NF1_FROM_FRONTIERS, every FNT cell.  n == 0 is valid.  *n_sources =
+ *                  the number of distinct source cells (n_sources / d_n_sources may be NULL).
+ *  nf1(c)          the number of steps of the shortest 4-connected path of traversable cells inside the rectangle from c to a
+ *                  source: 0 on sources, -1 where there is no such path (cells that are not traversable included).  X * Y int32, x
+ *                  fastest.
+ *  path            for each of n start points (the goals' mapping): len = 0 for a start outside the rectangle, not finite, or with
+ *                  nf1 < 0.  Otherwise v_0 = the start's cell and v_{i+1} = the first 4-neighbour of v_i in the order -x +x -y +y
+ *                  whose value is nf1(v_i) - 1, down to a source; len = nf1(start) + 1 also when that exceeds max_len.  path_xy
+ *                  holds max_len points per start, each two int32, GLOBAL x, y; exactly min(len, max_len) of them are written, the
+ *                  rest is left as it was.
+ *  CostMap         the header gie_read_costmap_ground fills (z_size 1, z_origin from the ground field's z_lo) with type = 2
+ *                  (TYPE_NF1); payload of X * Y elements: d = (float)nf1, -1.0f where nf1 is -1; o = type != UNKNOWN; s and the
+ *                  padding 0.
+ * Lifetime: the field is kept until the next gie_ground_nf1_compute* and refers to the ground field's pivot; a map update does
+ *  not change it.  A later gie_ground_compute* invalidates it — the readers, the paths and the CostMap then return GIE_ERR_INVALID
+ *  until the next gie_ground_nf1_compute*: no copy of the ground field's type plane is kept.
+ * GIE_ERR_INVALID, nothing written: a NULL handle or param; clearance_sq < 0; an unknown flag bit or non-zero reserved; n < 0, or
+ *  n > 0 with a NULL array (goals; starts, path_xy or len); max_len < 1; a compute before a ground field exists; a read, path or
+ *  CostMap before the first compute or after an invalidation; a NULL output in gie_read_ground_nf1_dev, a NULL payload in
+ *  gie_read_costmap_ground_nf1_dev; a tiled mapper (all eight refuse, as every planner section does).
+ * The host forms synchronise; the _dev forms take DEVICE buffers and are enqueued on the mapper's stream (gie_get_stream) with no
+ *  host wait and no read-back.
+ * Memory: a mapper that never calls the section allocates and launches nothing.  The first compute allocates per CELL (gie_dalloc,
+ *  freed by gie_destroy): the field (4 bytes), two bit planes with rows padded to 64-bit words — blocked or visited, and the
+ *  frontier — and four control words: 4.25 bytes per cell when X is a multiple of 64, 1.1 MB for 512 x 512.
+ * Cost: a compute is at most three launches: the bit planes (one pass over the ground field's type and dist_sq, 5 bytes per cell),
+ *  the goals, and the propagation — ONE workgroup that runs every BFS level up to a workgroup barrier, on bit planes it holds
+ *  in the LDS of its compute unit when three — frontier, next frontier, blocked — fit 144 KiB (ceil(X/64) * Y <= 6144 words: 512 x 768
+ *  and everything smaller), on the two planes in global memory otherwise; which, the size alone decides.  No grid barrier: the launch is no member of the chain of
+ *  grid-barrier launches, needs no co-residency and has no timeout path — gie_nf1_compute's GIE_ERR_TIMEOUT cannot occur; the
+ *  number of levels is bounded by X * Y on the device.  A level costs the workgroup one pass over the two planes and a 4-byte
+ *  store per cell that gets its value.
+ * gie_profile_read: "ground_nf1" = compute, exports and paths (the entry in front of "ground"). */
+#define GIE_GROUND_NF1_UNKNOWN_TRAVERSABLE 1    /* UNKNOWN cells may be traversed (their dist_sq still decides) */
+#define GIE_GROUND_NF1_FROM_FRONTIERS 2         /* every traversable FNT cell is a source */
+typedef struct gie_ground_nf1_param {   /* 32 bytes */
+    int32_t clearance_sq;   /* >= 0, squared cells: dist_sq of a traversable cell is at least this (or -1) */
+    int32_t flags;          /* GIE_GROUND_NF1_* */
+    int32_t reserved[6];    /* 0 */
+} gie_ground_nf1_param;
+int gie_ground_nf1_compute(gie_mapper *h, const float *goal_xy, int n, const gie_ground_nf1_param *p, int32_t *n_sources);
+int gie_ground_nf1_compute_dev(gie_mapper *h, const float *d_goal_xy, int n, const gie_ground_nf1_param *p, int32_t *d_n_sources);
+int gie_read_ground_nf1(gie_mapper *h, int32_t *nf1);
+int gie_read_ground_nf1_dev(gie_mapper *h, int32_t *d_nf1);
+int gie_ground_nf1_path(gie_mapper *h, const float *start_xy, int n, int max_len, int32_t *path_xy, int32_t *len);
+int gie_ground_nf1_path_dev(gie_mapper *h, const float *d_start_xy, int n, int max_len, int32_t *d_path_xy, int32_t *d_len);
+int gie_read_costmap_ground_nf1(gie_mapper *h, gie_seendist *payload, gie_costmap_hdr *hdr);
+int gie_read_costmap_ground_nf1_dev(gie_mapper *h, gie_seendist *d_payload, gie_costmap_hdr *hdr);
+
 /* ---- goal-to-goal cost matrix: the path lengths among up to 64 points (the robot and the goals of the frontier clusters, say), the
  * input of every tour-based explorer — in which order to visit the clusters.  n fields of gie_nf1_compute would give the same
  * numbers with n persistent launches and n whole fields; here ONE level-synchronous pass advances all searches, a 64-bit mask per
