@@ -145,6 +145,7 @@ struct gie_mapper {
     gie_los_cache los;                    /* line of sight (HIP backend: gie_los.inc.h) */
     gie_ground_cache ground;              /* the ground costmap (HIP backend: gie_ground.inc.h) */
     gie_gnf1_cache gnf1;                  /* the ground navigation function (HIP backend: gie_ground_nf1.inc.h) */
+    uint64_t *glos_blk = nullptr;         /* ground line of sight (HIP backend: gie_ground_los.inc.h): the blocked bit plane, allocated at the first call and rebuilt by every call */
     gie_costmat_cache costmat;            /* the cost matrix's scratch (HIP backend: gie_costmat.inc.h) */
     int32_t *cloud_count = nullptr;       /* display clouds (HIP backend: gie_cloud.inc.h): the counter of a _dev call that passes none, allocated at the first such call */
 };

@@ -137,6 +137,27 @@ class GroundNf1Param(C.Structure):
     _fields_ = [("clearance_sq", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 6)]
 
 
+class GroundLosParam(C.Structure):
+    """gie_ground_los_param (include/gie.h): 16 bytes."""
+    _fields_ = [("clearance_sq", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class GroundHit(C.Structure):
+    """gie_ground_hit (include/gie.h): 24 bytes."""
+    _fields_ = [("first", C.c_int32), ("len", C.c_int32), ("hit", C.c_int32 * 2), ("min_dist_sq", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GroundShortcutParam(C.Structure):
+    """gie_ground_shortcut_param (include/gie.h): 32 bytes."""
+    _fields_ = [("lookahead", C.c_int32), ("max_wp", C.c_int32), ("clearance_sq", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class GroundWaypoint(C.Structure):
+    """gie_ground_waypoint (include/gie.h): 24 bytes."""
+    _fields_ = [("xy", C.c_int32 * 2), ("index", C.c_int32), ("min_dist_sq", C.c_int32), ("forced", C.c_int32), ("reserved", C.c_int32)]
+
+
+assert C.sizeof(GroundLosParam) == 16 and C.sizeof(GroundHit) == 24 and C.sizeof(GroundShortcutParam) == 32 and C.sizeof(GroundWaypoint) == 24
 assert C.sizeof(GroundParam) == 32 and C.sizeof(GroundCell) == 16 and C.sizeof(GroundNf1Param) == 32
 assert C.sizeof(CloudParam) == 32 and C.sizeof(CloudPoint) == 16
 assert C.sizeof(ShortcutParam) == 16 and C.sizeof(Waypoint) == 24 and C.sizeof(ShortcutInfo) == 16
@@ -150,6 +171,7 @@ CLOUD_DIST = 1
 GROUND_UNKNOWN_BLOCKS = 1
 GROUND_NF1_UNKNOWN_TRAVERSABLE = 1
 GROUND_NF1_FROM_FRONTIERS = 2
+GROUND_LOS_UNKNOWN_TRAVERSABLE = 1
 VOX_UNKNOWN, VOX_FREE, VOX_OCCUPIED, VOX_FNT = 0, 1, 2, 3
 
 
@@ -299,6 +321,11 @@ DEVICE_ONLY = {
     "ground_nf1_path_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "read_costmap_ground_nf1": (C.c_int, [_H, C.c_void_p, C.POINTER(CostMapHdr)]),
     "read_costmap_ground_nf1_dev": (C.c_int, [_H, C.c_void_p, C.POINTER(CostMapHdr)]),
+    # ground line of sight: segment checks and any-angle paths on the ground costmap (include/gie.h): device library only
+    "ground_segments": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(GroundLosParam), C.c_void_p]),
+    "ground_segments_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(GroundLosParam), C.c_void_p]),
+    "ground_shortcut": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(GroundShortcutParam), C.c_void_p, C.c_void_p]),
+    "ground_shortcut_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(GroundShortcutParam), C.c_void_p, C.c_void_p]),
     # goal-to-goal cost matrix of the local volume (include/gie.h): device library only
     "costmat_compute": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(Nf1Param), C.c_void_p, C.c_void_p]),
     "costmat_compute_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(Nf1Param), C.c_void_p, C.c_void_p]),

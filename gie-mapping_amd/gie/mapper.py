@@ -13,8 +13,8 @@ import sys
 import numpy as np
 
 from . import _capi
-from ._capi import CLOUD_DIST, CLOUD_TYPE, GROUND_NF1_FROM_FRONTIERS, GROUND_NF1_UNKNOWN_TRAVERSABLE, GROUND_UNKNOWN_BLOCKS, LOS_UNKNOWN_OPAQUE, NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE, VOX_FNT, VOX_FREE, VOX_OCCUPIED, VOX_UNKNOWN
-from ._capi import CamParam, CloudParam, Config, CostMapHdr, FrameStats, FrontierParam, GroundNf1Param, GroundParam, LosParam, MultiScanParam, Nf1Param, ScanParam, ShortcutParam, ViewParam, Voxel
+from ._capi import CLOUD_DIST, CLOUD_TYPE, GROUND_LOS_UNKNOWN_TRAVERSABLE, GROUND_NF1_FROM_FRONTIERS, GROUND_NF1_UNKNOWN_TRAVERSABLE, GROUND_UNKNOWN_BLOCKS, LOS_UNKNOWN_OPAQUE, NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE, VOX_FNT, VOX_FREE, VOX_OCCUPIED, VOX_UNKNOWN
+from ._capi import CamParam, CloudParam, Config, CostMapHdr, FrameStats, FrontierParam, GroundLosParam, GroundNf1Param, GroundParam, GroundShortcutParam, LosParam, MultiScanParam, Nf1Param, ScanParam, ShortcutParam, ViewParam, Voxel
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG, "csrc", "libgie_hip.so")
@@ -37,6 +37,8 @@ CLOUD_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("intensity", 
 CLOUD_NO_BAND = (-2 ** 31, 2 ** 31 - 1)
 # gie_ground_cell (16 bytes)
 GROUND_CELL_DTYPE = np.dtype([("dist_sq", "<i4"), ("coc", "<i4", (2,)), ("type", "i1"), ("inside", "u1"), ("pad", "u1", (2,))])
+GROUND_HIT_DTYPE = np.dtype([("first", "<i4"), ("len", "<i4"), ("hit", "<i4", (2,)), ("min_dist_sq", "<i4"), ("reserved", "<i4")])
+GROUND_WAYPOINT_DTYPE = np.dtype([("xy", "<i4", (2,)), ("index", "<i4"), ("min_dist_sq", "<i4"), ("forced", "<i4"), ("reserved", "<i4")])
 VOXEL_DTYPE = np.dtype([("occ_val", "u1"), ("vox_type", "i1"), ("pad", "<i2"), ("dist_sq", "<i4"),
                         ("coc", "<i4", (3,))])
 
@@ -880,6 +882,68 @@ class Mapper(MapperBase):
         """n starts (n x 2 float32), points (n x max_len x 2 int32) and lengths (n int32) in DEVICE buffers, on the mapper's stream."""
         self._chk(self._f["ground_nf1_path_dev"](self._h, C.c_void_p(d_starts or None), int(n), int(max_len), C.c_void_p(d_path or None),
                                                  C.c_void_p(d_len or None)))
+
+    # --- ground line of sight: segment checks and any-angle paths on the ground costmap (include/gie.h) ---
+    def ground_los_param(self, clearance_sq=0, unknown_traversable=False):
+        """gie_ground_los_param: clearance_sq in squared CELLS, compared with the ground field's dist_sq."""
+        p = GroundLosParam()
+        p.clearance_sq, p.flags = int(clearance_sq), GROUND_LOS_UNKNOWN_TRAVERSABLE if unknown_traversable else 0
+        return p
+
+    def ground_segments(self, a, b, clearance_sq=0, unknown_traversable=False):
+        """n segments between points a and b (n x 2 metres, world frame) over the current ground field -> GROUND_HIT_DTYPE [n]
+        (synchronises)."""
+        a = np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(-1, 2))
+        b = np.ascontiguousarray(np.asarray(b, dtype=np.float32).reshape(-1, 2))
+        if len(a) != len(b):
+            raise ValueError("ground_segments: as many start points as end points")
+        out = np.zeros(len(a), GROUND_HIT_DTYPE)
+        p = self.ground_los_param(clearance_sq, unknown_traversable)
+        n = len(a)
+        self._chk(self._f["ground_segments"](self._h, _ptr(a) if n else None, _ptr(b) if n else None, n, C.byref(p), _ptr(out) if n else None))
+        return out
+
+    def ground_segments_dev(self, d_a, d_b, n, d_out, clearance_sq=0, unknown_traversable=False):
+        """n segments with endpoints (n x 2 float32 each) and results (n x 24 bytes) in DEVICE buffers (raw addresses), on the
+        mapper's stream."""
+        p = self.ground_los_param(clearance_sq, unknown_traversable)
+        self._chk(self._f["ground_segments_dev"](self._h, C.c_void_p(d_a or None), C.c_void_p(d_b or None), int(n), C.byref(p), C.c_void_p(d_out or None)))
+
+    def ground_shortcut_param(self, lookahead, max_wp, clearance_sq=0, unknown_traversable=False):
+        p = GroundShortcutParam()
+        p.lookahead, p.max_wp, p.clearance_sq = int(lookahead), int(max_wp), int(clearance_sq)
+        p.flags = GROUND_LOS_UNKNOWN_TRAVERSABLE if unknown_traversable else 0
+        return p
+
+    def ground_shortcut(self, paths, lens, lookahead, max_wp, clearance_sq=0, unknown_traversable=False, wp=None):
+        """Waypoints of n paths (paths: (n, max_len, 2) int32 global cells and lens [n] int32, as ground_nf1_path leaves them) with a
+        look-ahead of `lookahead` points: (wp [n, max_wp] GROUND_WAYPOINT_DTYPE, info [n] SHORTCUT_INFO_DTYPE) (synchronises).  Only
+        the first min(info.count, max_wp) records of a path are written: the rest of wp is zero, or what the caller's `wp` held."""
+        pts = np.ascontiguousarray(np.asarray(paths, dtype=np.int32))
+        if pts.ndim != 3 or pts.shape[2] != 2:
+            raise ValueError("ground_shortcut: paths must be (n, max_len, 2)")
+        n, max_len = pts.shape[0], pts.shape[1]
+        ln = np.ascontiguousarray(np.asarray(lens, dtype=np.int32).reshape(-1))
+        if len(ln) != n:
+            raise ValueError("ground_shortcut: one length per path")
+        max_wp = int(max_wp)
+        if wp is None:
+            wp = np.zeros((n, max(max_wp, 0)), GROUND_WAYPOINT_DTYPE)
+        elif wp.dtype != GROUND_WAYPOINT_DTYPE or wp.shape != (n, max_wp) or not wp.flags.c_contiguous:
+            raise ValueError("ground_shortcut: wp must be a contiguous (n, max_wp) GROUND_WAYPOINT_DTYPE array")
+        info = np.zeros(n, SHORTCUT_INFO_DTYPE)
+        p = self.ground_shortcut_param(lookahead, max_wp, clearance_sq, unknown_traversable)
+        spare = np.zeros(1, GROUND_WAYPOINT_DTYPE)            # (an empty array has no address to give: n == 0, or max_wp == 0)
+        self._chk(self._f["ground_shortcut"](self._h, _ptr(pts) if pts.size else None, _ptr(ln) if n else None, n, max_len, C.byref(p),
+                                             _ptr(wp if wp.size else spare), _ptr(info) if n else None))
+        return wp, info
+
+    def ground_shortcut_dev(self, d_path, d_len, n, max_len, d_wp, d_info, lookahead, max_wp, clearance_sq=0, unknown_traversable=False):
+        """n paths with points (n x max_len x 2 int32), lengths (n int32), waypoints (n x max_wp x 24 bytes) and infos (n x 16 bytes)
+        in DEVICE buffers (raw addresses; 0 = not wanted), on the mapper's stream."""
+        p = self.ground_shortcut_param(lookahead, max_wp, clearance_sq, unknown_traversable)
+        self._chk(self._f["ground_shortcut_dev"](self._h, C.c_void_p(d_path or None), C.c_void_p(d_len or None), int(n), int(max_len), C.byref(p),
+                                                 C.c_void_p(d_wp or None), C.c_void_p(d_info or None)))
 
     def read_costmap_ground_nf1(self):
         """The one-layer TYPE_NF1 CostMap of the ground navigation function: (SeenDist payload [Y][X], header) (synchronises)."""

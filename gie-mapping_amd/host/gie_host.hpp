@@ -634,6 +634,29 @@ public:
     }
     int32_t ground_plan_len = 0, ground_plan_sources = 0;      /* of the last ground_plan() */
 
+    /* The plan a ground robot can drive (include/gie.h "ground line of sight"): ground_plan()'s chain — the ground field, its NF1,
+     * one descent of at most max_len points from the robot's position — and then the any-angle shortcut of that descent at the
+     * same clearance, ground_clearance_sq(), with a look-ahead of `lookahead` path points: wp holds the waypoints, the robot's
+     * cell first (every one of them: it is sized by the count), ground_waypoints_info their count, the number of forced legs (0
+     * for a descent of this field) and the length in cells.  ground_plan_len and ground_plan_sources are set as by ground_plan().
+     * Returns false, and leaves everything alone, while the band is not set. */
+    bool ground_waypoints(const float *goal_xy, int n, bool from_frontiers, int max_len, int lookahead, std::vector<gie_ground_waypoint> &wp)
+    {
+        std::vector<std::array<int32_t, 2>> path;
+        if (!ground_plan(goal_xy, n, from_frontiers, max_len, path)) return false;
+        const int32_t len = (int32_t)path.size();
+        const int cap = std::max(len, 1);
+        std::vector<int32_t> xy((size_t)cap * 2, 0);
+        for (size_t i = 0; i < path.size(); i++) { xy[2 * i] = path[i][0]; xy[2 * i + 1] = path[i][1]; }
+        gie_ground_shortcut_param p = {};
+        p.lookahead = lookahead; p.max_wp = cap; p.clearance_sq = ground_clearance_sq();
+        wp.assign((size_t)cap, gie_ground_waypoint{});
+        chk(gie_ground_shortcut(m_, xy.data(), &len, 1, cap, &p, wp.data(), &ground_waypoints_info));
+        wp.resize((size_t)ground_waypoints_info.count);
+        return true;
+    }
+    gie_shortcut_info ground_waypoints_info = { 0, 0, 0.f, 0 };   /* of the last ground_waypoints() */
+
     /* VOLMAPNODE::visualize without the publishers: the clouds the display flags ask for (the others come back empty), of the map as
      * it stands.  sensor_pos is the reference's argument: its z is replaced by vis_height before the slice's z is taken
      * (volumetric_mapper.h:339-341), so only vis_height decides.  The local clouds always come from the device (gie_cloud_local);

@@ -752,6 +752,114 @@ int gie_ground_nf1_path_dev(gie_mapper *h, const float *d_start_xy, int n, int m
 int gie_read_costmap_ground_nf1(gie_mapper *h, gie_seendist *payload, gie_costmap_hdr *hdr);
 int gie_read_costmap_ground_nf1_dev(gie_mapper *h, gie_seendist *d_payload, gie_costmap_hdr *hdr);
 
+/* ---- ground line of sight: straight segments and any-angle paths on the ground costmap — the ground counterparts of the segment
+ * checks of "line of sight" and of "path shortcutting".  Those two read the opaque plane of gie_los_prepare, which is built from
+ * the volume: there the floor is an obstacle one voxel away everywhere (why the ground costmap exists).  Here a disc robot's
+ * straight move is tested against the ground field, and gie_ground_nf1_path's 4-connected staircase becomes the few straight legs
+ * a controller can follow.  No counterpart in the reference's code.
+ *
+ * Every call refers to the ground field that is valid where the call is enqueued: type(c), dist_sq(c) and the pivot are that field's
+ * (gie_read_ground*).  There is no prepare call and no kept result: a later gie_ground_compute* simply makes later calls see the
+ * new field; a map update changes nothing, because it does not change the ground field; the ground navigation function is not
+ * needed and not touched.  Every value but `length` is an integer and exact.
+ *  blocked(c)    c is not traversable by the ground navigation function's rule: traversable(c) iff type(c) is FREE or FNT (or
+ *                UNKNOWN, with GIE_GROUND_LOS_UNKNOWN_TRAVERSABLE), and dist_sq(c) == -1 or dist_sq(c) >= clearance_sq (squared
+ *                cells).  A field without an obstacle column has dist_sq == -1 everywhere: every clearance passes.  The robot's
+ *                disc is swept along a line by that rule: a cell of the line closer than the radius to an obstacle column is blocked.
+ *  cell line     L2(a, b), for local cells a and b: the voxel line of "line of sight" on two axes — the cells whose square shares
+ *                a piece of POSITIVE length with the straight segment between the two cell centres, in the order of those pieces
+ *                from a to b.  L2(a, a) = (a).  The walk: with n_k = |b_k - a_k|, crossing j (1..n_k) of axis k lies at
+ *                t = (2j - 1) / (2 n_k); take the smaller pending t and step BOTH axes when they tie, until none is pending.
+ *                (2 j_x - 1) * n_y against (2 j_y - 1) * n_x decides the order, exactly in 32-bit integers (gie_create keeps every
+ *                side <= 1024).  L2(b, a) is L2(a, b) reversed; no cell repeats; 1 + max(n_x, n_y) <= len <= 1 + n_x + n_y;
+ *                L2(a, b) is L((a, 0), (b, 0)) of "line of sight" without the third coordinate.
+ *                A tie is a diagonal move through a corner of the grid: the two cells that touch the line only at that corner
+ *                are not on it, so the line passes BETWEEN two corner-touching cells whatever they hold.  With clearance_sq >= 2
+ *                that is harmless: a cell beside an obstacle column (dist_sq 1) is then blocked itself, and a diagonal move between
+ *                two obstacle columns has both its ends blocked.  With clearance_sq 0 or 1 a line may slip between two obstacle
+ *                columns that touch at a corner.
+ *  segment       a pair of points (metres, world frame, two floats each), each mapped as in gie_ground_query:
+ *                gie_pos2coord(p_k, w) - pvt_k for k = x, y.  Result, one gie_ground_hit per segment:
+ *                  first        index along L2(a, b) of the first blocked cell (a has index 0); -1 when none is blocked; -2 when
+ *                               an endpoint is not finite or lies outside the field's rectangle (every other field is then 0);
+ *                  len          the number of cells of L2(a, b);
+ *                  hit          the first blocked cell, GLOBAL cell coordinates (local + pivot); b's when first == -1;
+ *                  min_dist_sq  the minimum of dist_sq over the cells of index 0 .. first (all of the line when first == -1), the
+ *                               values gie_read_ground returns: -1 on a field without an obstacle column;
+ *                  reserved     0.
+ *  shortcut input  the buffers of gie_ground_nf1_path*: n paths of max_len points (2 int32 each, GLOBAL cell coordinates), len[i]
+ *                as that call left it: path i has m = min(max(len[i], 0), max_len) points v_0 .. v_{m-1}.  Any polyline of cells is
+ *                legal: it need not be 4-connected or come from NF1, points may repeat, lie outside the field or be any int32
+ *                (local = global - pivot is computed in 64 bits).
+ *  Clear(a, b)   a and b are inside the field's rectangle and no cell of L2(a, b), both ends included, is blocked.
+ *  waypoints     indices k_0 = 0 < k_1 < .. < k_T = m - 1.  While k_t < m - 1, with K = lookahead:
+ *                  J = { j : k_t < j <= min(k_t + K, m - 1) and Clear(v_{k_t}, v_j) };  k_{t+1} = max J,
+ *                or, when J is empty, k_{t+1} = k_t + 1 and that leg is FORCED: the path stays connected and the caller learns that
+ *                it is not valid there.  Visibility along a path is not monotone (a pillar's shadow hides a stretch of points and
+ *                lets the ones behind it through): max J is the largest clear index of the whole window, not the last before the
+ *                first blocked one.  count = T + 1; 0 when m = 0.
+ *  gie_ground_waypoint  record t: xy = v_{k_t} as given, index = k_t, reserved = 0.
+ *                  t = 0: forced = 0; min_dist_sq = dist_sq(v_0) when v_0 is inside the rectangle, otherwise -2.
+ *                  a clear leg: forced = 0; min_dist_sq = the minimum of dist_sq over all cells of L2(v_{k_{t-1}}, v_{k_t}).
+ *                  a forced leg: forced = 1; min_dist_sq = -2.  (-1 is a legal distance — no obstacle column — so -2 marks
+ *                  "no value".)
+ *  gie_shortcut_info  the record of "path shortcutting", reused: count as above, even when it exceeds max_wp; forced = the number
+ *                of forced legs; length = a float sum, started at 0.0f and accumulated in leg order t = 1 .. T: each CLEAR leg adds
+ *                sqrtf((float)(dx^2 + dy^2)) of its two ends (an exact integer below 2^22; sqrtf as in gie_read_sdf), a forced leg
+ *                adds nothing.  The unit is cells.
+ *  capacity      wp holds max_wp records per path; only the first min(count, max_wp) of a path are written (the convention of
+ *                gie_ground_nf1_path's len > max_len), entries beyond them are left as they are.  info is complete whatever max_wp
+ *                is.  Shortcutting a path of gie_ground_nf1_path with the clearance_sq and UNKNOWN flag of its
+ *                gie_ground_nf1_compute has no forced leg: consecutive path cells are traversable neighbours.
+ * GIE_ERR_INVALID, nothing written: a NULL handle; a tiled mapper (all four refuse, as every planner section does); no ground field
+ *  yet; a NULL param; clearance_sq < 0; a flag other than GIE_GROUND_LOS_UNKNOWN_TRAVERSABLE; non-zero reserved; n < 0; n > 0 with a
+ *  NULL input (a_xy, b_xy; path_xy, len) or, for segments, a NULL out; max_len < 1; lookahead outside 1..4096; max_wp < 0; wp NULL
+ *  with max_wp > 0; wp and info both NULL.  n == 0 is valid and launches nothing.
+ * The host forms stage through the two scratch slots of the host forms and synchronise; gie_ground_shortcut hands the entries of
+ *  wp beyond a path's records back as they were.  The _dev forms take DEVICE buffers and are enqueued on the mapper's stream
+ *  (gie_get_stream) with no host wait, no read-back and no grid barrier.
+ * Memory: a mapper that never calls the section allocates and launches nothing.  The first call allocates one bit plane of blocked
+ *  cells with rows padded to 64-bit words (8 * ceil(X/64) / X bytes per cell: 32 KiB for 512 x 512; gie_dalloc, freed by
+ *  gie_destroy), of which no reader may assume anything between calls.
+ * Cost: a call is two launches: the blocked plane (one pass over the ground field's type and dist_sq, 5 bytes per cell) and the
+ *  query — a lane per segment, or a wave per path (a leg costs its window's lines in chunks of 64 from the far end, up to the first
+ *  chunk with a clear one; a point outside the rectangle or in a blocked cell costs nothing).
+ * gie_profile_read: counted under "ground_query". */
+#define GIE_GROUND_LOS_UNKNOWN_TRAVERSABLE 1    /* UNKNOWN cells are not blocked by their type (their dist_sq still decides) */
+typedef struct gie_ground_los_param {   /* 16 bytes */
+    int32_t clearance_sq;   /* >= 0, squared cells: dist_sq of a cell that is not blocked is at least this (or -1) */
+    int32_t flags;          /* GIE_GROUND_LOS_* */
+    int32_t reserved[2];    /* 0 */
+} gie_ground_los_param;
+typedef struct gie_ground_hit {         /* 24 bytes */
+    int32_t first;
+    int32_t len;
+    int32_t hit[2];
+    int32_t min_dist_sq;
+    int32_t reserved;       /* 0 */
+} gie_ground_hit;
+typedef struct gie_ground_shortcut_param {   /* 32 bytes */
+    int32_t lookahead;      /* K in 1..4096: a leg may reach at most K path points ahead */
+    int32_t max_wp;         /* >= 0: capacity of the waypoint array, per path */
+    int32_t clearance_sq;   /* as gie_ground_los_param */
+    int32_t flags;          /* GIE_GROUND_LOS_* */
+    int32_t reserved[4];    /* 0 */
+} gie_ground_shortcut_param;
+typedef struct gie_ground_waypoint {    /* 24 bytes */
+    int32_t xy[2];          /* the path point, GLOBAL cell coordinates, copied from the input */
+    int32_t index;          /* its index in the input path */
+    int32_t min_dist_sq;    /* squared cells; -2: a forced leg, or a first point outside the rectangle */
+    int32_t forced;         /* 1: the leg that ends here is not a clear line */
+    int32_t reserved;       /* 0 */
+} gie_ground_waypoint;
+int gie_ground_segments(gie_mapper *h, const float *a_xy, const float *b_xy, int n, const gie_ground_los_param *p, gie_ground_hit *out);
+int gie_ground_segments_dev(gie_mapper *h, const float *d_a_xy, const float *d_b_xy, int n, const gie_ground_los_param *p,
+                            gie_ground_hit *d_out);
+int gie_ground_shortcut(gie_mapper *h, const int32_t *path_xy, const int32_t *len, int n, int max_len,
+                        const gie_ground_shortcut_param *p, gie_ground_waypoint *wp, gie_shortcut_info *info);
+int gie_ground_shortcut_dev(gie_mapper *h, const int32_t *d_path_xy, const int32_t *d_len, int n, int max_len,
+                            const gie_ground_shortcut_param *p, gie_ground_waypoint *d_wp, gie_shortcut_info *d_info);
+
 /* ---- goal-to-goal cost matrix: the path lengths among up to 64 points (the robot and the goals of the frontier clusters, say), the
  * input of every tour-based explorer — in which order to visit the clusters.  n fields of gie_nf1_compute would give the same
  * numbers with n persistent launches and n whole fields; here ONE level-synchronous pass advances all searches, a 64-bit mask per
