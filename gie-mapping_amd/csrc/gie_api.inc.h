@@ -15,7 +15,7 @@
 #include <unistd.h>
 static const char *const gie_kernel_names[GIE_K_NUM] = { "ogm_classify", "ray_register", "ray_free", "ray_finalize", "block_alloc", "fuse",
        "edt_pass_y", "edt_pass_x", "edt_pass_z", "mark", "frontiers", "wave_a", "wave_b", "waves", "commit", "edt_prep", "mark_commit",
-       "ground_nf1", "ground", "ground_query", "cloud", "los", "los_query", "sdf", "sdf_query" };
+       "ground_frontier", "ground_nf1", "ground", "ground_query", "cloud", "los", "los_query", "sdf", "sdf_query" };
 
 #define GIE_REHASH_PERIOD 64                 /* map updates between two rebuilds of the hash table while blocks are being erased */
 static thread_local std::string g_gie_err;
@@ -100,6 +100,17 @@ struct gie_gnf1_cache {
     int32_t *words = nullptr;             /* control words */
     int valid = 0;                        /* a compute has been enqueued on the current ground field */
 };
+/* the ground frontier clusters (gie_ground_frontier.inc.h): allocated at their first compute through gie_dalloc, kept until the next
+ * compute; they refer to the ground field's pivot and are invalidated by the next gie_ground_compute* */
+struct gie_gfr_cache {
+    int32_t *planes = nullptr;            /* the union-find forest and the sizes, X * Y each */
+    uint64_t *bits = nullptr;             /* two bit planes */
+    int32_t *words = nullptr;             /* per-word counts and ranks, control words */
+    void *rec = nullptr;                  /* rec_cap records */
+    int rec_cap = 0;
+    int valid = 0;                        /* a compute has been enqueued on the current ground field */
+    int max_clusters = 0, min_size = 1;   /* of that compute */
+};
 /* the goal-to-goal cost matrix (gie_costmat.inc.h): scratch only, allocated at the first compute through gie_dalloc; no result is kept */
 struct gie_costmat_cache {
     uint64_t *masks = nullptr;            /* two planes of one 64-bit mask per voxel */
@@ -146,6 +157,7 @@ struct gie_mapper {
     gie_ground_cache ground;              /* the ground costmap (HIP backend: gie_ground.inc.h) */
     gie_gnf1_cache gnf1;                  /* the ground navigation function (HIP backend: gie_ground_nf1.inc.h) */
     uint64_t *glos_blk = nullptr;         /* ground line of sight (HIP backend: gie_ground_los.inc.h): the blocked bit plane, allocated at the first call and rebuilt by every call */
+    gie_gfr_cache gfr;                    /* the ground frontier clusters (HIP backend: gie_ground_frontier.inc.h) */
     gie_costmat_cache costmat;            /* the cost matrix's scratch (HIP backend: gie_costmat.inc.h) */
     int32_t *cloud_count = nullptr;       /* display clouds (HIP backend: gie_cloud.inc.h): the counter of a _dev call that passes none, allocated at the first such call */
 };
@@ -1554,10 +1566,13 @@ extern "C" int gie_profile_read(gie_mapper *m, gie_kernel_time *out, int max_ent
     if (!m || !out || max_entries < GIE_K_NUM) { gie_set_err("gie_profile_read: need room for all kernels"); return GIE_ERR_INVALID; }
     float ms[GIE_K_NUM]; int n[GIE_K_NUM];
     be_prof_collect(&m->be, ms, n, GIE_K_NUM);
+    int k = 0;
     for (int i = 0; i < GIE_K_NUM; i++) {
-        memset(out[i].name, 0, sizeof(out[i].name));
-        strncpy(out[i].name, gie_kernel_names[i], sizeof(out[i].name) - 1);
-        out[i].total_ms = ms[i]; out[i].launches = n[i];
+        if (i == GIE_K_GROUND_FRONTIER && !m->gfr.planes) continue;     /* (listed once the section has been used: gie.h "ground frontier clusters") */
+        memset(out[k].name, 0, sizeof(out[k].name));
+        strncpy(out[k].name, gie_kernel_names[i], sizeof(out[k].name) - 1);
+        out[k].total_ms = ms[i]; out[k].launches = n[i];
+        k++;
     }
-    return GIE_K_NUM;
+    return k;
 }

@@ -231,7 +231,7 @@ enum {
 /* ids of the per-kernel profile (be_prof brackets; gie_kernel_names, gie_profile_read) */
 enum { GIE_K_CLASSIFY = 0, GIE_K_RAY_REGISTER, GIE_K_RAY_FREE, GIE_K_RAY_FINAL, GIE_K_ALLOC, GIE_K_FUSE, GIE_K_EDT_Y, GIE_K_EDT_X,
        GIE_K_EDT_Z, GIE_K_MARK, GIE_K_FRONTIER, GIE_K_WAVE_A, GIE_K_WAVE_B, GIE_K_WAVE_C, GIE_K_COMMIT, GIE_K_EDT_ZFACES, GIE_K_MARKC,
-       GIE_K_GROUND_NF1, GIE_K_GROUND, GIE_K_GROUND_QUERY, GIE_K_CLOUD, GIE_K_LOS, GIE_K_LOS_QUERY, GIE_K_SDF, GIE_K_SDF_QUERY, GIE_K_NUM };   /* (the signed distance field's ids come last, as gie.h says; the map update's keep their indices) */
+       GIE_K_GROUND_FRONTIER, GIE_K_GROUND_NF1, GIE_K_GROUND, GIE_K_GROUND_QUERY, GIE_K_CLOUD, GIE_K_LOS, GIE_K_LOS_QUERY, GIE_K_SDF, GIE_K_SDF_QUERY, GIE_K_NUM };   /* (the signed distance field's ids come last, as gie.h says; the map update's keep their indices) */
 #define GIE_MAX_LEVELS 4096
 #define GIE_ERRF_POOL 1
 #define GIE_ERRF_QUEUE 2

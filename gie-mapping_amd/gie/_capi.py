@@ -157,6 +157,19 @@ class GroundWaypoint(C.Structure):
     _fields_ = [("xy", C.c_int32 * 2), ("index", C.c_int32), ("min_dist_sq", C.c_int32), ("forced", C.c_int32), ("reserved", C.c_int32)]
 
 
+class GroundFrontierParam(C.Structure):
+    """gie_ground_frontier_param (include/gie.h): 32 bytes; clearance_sq in squared cells."""
+    _fields_ = [("clearance_sq", C.c_int32), ("min_size", C.c_int32), ("connectivity", C.c_int32), ("max_clusters", C.c_int32),
+                ("flags", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class GroundFrontierCluster(C.Structure):
+    """gie_ground_frontier_cluster (include/gie.h): 64 bytes, sum at offset 40."""
+    _fields_ = [("label", C.c_int32), ("size", C.c_int32), ("lo", C.c_int32 * 2), ("hi", C.c_int32 * 2), ("rep", C.c_int32 * 2),
+                ("centroid", C.c_float * 2), ("sum", C.c_int64 * 2), ("rep_dist_sq", C.c_int32), ("reserved", C.c_int32)]
+
+
+assert C.sizeof(GroundFrontierParam) == 32 and C.sizeof(GroundFrontierCluster) == 64 and GroundFrontierCluster.sum.offset == 40
 assert C.sizeof(GroundLosParam) == 16 and C.sizeof(GroundHit) == 24 and C.sizeof(GroundShortcutParam) == 32 and C.sizeof(GroundWaypoint) == 24
 assert C.sizeof(GroundParam) == 32 and C.sizeof(GroundCell) == 16 and C.sizeof(GroundNf1Param) == 32
 assert C.sizeof(CloudParam) == 32 and C.sizeof(CloudPoint) == 16
@@ -326,6 +339,15 @@ DEVICE_ONLY = {
     "ground_segments_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(GroundLosParam), C.c_void_p]),
     "ground_shortcut": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(GroundShortcutParam), C.c_void_p, C.c_void_p]),
     "ground_shortcut_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(GroundShortcutParam), C.c_void_p, C.c_void_p]),
+    # ground frontier clusters and the gather of the ground navigation function (include/gie.h): device library only
+    "ground_frontier_compute": (C.c_int, [_H, C.POINTER(GroundFrontierParam), C.c_void_p, C.c_void_p]),
+    "ground_frontier_compute_dev": (C.c_int, [_H, C.POINTER(GroundFrontierParam), C.c_void_p]),
+    "read_ground_frontier_clusters": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "read_ground_frontier_clusters_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "read_ground_frontier_labels": (C.c_int, [_H, C.c_void_p]),
+    "read_ground_frontier_labels_dev": (C.c_int, [_H, C.c_void_p]),
+    "ground_nf1_query": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p]),
+    "ground_nf1_query_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p]),
     # goal-to-goal cost matrix of the local volume (include/gie.h): device library only
     "costmat_compute": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(Nf1Param), C.c_void_p, C.c_void_p]),
     "costmat_compute_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(Nf1Param), C.c_void_p, C.c_void_p]),

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import CLOUD_DIST, CLOUD_TYPE, GROUND_LOS_UNKNOWN_TRAVERSABLE, GROUND_NF1_FROM_FRONTIERS, GROUND_NF1_UNKNOWN_TRAVERSABLE, GROUND_UNKNOWN_BLOCKS, LOS_UNKNOWN_OPAQUE, NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE, VOX_FNT, VOX_FREE, VOX_OCCUPIED, VOX_UNKNOWN
-from ._capi import CamParam, CloudParam, Config, CostMapHdr, FrameStats, FrontierParam, GroundLosParam, GroundNf1Param, GroundParam, GroundShortcutParam, LosParam, MultiScanParam, Nf1Param, ScanParam, ShortcutParam, ViewParam, Voxel
+from ._capi import CamParam, CloudParam, Config, CostMapHdr, FrameStats, FrontierParam, GroundFrontierParam, GroundLosParam, GroundNf1Param, GroundParam, GroundShortcutParam, LosParam, MultiScanParam, Nf1Param, ScanParam, ShortcutParam, ViewParam, Voxel
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG, "csrc", "libgie_hip.so")
@@ -39,6 +39,9 @@ CLOUD_NO_BAND = (-2 ** 31, 2 ** 31 - 1)
 GROUND_CELL_DTYPE = np.dtype([("dist_sq", "<i4"), ("coc", "<i4", (2,)), ("type", "i1"), ("inside", "u1"), ("pad", "u1", (2,))])
 GROUND_HIT_DTYPE = np.dtype([("first", "<i4"), ("len", "<i4"), ("hit", "<i4", (2,)), ("min_dist_sq", "<i4"), ("reserved", "<i4")])
 GROUND_WAYPOINT_DTYPE = np.dtype([("xy", "<i4", (2,)), ("index", "<i4"), ("min_dist_sq", "<i4"), ("forced", "<i4"), ("reserved", "<i4")])
+# gie_ground_frontier_cluster: 64 bytes, the offsets of the C struct
+GROUND_FRONTIER_CLUSTER_DTYPE = np.dtype([("label", "<i4"), ("size", "<i4"), ("lo", "<i4", (2,)), ("hi", "<i4", (2,)), ("rep", "<i4", (2,)),
+                                          ("centroid", "<f4", (2,)), ("sum", "<i8", (2,)), ("rep_dist_sq", "<i4"), ("reserved", "<i4")])
 VOXEL_DTYPE = np.dtype([("occ_val", "u1"), ("vox_type", "i1"), ("pad", "<i2"), ("dist_sq", "<i4"),
                         ("coc", "<i4", (3,))])
 
@@ -944,6 +947,67 @@ class Mapper(MapperBase):
         p = self.ground_shortcut_param(lookahead, max_wp, clearance_sq, unknown_traversable)
         self._chk(self._f["ground_shortcut_dev"](self._h, C.c_void_p(d_path or None), C.c_void_p(d_len or None), int(n), int(max_len), C.byref(p),
                                                  C.c_void_p(d_wp or None), C.c_void_p(d_info or None)))
+
+    # --- ground frontier clusters and route costs to them (include/gie.h) ------------------------
+    def ground_frontier_param(self, clearance_sq=0, min_size=1, connectivity=8, max_clusters=256):
+        """gie_ground_frontier_param: clearance_sq in squared CELLS, compared with the ground field's dist_sq (as ground_nf1_param)."""
+        p = GroundFrontierParam()
+        p.clearance_sq, p.min_size, p.connectivity, p.max_clusters = int(clearance_sq), int(min_size), int(connectivity), int(max_clusters)
+        return p
+
+    def ground_frontier_compute(self, clearance_sq=0, min_size=1, connectivity=8, max_clusters=256):
+        """Connected components (connectivity 4 or 8) of the current ground field's FNT cells with clearance_sq, those of at least
+        min_size cells kept: (n_clusters, n_cells) (synchronises).  n_clusters counts every kept component, also beyond max_clusters."""
+        p = self.ground_frontier_param(clearance_sq, min_size, connectivity, max_clusters)
+        nc, nv = C.c_int32(0), C.c_int32(0)
+        self._chk(self._f["ground_frontier_compute"](self._h, C.byref(p), C.byref(nc), C.byref(nv)))
+        self._ground_frontier_cap = p.max_clusters            # (what the readers' buffers hold)
+        return nc.value, nv.value
+
+    def ground_frontier_compute_dev(self, clearance_sq=0, min_size=1, connectivity=8, max_clusters=256, d_counts=0):
+        """The same on the mapper's stream without a host wait; d_counts: 2 int32 in a DEVICE buffer (raw address; 0 = not wanted)."""
+        p = self.ground_frontier_param(clearance_sq, min_size, connectivity, max_clusters)
+        self._chk(self._f["ground_frontier_compute_dev"](self._h, C.byref(p), C.c_void_p(d_counts or None)))
+        self._ground_frontier_cap = p.max_clusters
+
+    def read_ground_frontier_clusters(self):
+        """(records, goal_xy, n_clusters): the records produced (GROUND_FRONTIER_CLUSTER_DTYPE, ascending label; at most the
+        compute's max_clusters), the goal array [max_clusters, 2] float32 metres (NaN beyond the records) and the number of kept
+        components (synchronises)."""
+        cap = getattr(self, "_ground_frontier_cap", 0)
+        rec = np.zeros(max(cap, 1), GROUND_FRONTIER_CLUSTER_DTYPE)
+        goal = np.zeros((max(cap, 1), 2), np.float32)
+        n = C.c_int32(0)
+        self._chk(self._f["read_ground_frontier_clusters"](self._h, _ptr(rec), _ptr(goal), C.byref(n)))
+        return rec[:min(n.value, cap)], goal[:cap], n.value
+
+    def read_ground_frontier_clusters_dev(self, d_out, d_goal_xy, d_n_clusters):
+        """Records (max_clusters x 64 bytes), goal points (max_clusters x 2 float32) and the count (int32) into DEVICE buffers
+        (raw addresses; 0 = not wanted, not both of the first two), asynchronous on the mapper's stream."""
+        self._chk(self._f["read_ground_frontier_clusters_dev"](self._h, C.c_void_p(d_out or None), C.c_void_p(d_goal_xy or None),
+                                                               C.c_void_p(d_n_clusters or None)))
+
+    def read_ground_frontier_labels(self):
+        """int32 label plane [Y][X]: -1 not a member, -2 member of a filtered component, otherwise the label (synchronises)."""
+        out = np.empty((self.size[1], self.size[0]), np.int32)
+        self._chk(self._f["read_ground_frontier_labels"](self._h, _ptr(out)))
+        return out
+
+    def read_ground_frontier_labels_dev(self, d_labels):
+        """The label plane into a device buffer (X * Y int32, raw address), asynchronous on the mapper's stream."""
+        self._chk(self._f["read_ground_frontier_labels_dev"](self._h, C.c_void_p(d_labels or None)))
+
+    def ground_nf1_query(self, xy):
+        """The current ground navigation function at n points (n x 2 metres, world frame): int32 [n] steps, -1 outside the field,
+        for a point that is not finite and where no source is reachable (synchronises)."""
+        xy = np.ascontiguousarray(np.asarray(xy, dtype=np.float32).reshape(-1, 2))
+        out = np.zeros(xy.shape[0], np.int32)
+        self._chk(self._f["ground_nf1_query"](self._h, _ptr(xy) if len(xy) else None, len(xy), _ptr(out) if len(xy) else None))
+        return out
+
+    def ground_nf1_query_dev(self, d_xy, n, d_steps):
+        """n points (n x 2 float32) and their steps (n int32) in DEVICE buffers (raw addresses), on the mapper's stream."""
+        self._chk(self._f["ground_nf1_query_dev"](self._h, C.c_void_p(d_xy or None), int(n), C.c_void_p(d_steps or None)))
 
     def read_costmap_ground_nf1(self):
         """The one-layer TYPE_NF1 CostMap of the ground navigation function: (SeenDist payload [Y][X], header) (synchronises)."""

@@ -657,6 +657,68 @@ public:
     }
     gie_shortcut_info ground_waypoints_info = { 0, 0, 0.f, 0 };   /* of the last ground_waypoints() */
 
+#ifdef GIE_HOST_HAS_HIP
+    /* A ground robot's goal selection on the map as it stands (include/gie.h "ground frontier clusters"): which frontiers exist, how
+     * large they are, where to drive for each and how far that is.  Four steps chained through the _dev forms on the mapper's
+     * stream, with one device buffer and ONE sync (exploration_costs' pattern; the host learns no count in between):
+     *   the ground field of the band, exactly as ground_costmap() and ground_plan() set it up;
+     *   its frontier clusters at ground_clearance_sq(), connectivity 8, of at least min_size cells;
+     *   the ground navigation function whose one goal is the robot's position of the last publishMap (NF1 is symmetric);
+     *   that field gathered at the clusters' goals.
+     * clusters: the records in ascending label order, min(kept, max_clusters) of them; steps[i] = the 4-connected route length in
+     * cells from the robot to clusters[i].rep, -1 for a cluster the robot cannot reach — and for ALL clusters when the robot's own
+     * cell is not traversable (outside the field, not FREE or FNT, or closer than the clearance to an obstacle column): the field
+     * then has no source.  ground_goals_kept = the number of kept components (which may exceed max_clusters), ground_goals_cells =
+     * their members; ground_counts as by ground_costmap().  Returns false, and leaves everything alone, while the band is not set. */
+    bool ground_exploration_goals(int max_clusters, int min_size, std::vector<gie_ground_frontier_cluster> &clusters, std::vector<int32_t> &steps)
+    {
+        if (param.ground_max_height < param.ground_min_height) return false;
+        if (max_clusters < 0) throw std::invalid_argument("ground_exploration_goals: max_clusters >= 0");
+        const size_t cap = (size_t)max_clusters, off_goal = cap * sizeof(gie_ground_frontier_cluster), off_robot = off_goal + cap * 8, off_steps = off_robot + 8,
+                     off_counts = off_steps + cap * 4, off_ground = off_counts + 8, bytes = off_ground + 16;
+        if (bytes > explore_cap_) {
+            if (explore_dev_) (void)hipFree(explore_dev_);
+            explore_dev_ = nullptr; explore_cap_ = 0;
+            if (hipMalloc(&explore_dev_, bytes) != hipSuccess) throw std::runtime_error("ground_exploration_goals: device allocation failed");
+            explore_cap_ = bytes;
+        }
+        void *stream = nullptr;
+        chk(gie_get_stream(m_, &stream));
+        char *d = static_cast<char *>(explore_dev_);
+        explore_host_.resize(bytes);
+        if (hipMemcpyAsync(d + off_robot, robot_pos_, 8, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess) throw std::runtime_error("ground_exploration_goals: copy failed");
+        const float w = cfg_.voxel_width;
+        gie_ground_param g = {};
+        g.z_lo = (int32_t)std::floor(param.ground_min_height / w + 0.5f);      /* as ground_costmap() */
+        g.z_hi = (int32_t)std::floor(param.ground_max_height / w + 0.5f);
+        g.min_known = param.ground_min_known;
+        chk(gie_ground_compute_dev(m_, &g, reinterpret_cast<int32_t *>(d + off_ground)));
+        gie_ground_frontier_param fp = {};
+        fp.clearance_sq = ground_clearance_sq(); fp.min_size = min_size; fp.connectivity = 8; fp.max_clusters = max_clusters;
+        chk(gie_ground_frontier_compute_dev(m_, &fp, reinterpret_cast<int32_t *>(d + off_counts)));
+        float *d_goal = reinterpret_cast<float *>(d + off_goal);
+        if (max_clusters > 0) chk(gie_read_ground_frontier_clusters_dev(m_, reinterpret_cast<gie_ground_frontier_cluster *>(d), d_goal, nullptr));
+        gie_ground_nf1_param np = {};
+        np.clearance_sq = fp.clearance_sq;
+        chk(gie_ground_nf1_compute_dev(m_, reinterpret_cast<const float *>(d + off_robot), 1, &np, nullptr));
+        chk(gie_ground_nf1_query_dev(m_, d_goal, max_clusters, reinterpret_cast<int32_t *>(d + off_steps)));
+        if (hipMemcpyAsync(explore_host_.data(), d, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess) throw std::runtime_error("ground_exploration_goals: copy failed");
+        chk(gie_sync(m_));
+        int32_t counts[2];
+        std::memcpy(counts, explore_host_.data() + off_counts, 8);
+        std::memcpy(ground_counts, explore_host_.data() + off_ground, 16);
+        ground_goals_kept = counts[0]; ground_goals_cells = counts[1];
+        const size_t have = std::min<size_t>((size_t)counts[0], cap);
+        clusters.resize(have); steps.resize(have);
+        if (have) {
+            std::memcpy(clusters.data(), explore_host_.data(), have * sizeof(gie_ground_frontier_cluster));
+            std::memcpy(steps.data(), explore_host_.data() + off_steps, have * 4);
+        }
+        return true;
+    }
+    int32_t ground_goals_kept = 0, ground_goals_cells = 0;     /* of the last ground_exploration_goals() */
+#endif
+
     /* VOLMAPNODE::visualize without the publishers: the clouds the display flags ask for (the others come back empty), of the map as
      * it stands.  sensor_pos is the reference's argument: its z is replaced by vis_height before the slice's z is taken
      * (volumetric_mapper.h:339-341), so only vis_height decides.  The local clouds always come from the device (gie_cloud_local);

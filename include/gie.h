@@ -860,6 +860,99 @@ int gie_ground_shortcut(gie_mapper *h, const int32_t *path_xy, const int32_t *le
 int gie_ground_shortcut_dev(gie_mapper *h, const int32_t *d_path_xy, const int32_t *d_len, int n, int max_len,
                             const gie_ground_shortcut_param *p, gie_ground_waypoint *d_wp, gie_shortcut_info *d_info);
 
+/* ---- ground frontier clusters: the connected components of the ground field's FNT cells, filtered by size, each with a goal a
+ * ground robot can drive to, and the route length from the robot to each of them — the goal selection of an exploration loop
+ * ("which frontiers exist, how large are they, where do I drive for each, how far is it").  "frontier clusters" above does not
+ * serve a ground robot for the reason the ground costmap exists: in the volume the floor is an obstacle one voxel away
+ * everywhere, so FNT voxels at floor level fail every useful clearance, and the 3-D components are sheets, not the 2-D arcs a
+ * ground planner reasons about.  No counterpart in the reference's code.
+ *
+ * Everything is over the ground field that is valid where gie_ground_frontier_compute* is enqueued: type(c), dist_sq(c) and the
+ * pivot are that field's (gie_read_ground*).  id(c) = y * X + x is the local cell index.  Every value is an integer and exact; the
+ * floats are derived from the integers in the order of operations stated here.  w = voxel_width.
+ *  member(c)     type(c) == GIE_VOX_FNT, and dist_sq(c) == -1 or dist_sq(c) >= clearance_sq (squared cells): the ground navigation
+ *                function's traversable rule restricted to FNT cells, so with equal clearance_sq every member is a legal source or
+ *                goal of gie_ground_nf1_compute.
+ *  adjacent      two distinct members that differ by at most 1 in x and in y (connectivity = 8), or that are edge neighbours
+ *                (connectivity = 4).  Any other value: GIE_ERR_INVALID.
+ *  component     a class of the transitive closure of `adjacent` inside the rectangle.  Its label is the smallest id of its members,
+ *                its size the number of members.  Both are independent of any schedule.
+ *  kept          size >= min_size: the noise filter.
+ *  label plane   X * Y int32, x fastest: -1 not a member; -2 member of a component that is not kept; otherwise the label.
+ *  cluster record  one gie_ground_frontier_cluster per kept component, in ascending order of label.
+ *                centroid_k = ((float)((double)sum_k / (double)size) + (float)pvt_k) * w, in this order of operations.
+ *                rep: with c_k = (2 * sum_k + size) / (2 * size) (integer division: the centroid rounded half up to a cell), the
+ *                member that minimises |v - c|^2 (integers), ties to the smaller id.  The centroid of an arc is usually not a
+ *                member and may lie in an obstacle column; rep always is a member.  rep_dist_sq = dist_sq(rep), the value
+ *                gie_read_ground returns (-1 on a field without an obstacle column): the room the robot has at its goal.
+ *                These are the rules of "frontier clusters" in two dimensions.
+ *  capacity      n_clusters is the number of KEPT components even when it exceeds max_clusters; only the first max_clusters
+ *                records (ascending label) are produced.  n_cells = members in kept components.  The label plane is complete
+ *                whatever the capacity.  d_counts (device, 2 int32, may be NULL) = { n_clusters, n_cells }; n_clusters / n_cells
+ *                of the host form may be NULL.
+ *  readers       gie_read_ground_frontier_clusters*: out and goal_xy hold max_clusters (of the compute) entries, either may be
+ *                NULL, not both.  out: the records produced; entries beyond them are left as they are.  goal_xy (2 floats per
+ *                entry): (float)rep_k * w for the records produced, NaN for the rest — so the whole array can be handed to
+ *                gie_ground_nf1_compute_dev and gie_ground_nf1_query_dev with n = max_clusters without the host ever learning the
+ *                count (both ignore points that are not finite).  gie_pos2coord((float)rep_k * w, w) = floorf(p / w + 0.5f) gives
+ *                rep_k back while |rep_k| < 2^20: product and quotient are each off by at most a few ulp of a value below 2^20
+ *                (3 * 2^-4 of a cell in all), inside the half-cell margin.  *n_clusters as the compute's (may be NULL).
+ *                gie_read_ground_frontier_labels*: the label plane.
+ *  gie_ground_nf1_query*  for each of n points (metres, world frame, two floats each): its cell by gie_ground_query's mapping,
+ *                gie_pos2coord(p_k, w) - pvt_k; steps = the value of the current ground navigation function at that cell, -1 for a
+ *                point outside the rectangle or not finite.  n == 0 is valid.  Refused exactly where gie_read_ground_nf1* is: no
+ *                field yet, or the field invalidated by a later gie_ground_compute*.  Ground NF1 is symmetric: ONE field whose
+ *                only goal is the robot, gathered at the clusters' goal array, gives the route length from the robot to every
+ *                cluster (-1: not reachable, or the NaN tail of the array) — instead of one compute per candidate goal.
+ * Lifetime: the clusters are kept until the next gie_ground_frontier_compute* and refer to the ground field's pivot; a map update
+ *  does not touch them.  A later gie_ground_compute* invalidates them (one flag, as for the ground navigation function): the three
+ *  readers then return GIE_ERR_INVALID until the next gie_ground_frontier_compute*.
+ * GIE_ERR_INVALID, nothing written: a NULL handle or param; clearance_sq < 0; min_size < 1; a connectivity other than 4 and 8;
+ *  max_clusters < 0; non-zero flags or reserved; a compute before a ground field exists; a reader before the first compute or after
+ *  an invalidation; both outputs of the cluster reader NULL; a NULL plane in the label readers; n < 0, or n > 0 with a NULL array;
+ *  a tiled mapper (all eight refuse, as every planner section does).
+ * The host forms synchronise; the _dev forms take DEVICE buffers and are enqueued on the mapper's stream (gie_get_stream) with no
+ *  host wait and no read-back.
+ * Memory: a mapper that never calls the section allocates and launches nothing.  The first compute allocates per CELL (gie_dalloc,
+ *  freed by gie_destroy): the union-find forest and the sizes (8 bytes), two bit planes with rows padded to 64-bit words — members,
+ *  kept roots — and 8 bytes per such word (0.375 bytes per cell when X is a multiple of 64): 2.2 MB for 512 x 512; and 64 bytes per
+ *  record of the largest max_clusters asked for.
+ * Cost: a compute is one memset and a fixed sequence of about a dozen launches whatever the data (three fewer with max_clusters == 0),
+ *  none with a grid barrier: it does not join the chain of grid-barrier launches and has no timeout path; no loop of the host's, no
+ *  read-back.  The member plane is one pass over the ground field's type and dist_sq (5 bytes per cell); everything after it works
+ *  on 64-bit words of that plane.  The statistics are integer atomics, one set per (64 x 64 tile, component) and not per member
+ *  or run, so a result is bit-identical from run to run and one large component is no hot spot.  The gather is one launch, a lane
+ *  per point.
+ * gie_profile_read: "ground_frontier" = the compute and the three readers, the entry directly in front of "ground_nf1"; it is
+ *  listed once the mapper has called gie_ground_frontier_compute* — the profile of a mapper that never calls the section is the
+ *  list as it was.  The gather is counted under "ground_nf1". */
+typedef struct gie_ground_frontier_cluster {   /* 64 bytes */
+    int32_t label;          /* smallest local cell index y * X + x of a member */
+    int32_t size;
+    int32_t lo[2], hi[2];   /* bounding box, GLOBAL x, y (local + pivot), both inclusive */
+    int32_t rep[2];         /* representative member, GLOBAL x, y */
+    float   centroid[2];    /* metres, world frame */
+    int64_t sum[2];         /* sums of the members' LOCAL x, y  (offset 40) */
+    int32_t rep_dist_sq;    /* the ground field's dist_sq at rep (-1: no obstacle column) */
+    int32_t reserved;       /* 0 */
+} gie_ground_frontier_cluster;
+typedef struct gie_ground_frontier_param {     /* 32 bytes */
+    int32_t clearance_sq;   /* >= 0, squared cells */
+    int32_t min_size;       /* >= 1 */
+    int32_t connectivity;   /* 4 or 8 */
+    int32_t max_clusters;   /* >= 0 */
+    int32_t flags;          /* 0 */
+    int32_t reserved[3];    /* 0 */
+} gie_ground_frontier_param;
+int gie_ground_frontier_compute(gie_mapper *h, const gie_ground_frontier_param *p, int32_t *n_clusters, int32_t *n_cells);
+int gie_ground_frontier_compute_dev(gie_mapper *h, const gie_ground_frontier_param *p, int32_t *d_counts);   /* {n_clusters, n_cells}, may be NULL */
+int gie_read_ground_frontier_clusters(gie_mapper *h, gie_ground_frontier_cluster *out, float *goal_xy, int32_t *n_clusters);
+int gie_read_ground_frontier_clusters_dev(gie_mapper *h, gie_ground_frontier_cluster *d_out, float *d_goal_xy, int32_t *d_n_clusters);
+int gie_read_ground_frontier_labels(gie_mapper *h, int32_t *labels);
+int gie_read_ground_frontier_labels_dev(gie_mapper *h, int32_t *d_labels);
+int gie_ground_nf1_query(gie_mapper *h, const float *xy, int n, int32_t *steps);
+int gie_ground_nf1_query_dev(gie_mapper *h, const float *d_xy, int n, int32_t *d_steps);
+
 /* ---- goal-to-goal cost matrix: the path lengths among up to 64 points (the robot and the goals of the frontier clusters, say), the
  * input of every tour-based explorer — in which order to visit the clusters.  n fields of gie_nf1_compute would give the same
  * numbers with n persistent launches and n whole fields; here ONE level-synchronous pass advances all searches, a 64-bit mask per
