@@ -117,6 +117,12 @@ struct gie_costmat_cache {
     uint64_t *trav = nullptr;             /* the traversable bit plane */
     int32_t *words = nullptr;             /* control words, tile stamps, two tile lists */
 };
+/* the ground cost matrix (gie_ground_costmat.inc.h): scratch only, allocated at the first compute; no result is kept */
+struct gie_gcm_cache {
+    uint64_t *blk0 = nullptr;             /* the blocked bit plane, rebuilt by every call */
+    uint64_t *planes = nullptr;           /* fields beyond the LDS budget: two bit planes per source, planes_n sources */
+    int planes_n = 0;
+};
 struct gie_mapper {
     gie_config cfg;
     gie_ctx c;
@@ -158,6 +164,7 @@ struct gie_mapper {
     gie_gnf1_cache gnf1;                  /* the ground navigation function (HIP backend: gie_ground_nf1.inc.h) */
     uint64_t *glos_blk = nullptr;         /* ground line of sight (HIP backend: gie_ground_los.inc.h): the blocked bit plane, allocated at the first call and rebuilt by every call */
     gie_gfr_cache gfr;                    /* the ground frontier clusters (HIP backend: gie_ground_frontier.inc.h) */
+    gie_gcm_cache gcm;                    /* the ground cost matrix's scratch (HIP backend: gie_ground_costmat.inc.h) */
     gie_costmat_cache costmat;            /* the cost matrix's scratch (HIP backend: gie_costmat.inc.h) */
     int32_t *cloud_count = nullptr;       /* display clouds (HIP backend: gie_cloud.inc.h): the counter of a _dev call that passes none, allocated at the first such call */
 };

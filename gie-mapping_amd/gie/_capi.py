@@ -348,6 +348,9 @@ DEVICE_ONLY = {
     "read_ground_frontier_labels_dev": (C.c_int, [_H, C.c_void_p]),
     "ground_nf1_query": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p]),
     "ground_nf1_query_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p]),
+    # ground cost matrix: route lengths among points on the ground costmap (include/gie.h): device library only
+    "ground_costmat_compute": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(GroundNf1Param), C.c_void_p, C.c_void_p]),
+    "ground_costmat_compute_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(GroundNf1Param), C.c_void_p, C.c_void_p]),
     # goal-to-goal cost matrix of the local volume (include/gie.h): device library only
     "costmat_compute": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(Nf1Param), C.c_void_p, C.c_void_p]),
     "costmat_compute_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(Nf1Param), C.c_void_p, C.c_void_p]),

@@ -1009,6 +1009,26 @@ class Mapper(MapperBase):
         """n points (n x 2 float32) and their steps (n int32) in DEVICE buffers (raw addresses), on the mapper's stream."""
         self._chk(self._f["ground_nf1_query_dev"](self._h, C.c_void_p(d_xy or None), int(n), C.c_void_p(d_steps or None)))
 
+    # --- ground cost matrix: route lengths among points on the ground costmap (include/gie.h) -----
+    def ground_costmat(self, points, clearance_sq=0, unknown_traversable=False):
+        """4-connected route lengths among n <= 256 points (n x 2 metres, world frame) over the current ground field, clearance_sq
+        in squared CELLS (as ground_nf1_param): (cost [n, n] int32, valid [n] bool) (synchronises)."""
+        xy = np.ascontiguousarray(np.asarray(points, dtype=np.float32).reshape(-1, 2))
+        n = xy.shape[0]
+        p = self.ground_nf1_param(clearance_sq, unknown_traversable)
+        cost = np.empty((n, n), np.int32)
+        valid = np.zeros(n, np.uint8)
+        self._chk(self._f["ground_costmat_compute"](self._h, _ptr(xy) if n else None, n, C.byref(p), _ptr(cost) if n else None,
+                                                    _ptr(valid) if n else None))
+        return cost, valid.astype(bool)
+
+    def ground_costmat_dev(self, d_points, n, d_cost, d_valid=0, clearance_sq=0, unknown_traversable=False):
+        """The same with points (n x 2 float32), the matrix (n x n int32) and valid (n uint8; 0 = not wanted) in DEVICE buffers
+        (raw addresses), on the mapper's stream; the host does not wait."""
+        p = self.ground_nf1_param(clearance_sq, unknown_traversable)
+        self._chk(self._f["ground_costmat_compute_dev"](self._h, C.c_void_p(d_points or None), int(n), C.byref(p), C.c_void_p(d_cost or None),
+                                                        C.c_void_p(d_valid or None)))
+
     def read_costmap_ground_nf1(self):
         """The one-layer TYPE_NF1 CostMap of the ground navigation function: (SeenDist payload [Y][X], header) (synchronises)."""
         pay = np.empty((self.size[1], self.size[0]), SEENDIST_DTYPE)

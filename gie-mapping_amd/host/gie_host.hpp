@@ -717,6 +717,58 @@ public:
         return true;
     }
     int32_t ground_goals_kept = 0, ground_goals_cells = 0;     /* of the last ground_exploration_goals() */
+
+    /* What a ground robot's tour planner needs to order the frontier clusters (include/gie.h "ground cost matrix"): the 4-connected
+     * route lengths in cells, at ground_clearance_sq(), among the robot (point 0: the position of the last publishMap) and the goals
+     * of at most max_clusters (<= 255) ground frontier clusters of at least min_size cells (connectivity 8).  ground_exploration_goals'
+     * chain with exploration_costs' pattern: the ground field of the band, its frontier clusters, their goals into one device buffer
+     * directly behind the robot's position, the matrix of that buffer — ONE copy back and ONE sync; the host learns no count in
+     * between.
+     *   goals  2 * (max_clusters + 1) floats, metres: the robot, then the goals in ascending label order, NaN beyond the clusters;
+     *   cost   (max_clusters + 1)^2, row-major: -1 for a NaN entry, a goal the robot cannot reach, or a robot whose own cell is not
+     *          traversable (row and column 0 are then all -1).
+     * ground_goals_kept, ground_goals_cells and ground_counts are set as by ground_exploration_goals().  Returns false, and leaves
+     * everything alone, while the band is not set. */
+    bool ground_exploration_costs(int max_clusters, int min_size, std::vector<int32_t> &cost, std::vector<float> &goals)
+    {
+        if (param.ground_max_height < param.ground_min_height) return false;
+        if (max_clusters < 0 || max_clusters + 1 > GIE_GROUND_COSTMAT_MAX_POINTS) throw std::invalid_argument("ground_exploration_costs: 0 <= max_clusters <= 255");
+        const size_t n = (size_t)max_clusters + 1, off_cost = n * 8, off_counts = off_cost + n * n * 4, off_ground = off_counts + 8, bytes = off_ground + 16;
+        if (bytes > explore_cap_) {
+            if (explore_dev_) (void)hipFree(explore_dev_);
+            explore_dev_ = nullptr; explore_cap_ = 0;
+            if (hipMalloc(&explore_dev_, bytes) != hipSuccess) throw std::runtime_error("ground_exploration_costs: device allocation failed");
+            explore_cap_ = bytes;
+        }
+        void *stream = nullptr;
+        chk(gie_get_stream(m_, &stream));
+        char *d = static_cast<char *>(explore_dev_);
+        explore_host_.resize(bytes);
+        if (hipMemcpyAsync(d, robot_pos_, 8, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess) throw std::runtime_error("ground_exploration_costs: copy failed");
+        const float w = cfg_.voxel_width;
+        gie_ground_param g = {};
+        g.z_lo = (int32_t)std::floor(param.ground_min_height / w + 0.5f);      /* as ground_costmap() */
+        g.z_hi = (int32_t)std::floor(param.ground_max_height / w + 0.5f);
+        g.min_known = param.ground_min_known;
+        chk(gie_ground_compute_dev(m_, &g, reinterpret_cast<int32_t *>(d + off_ground)));
+        gie_ground_frontier_param fp = {};
+        fp.clearance_sq = ground_clearance_sq(); fp.min_size = min_size; fp.connectivity = 8; fp.max_clusters = max_clusters;
+        chk(gie_ground_frontier_compute_dev(m_, &fp, reinterpret_cast<int32_t *>(d + off_counts)));
+        if (max_clusters > 0) chk(gie_read_ground_frontier_clusters_dev(m_, nullptr, reinterpret_cast<float *>(d) + 2, nullptr));
+        gie_ground_nf1_param np = {};
+        np.clearance_sq = fp.clearance_sq;
+        chk(gie_ground_costmat_compute_dev(m_, reinterpret_cast<const float *>(d), (int)n, &np, reinterpret_cast<int32_t *>(d + off_cost), nullptr));
+        if (hipMemcpyAsync(explore_host_.data(), d, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess) throw std::runtime_error("ground_exploration_costs: copy failed");
+        chk(gie_sync(m_));
+        goals.resize(2 * n); cost.resize(n * n);
+        std::memcpy(goals.data(), explore_host_.data(), off_cost);
+        std::memcpy(cost.data(), explore_host_.data() + off_cost, n * n * 4);
+        int32_t counts[2];
+        std::memcpy(counts, explore_host_.data() + off_counts, 8);
+        std::memcpy(ground_counts, explore_host_.data() + off_ground, 16);
+        ground_goals_kept = counts[0]; ground_goals_cells = counts[1];
+        return true;
+    }
 #endif
 
     /* VOLMAPNODE::visualize without the publishers: the clouds the display flags ask for (the others come back empty), of the map as

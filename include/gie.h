@@ -953,6 +953,54 @@ int gie_read_ground_frontier_labels_dev(gie_mapper *h, int32_t *d_labels);
 int gie_ground_nf1_query(gie_mapper *h, const float *xy, int n, int32_t *steps);
 int gie_ground_nf1_query_dev(gie_mapper *h, const float *d_xy, int n, int32_t *d_steps);
 
+/* ---- ground cost matrix: the route lengths among up to 256 points on the ground costmap (the robot and the goals of the ground
+ * frontier clusters, say) — the input of every tour-based explorer of a ground robot: in which order to visit the clusters.  It is
+ * "cost matrix" below in two dimensions, on the ground navigation function's rules; that section does not serve a ground robot for
+ * the reason the ground costmap exists.  n calls of gie_ground_nf1_compute* and gie_ground_nf1_query* would give the same numbers
+ * one after the other, each on one compute unit, and each would overwrite the ONE ground navigation function the robot's own plan
+ * needs; here the n searches are the n workgroups of one launch and no field is written.  No counterpart in the reference's code.
+ *
+ * Everything is over the ground field that is valid where gie_ground_costmat_compute* is enqueued: type(c), dist_sq(c) and the pivot
+ * are that field's (gie_read_ground*).  Every value is an integer and exact.  w = voxel_width.
+ *  traversable(c)  the ground navigation function's rule with this call's clearance_sq (squared cells): type(c) is FREE or FNT (or
+ *                  UNKNOWN, with GIE_GROUND_NF1_UNKNOWN_TRAVERSABLE), and dist_sq(c) == -1 or dist_sq(c) >= clearance_sq.
+ *                  GIE_GROUND_NF1_UNKNOWN_TRAVERSABLE is the only legal flag: GIE_GROUND_NF1_FROM_FRONTIERS has no meaning here
+ *                  and is GIE_ERR_INVALID.
+ *  cell(i)         of point i (metres, world frame, two floats), gie_ground_query's mapping: gie_pos2coord(p_k, w) - pvt_k.  The
+ *                  point is VALID when it is finite, inside the rectangle and its cell traversable.  valid[i] = 1 or 0 (valid may
+ *                  be NULL).
+ *  cost            n x n int32, row-major.  cost[i][j] = the number of steps of the shortest 4-connected path from cell(i) to
+ *                  cell(j) whose every cell is traversable and inside the rectangle; 0 when the cells coincide (i = j included);
+ *                  -1 when either point is invalid or there is no such path.  The matrix is symmetric, the rows and columns of
+ *                  invalid points are all -1, two points on one cell have identical rows.  By definition cost[i][j] is what
+ *                  gie_ground_nf1_query returns at point i on the field gie_ground_nf1_compute gives for the single goal j with
+ *                  the same clearance_sq and flags.
+ * Arguments: 0 <= n <= GIE_GROUND_COSTMAT_MAX_POINTS; n == 0 is valid, writes nothing and launches nothing.
+ * GIE_ERR_INVALID, nothing written: a NULL handle; a tiled mapper (as every planner section: the searches would stop at the tile's
+ *  faces); a call before a ground field exists; a NULL p; clearance_sq < 0; an unknown flag, or GIE_GROUND_NF1_FROM_FRONTIERS;
+ *  non-zero reserved; n outside the range; n > 0 with a NULL xy or cost.
+ * The goal array gie_read_ground_frontier_clusters_dev writes (NaN in its unused entries) can stand behind a robot position in one
+ *  buffer and be handed over as it is: max_clusters + 1 points, the NaN ones invalid.  The host never learns a count.
+ * State: nothing is kept for later readers; the result is complete when the call's work is done.  The call neither reads, writes nor
+ *  invalidates the current ground navigation function or the ground frontier clusters, and a map update does not touch it.
+ * The host form stages through the export buffers and synchronises.  The _dev form takes DEVICE buffers and is enqueued on the
+ *  mapper's stream (gie_get_stream) with no host wait and no read-back.
+ * Propagation: one launch of n workgroups of 1024 threads, workgroup i the whole search from point i: the ground navigation
+ *  function's level loop on three bit planes in the LDS of one compute unit (144 KiB: one workgroup per compute unit, 256 points
+ *  occupy the chip once), one workgroup barrier per level, without the stores of a field: a search only notes the level at which
+ *  the other points' bits enter its frontier.  It ends when a level adds nothing, or one level after its last valid target was
+ *  found; the matrix is the same either way.  A field beyond the LDS budget (ceil(X/64) * Y > 6144 words, 1024 x 1024 say) runs the
+ *  same loop with two of the planes in global memory, a pair PER SOURCE, and two barriers per level.  No grid barrier and no
+ *  co-residency: the launch does not join the chain of grid-barrier launches and has no timeout path; the level count is bounded
+ *  by X * Y.  Only integers, no atomics, a row is written by one workgroup only: a result is bit-identical from run to run.
+ * Memory: a mapper that never calls the section allocates and launches nothing.  The first call allocates one bit plane with rows
+ *  padded to 64-bit words (gie_dalloc, freed by gie_destroy; 32 KiB for 512 x 512); the first call on a field beyond the LDS budget
+ *  two such planes per point, for the largest n asked for (64 MiB for 1024 x 1024 and 256 points).
+ * gie_profile_read: counted under "ground_nf1"; no entry of its own. */
+#define GIE_GROUND_COSTMAT_MAX_POINTS 256
+int gie_ground_costmat_compute(gie_mapper *h, const float *xy, int n, const gie_ground_nf1_param *p, int32_t *cost, uint8_t *valid);
+int gie_ground_costmat_compute_dev(gie_mapper *h, const float *d_xy, int n, const gie_ground_nf1_param *p, int32_t *d_cost, uint8_t *d_valid);
+
 /* ---- goal-to-goal cost matrix: the path lengths among up to 64 points (the robot and the goals of the frontier clusters, say), the
  * input of every tour-based explorer — in which order to visit the clusters.  n fields of gie_nf1_compute would give the same
  * numbers with n persistent launches and n whole fields; here ONE level-synchronous pass advances all searches, a 64-bit mask per
