@@ -165,6 +165,7 @@ struct gie_mapper {
     uint64_t *glos_blk = nullptr;         /* ground line of sight (HIP backend: gie_ground_los.inc.h): the blocked bit plane, allocated at the first call and rebuilt by every call */
     gie_gfr_cache gfr;                    /* the ground frontier clusters (HIP backend: gie_ground_frontier.inc.h) */
     gie_gcm_cache gcm;                    /* the ground cost matrix's scratch (HIP backend: gie_ground_costmat.inc.h) */
+    uint64_t *gview_opq = nullptr;        /* ground view gain (HIP backend: gie_ground_view.inc.h): the opaque bit plane, allocated at the first call and rebuilt by every call */
     gie_costmat_cache costmat;            /* the cost matrix's scratch (HIP backend: gie_costmat.inc.h) */
     int32_t *cloud_count = nullptr;       /* display clouds (HIP backend: gie_cloud.inc.h): the counter of a _dev call that passes none, allocated at the first such call */
 };

@@ -157,6 +157,11 @@ class GroundWaypoint(C.Structure):
     _fields_ = [("xy", C.c_int32 * 2), ("index", C.c_int32), ("min_dist_sq", C.c_int32), ("forced", C.c_int32), ("reserved", C.c_int32)]
 
 
+class GroundViewParam(C.Structure):
+    """gie_ground_view_param (include/gie.h): 32 bytes; ranges in metres."""
+    _fields_ = [("r_min", C.c_float), ("r_max", C.c_float), ("n_planes", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
 class GroundFrontierParam(C.Structure):
     """gie_ground_frontier_param (include/gie.h): 32 bytes; clearance_sq in squared cells."""
     _fields_ = [("clearance_sq", C.c_int32), ("min_size", C.c_int32), ("connectivity", C.c_int32), ("max_clusters", C.c_int32),
@@ -170,6 +175,7 @@ class GroundFrontierCluster(C.Structure):
 
 
 assert C.sizeof(GroundFrontierParam) == 32 and C.sizeof(GroundFrontierCluster) == 64 and GroundFrontierCluster.sum.offset == 40
+assert C.sizeof(GroundViewParam) == 32 and GroundViewParam.n_planes.offset == 8 and GroundViewParam.reserved.offset == 16
 assert C.sizeof(GroundLosParam) == 16 and C.sizeof(GroundHit) == 24 and C.sizeof(GroundShortcutParam) == 32 and C.sizeof(GroundWaypoint) == 24
 assert C.sizeof(GroundParam) == 32 and C.sizeof(GroundCell) == 16 and C.sizeof(GroundNf1Param) == 32
 assert C.sizeof(CloudParam) == 32 and C.sizeof(CloudPoint) == 16
@@ -185,6 +191,8 @@ GROUND_UNKNOWN_BLOCKS = 1
 GROUND_NF1_UNKNOWN_TRAVERSABLE = 1
 GROUND_NF1_FROM_FRONTIERS = 2
 GROUND_LOS_UNKNOWN_TRAVERSABLE = 1
+GROUND_VIEW_UNKNOWN_OPAQUE = 1
+GROUND_VIEW_UNION = 2
 VOX_UNKNOWN, VOX_FREE, VOX_OCCUPIED, VOX_FNT = 0, 1, 2, 3
 
 
@@ -351,6 +359,11 @@ DEVICE_ONLY = {
     # ground cost matrix: route lengths among points on the ground costmap (include/gie.h): device library only
     "ground_costmat_compute": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(GroundNf1Param), C.c_void_p, C.c_void_p]),
     "ground_costmat_compute_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(GroundNf1Param), C.c_void_p, C.c_void_p]),
+    # ground view gain: visible cells per candidate pose on the ground costmap (include/gie.h): device library only
+    "ground_view_gain": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(GroundViewParam), C.c_void_p]),
+    "ground_view_gain_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(GroundViewParam), C.c_void_p]),
+    "ground_view_mask": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.POINTER(GroundViewParam), C.c_void_p, C.c_void_p]),
+    "ground_view_mask_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.POINTER(GroundViewParam), C.c_void_p, C.c_void_p]),
     # goal-to-goal cost matrix of the local volume (include/gie.h): device library only
     "costmat_compute": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(Nf1Param), C.c_void_p, C.c_void_p]),
     "costmat_compute_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(Nf1Param), C.c_void_p, C.c_void_p]),

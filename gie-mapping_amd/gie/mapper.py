@@ -13,8 +13,8 @@ import sys
 import numpy as np
 
 from . import _capi
-from ._capi import CLOUD_DIST, CLOUD_TYPE, GROUND_LOS_UNKNOWN_TRAVERSABLE, GROUND_NF1_FROM_FRONTIERS, GROUND_NF1_UNKNOWN_TRAVERSABLE, GROUND_UNKNOWN_BLOCKS, LOS_UNKNOWN_OPAQUE, NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE, VOX_FNT, VOX_FREE, VOX_OCCUPIED, VOX_UNKNOWN
-from ._capi import CamParam, CloudParam, Config, CostMapHdr, FrameStats, FrontierParam, GroundFrontierParam, GroundLosParam, GroundNf1Param, GroundParam, GroundShortcutParam, LosParam, MultiScanParam, Nf1Param, ScanParam, ShortcutParam, ViewParam, Voxel
+from ._capi import CLOUD_DIST, CLOUD_TYPE, GROUND_LOS_UNKNOWN_TRAVERSABLE, GROUND_NF1_FROM_FRONTIERS, GROUND_NF1_UNKNOWN_TRAVERSABLE, GROUND_UNKNOWN_BLOCKS, GROUND_VIEW_UNION, GROUND_VIEW_UNKNOWN_OPAQUE, LOS_UNKNOWN_OPAQUE, NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE, VOX_FNT, VOX_FREE, VOX_OCCUPIED, VOX_UNKNOWN
+from ._capi import CamParam, CloudParam, Config, CostMapHdr, FrameStats, FrontierParam, GroundFrontierParam, GroundLosParam, GroundNf1Param, GroundParam, GroundShortcutParam, GroundViewParam, LosParam, MultiScanParam, Nf1Param, ScanParam, ShortcutParam, ViewParam, Voxel
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG, "csrc", "libgie_hip.so")
@@ -1028,6 +1028,59 @@ class Mapper(MapperBase):
         p = self.ground_nf1_param(clearance_sq, unknown_traversable)
         self._chk(self._f["ground_costmat_compute_dev"](self._h, C.c_void_p(d_points or None), int(n), C.byref(p), C.c_void_p(d_cost or None),
                                                         C.c_void_p(d_valid or None)))
+
+    # --- ground view gain: visible cells per candidate pose on the ground costmap (include/gie.h) ---
+    def ground_view_param(self, r_min=0.0, r_max=1.0, n_planes=0, unknown_opaque=False, union=False):
+        """gie_ground_view_param: ranges in metres; n_planes half planes per view, `union` for a sector wider than 180 degrees."""
+        p = GroundViewParam()
+        p.r_min, p.r_max, p.n_planes = float(r_min), float(r_max), int(n_planes)
+        p.flags = (GROUND_VIEW_UNKNOWN_OPAQUE if unknown_opaque else 0) | (GROUND_VIEW_UNION if union else 0)
+        return p
+
+    @staticmethod
+    def _ground_view_arrays(who, xy, normals, n_planes):
+        xy = np.ascontiguousarray(np.asarray(xy, dtype=np.float32).reshape(-1, 2))
+        nr = None
+        if n_planes > 0:
+            nr = np.ascontiguousarray(np.asarray(normals, dtype=np.int32).reshape(-1, n_planes, 2))
+            if len(nr) != len(xy):
+                raise ValueError(who + ": n_planes normals per view")
+        return xy, nr
+
+    def ground_view_gain(self, xy, r_min=0.0, r_max=1.0, normals=None, n_planes=0, unknown_opaque=False, union=False):
+        """Scores of n views at points xy (n x 2 metres, world frame) over the current ground field, each cut by n_planes half planes
+        (normals: n x n_planes x 2 int32, x then y) -> VIEW_SCORE_DTYPE [n] (synchronises)."""
+        xy, nr = self._ground_view_arrays("ground_view_gain", xy, normals, int(n_planes))
+        n = len(xy)
+        out = np.zeros(n, VIEW_SCORE_DTYPE)
+        p = self.ground_view_param(r_min, r_max, n_planes, unknown_opaque, union)
+        self._chk(self._f["ground_view_gain"](self._h, _ptr(xy) if n else None, _ptr(nr) if nr is not None and n else None, n, C.byref(p),
+                                              _ptr(out) if n else None))
+        return out
+
+    def ground_view_gain_dev(self, d_xy, d_normals, n, d_out, r_min=0.0, r_max=1.0, n_planes=0, unknown_opaque=False, union=False):
+        """n views with points (n x 2 float32), normals (n x n_planes x 2 int32; 0 with n_planes == 0) and scores (n x 16 bytes) in
+        DEVICE buffers (raw addresses), on the mapper's stream."""
+        p = self.ground_view_param(r_min, r_max, n_planes, unknown_opaque, union)
+        self._chk(self._f["ground_view_gain_dev"](self._h, C.c_void_p(d_xy or None), C.c_void_p(d_normals or None), int(n), C.byref(p), C.c_void_p(d_out or None)))
+
+    def ground_view_mask(self, xy, r_min=0.0, r_max=1.0, normals=None, n_planes=0, unknown_opaque=False, union=False):
+        """One view: (mask uint8 [Y][X]: 0 not a candidate, 1 hidden, 2 visible; its VIEW_SCORE_DTYPE record) (synchronises)."""
+        xy, nr = self._ground_view_arrays("ground_view_mask", xy, normals, int(n_planes))
+        if len(xy) != 1:
+            raise ValueError("ground_view_mask: one view")
+        mask = np.zeros((self.size[1], self.size[0]), np.uint8)
+        score = np.zeros(1, VIEW_SCORE_DTYPE)
+        p = self.ground_view_param(r_min, r_max, n_planes, unknown_opaque, union)
+        self._chk(self._f["ground_view_mask"](self._h, _ptr(xy), _ptr(nr) if nr is not None else None, C.byref(p), _ptr(mask), _ptr(score)))
+        return mask, score[0]
+
+    def ground_view_mask_dev(self, d_xy, d_normals, d_mask, d_score=0, r_min=0.0, r_max=1.0, n_planes=0, unknown_opaque=False, union=False):
+        """The same with the point, the normals, the mask (X * Y bytes) and the score (16 bytes; 0 = not wanted) in DEVICE buffers
+        (raw addresses), on the mapper's stream."""
+        p = self.ground_view_param(r_min, r_max, n_planes, unknown_opaque, union)
+        self._chk(self._f["ground_view_mask_dev"](self._h, C.c_void_p(d_xy or None), C.c_void_p(d_normals or None), C.byref(p), C.c_void_p(d_mask or None),
+                                                  C.c_void_p(d_score or None)))
 
     def read_costmap_ground_nf1(self):
         """The one-layer TYPE_NF1 CostMap of the ground navigation function: (SeenDist payload [Y][X], header) (synchronises)."""

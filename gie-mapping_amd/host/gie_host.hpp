@@ -718,6 +718,65 @@ public:
     }
     int32_t ground_goals_kept = 0, ground_goals_cells = 0;     /* of the last ground_exploration_goals() */
 
+    /* Both halves of a ground explorer's utility in one chain (include/gie.h "ground view gain"): ground_exploration_goals()' four
+     * steps with gie_ground_view_gain_dev at the clusters' goal array appended on the stream — every cell within r_min .. r_max
+     * metres of a goal, in all directions (no half planes, UNKNOWN columns transparent).  Still one device buffer and ONE sync; the
+     * host learns no count in between (the NaN tail of the goal array scores -1 on the device and is cut off here).
+     * clusters and steps as by ground_exploration_goals(); scores[i] belongs to clusters[i]: the visible UNKNOWN / FNT / OCCUPIED
+     * columns around clusters[i].rep and the number of candidates.  ground_goals_kept, ground_goals_cells and ground_counts are set
+     * as there.  Returns false, and leaves everything alone, while the band is not set. */
+    bool ground_exploration_gains(int max_clusters, int min_size, float r_min, float r_max, std::vector<gie_ground_frontier_cluster> &clusters,
+                                  std::vector<int32_t> &steps, std::vector<gie_view_score> &scores)
+    {
+        if (param.ground_max_height < param.ground_min_height) return false;
+        if (max_clusters < 0) throw std::invalid_argument("ground_exploration_gains: max_clusters >= 0");
+        const size_t cap = (size_t)max_clusters, off_goal = cap * sizeof(gie_ground_frontier_cluster), off_robot = off_goal + cap * 8, off_steps = off_robot + 8,
+                     off_counts = off_steps + cap * 4, off_ground = off_counts + 8, off_scores = off_ground + 16, bytes = off_scores + cap * sizeof(gie_view_score);
+        if (bytes > explore_cap_) {
+            if (explore_dev_) (void)hipFree(explore_dev_);
+            explore_dev_ = nullptr; explore_cap_ = 0;
+            if (hipMalloc(&explore_dev_, bytes) != hipSuccess) throw std::runtime_error("ground_exploration_gains: device allocation failed");
+            explore_cap_ = bytes;
+        }
+        void *stream = nullptr;
+        chk(gie_get_stream(m_, &stream));
+        char *d = static_cast<char *>(explore_dev_);
+        explore_host_.resize(bytes);
+        if (hipMemcpyAsync(d + off_robot, robot_pos_, 8, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess) throw std::runtime_error("ground_exploration_gains: copy failed");
+        const float w = cfg_.voxel_width;
+        gie_ground_param g = {};
+        g.z_lo = (int32_t)std::floor(param.ground_min_height / w + 0.5f);      /* as ground_costmap() */
+        g.z_hi = (int32_t)std::floor(param.ground_max_height / w + 0.5f);
+        g.min_known = param.ground_min_known;
+        chk(gie_ground_compute_dev(m_, &g, reinterpret_cast<int32_t *>(d + off_ground)));
+        gie_ground_frontier_param fp = {};
+        fp.clearance_sq = ground_clearance_sq(); fp.min_size = min_size; fp.connectivity = 8; fp.max_clusters = max_clusters;
+        chk(gie_ground_frontier_compute_dev(m_, &fp, reinterpret_cast<int32_t *>(d + off_counts)));
+        float *d_goal = reinterpret_cast<float *>(d + off_goal);
+        if (max_clusters > 0) chk(gie_read_ground_frontier_clusters_dev(m_, reinterpret_cast<gie_ground_frontier_cluster *>(d), d_goal, nullptr));
+        gie_ground_nf1_param np = {};
+        np.clearance_sq = fp.clearance_sq;
+        chk(gie_ground_nf1_compute_dev(m_, reinterpret_cast<const float *>(d + off_robot), 1, &np, nullptr));
+        chk(gie_ground_nf1_query_dev(m_, d_goal, max_clusters, reinterpret_cast<int32_t *>(d + off_steps)));
+        gie_ground_view_param vp = {};
+        vp.r_min = r_min; vp.r_max = r_max;
+        chk(gie_ground_view_gain_dev(m_, d_goal, nullptr, max_clusters, &vp, reinterpret_cast<gie_view_score *>(d + off_scores)));
+        if (hipMemcpyAsync(explore_host_.data(), d, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess) throw std::runtime_error("ground_exploration_gains: copy failed");
+        chk(gie_sync(m_));
+        int32_t counts[2];
+        std::memcpy(counts, explore_host_.data() + off_counts, 8);
+        std::memcpy(ground_counts, explore_host_.data() + off_ground, 16);
+        ground_goals_kept = counts[0]; ground_goals_cells = counts[1];
+        const size_t have = std::min<size_t>((size_t)counts[0], cap);
+        clusters.resize(have); steps.resize(have); scores.resize(have);
+        if (have) {
+            std::memcpy(clusters.data(), explore_host_.data(), have * sizeof(gie_ground_frontier_cluster));
+            std::memcpy(steps.data(), explore_host_.data() + off_steps, have * 4);
+            std::memcpy(scores.data(), explore_host_.data() + off_scores, have * sizeof(gie_view_score));
+        }
+        return true;
+    }
+
     /* What a ground robot's tour planner needs to order the frontier clusters (include/gie.h "ground cost matrix"): the 4-connected
      * route lengths in cells, at ground_clearance_sq(), among the robot (point 0: the position of the last publishMap) and the goals
      * of at most max_clusters (<= 255) ground frontier clusters of at least min_size cells (connectivity 8).  ground_exploration_goals'

@@ -1001,6 +1001,66 @@ int gie_ground_nf1_query_dev(gie_mapper *h, const float *d_xy, int n, int32_t *d
 int gie_ground_costmat_compute(gie_mapper *h, const float *xy, int n, const gie_ground_nf1_param *p, int32_t *cost, uint8_t *valid);
 int gie_ground_costmat_compute_dev(gie_mapper *h, const float *d_xy, int n, const gie_ground_nf1_param *p, int32_t *d_cost, uint8_t *d_valid);
 
+/* ---- ground view gain: how many cells of the ground field a sensor would see from each of n candidate poses — the gain half of a
+ * ground robot's exploration utility, beside the route costs of "ground frontier clusters" and "ground cost matrix".  It is the view
+ * gain of "line of sight" in two dimensions; that call does not serve a ground robot for the reason the ground costmap exists: it
+ * reads the opaque plane of gie_los_prepare, which is built from the volume, where the floor is opaque one voxel below every line.
+ * No counterpart in the reference's code.
+ *
+ * Every call refers to the ground field that is valid where the call is enqueued: type(c) and the pivot are that field's
+ * (gie_read_ground*).  There is no prepare call and no kept result (the rule of "ground line of sight"): a later gie_ground_compute*
+ * makes later calls see the new field, a map update changes nothing, the ground navigation function is neither needed nor touched.
+ * Everything is an integer or one float operation on exact integers.  w = voxel_width.
+ *  views         two plain arrays: xy, 2 floats per view (metres, world frame), and normals, 2 * n_planes int32 per view, x then y
+ *                per plane; normals is not read (and may be NULL) when n_planes == 0.  The goal array of
+ *                gie_read_ground_frontier_clusters_dev, NaN tail included, can be handed over as d_xy unchanged.
+ *  p             the cell of a view's xy, gie_ground_query's mapping: gie_pos2coord(xy_k, w) - pvt_k.
+ *  opaque(c)     type(c) == GIE_VOX_OCCUPIED, or type(c) == GIE_VOX_UNKNOWN with GIE_GROUND_VIEW_UNKNOWN_OPAQUE.  dist_sq has no part
+ *                in it: sight is not clearance.
+ *  candidate     cell v is a CANDIDATE iff
+ *                  v is inside the rectangle and v != p;
+ *                  with d = v - p, rmin = r_min / w and rmax = r_max / w (float): (float)|d|^2 >= rmin * rmin and
+ *                  (float)|d|^2 <= rmax * rmax (|d|^2 is an exact integer below 2^21: one float product and one comparison on
+ *                  each side; whatever box an implementation bounds the candidates with, this test decides alone);
+ *                  the sector: n_planes == 1: normal_0 . d >= 0; n_planes == 2: both, or with GIE_GROUND_VIEW_UNION at least one of
+ *                  them (a sector wider than 180 degrees).  A normal component has magnitude <= 32767: the dot product is an exact
+ *                  int32.  A zero normal holds for every d.
+ *  visible       a candidate is VISIBLE iff no cell of L2(p, v) other than v itself is opaque; L2 is the cell line of "ground line
+ *                of sight", tie rule included (a line slips between two corner-touching cells).  p's own opacity is ignored, v may
+ *                be anything.
+ *  gie_view_score  the record of "line of sight", reused: unknown / frontier / occupied = the visible candidates of that column
+ *                type, candidates = all candidates; all four are -1 when xy is not finite or lies outside the rectangle.  The
+ *                counts are sums: they depend on no schedule.
+ *  mask          one view: X * Y bytes, x fastest: 0 not a candidate, 1 a hidden candidate, 2 a visible candidate; the byte at p
+ *                itself is 0.  An invalid view: the mask is all 0 and the score -1.  score may be NULL.
+ * GIE_ERR_INVALID, nothing written: a NULL handle or param; a call before the first gie_ground_compute*; a tiled mapper (as every
+ *  planner section); r_min or r_max not finite, r_min < 0, r_min > r_max (r_max may be anything finite); n_planes outside 0..2; an
+ *  unknown flag, GIE_GROUND_VIEW_UNION with n_planes != 2, non-zero reserved; n < 0; n > 0 with a NULL xy or out; normals NULL with
+ *  n_planes > 0; a NULL mask; in the host forms only, a normal component beyond +-32767 — the _dev forms never read the arrays on the
+ *  host: such a view scores -1 there.  n == 0 is valid and launches nothing; n has no upper limit.
+ * The host forms stage through the two scratch slots of the host forms and synchronise.  The _dev forms take DEVICE buffers and are
+ *  enqueued on the mapper's stream (gie_get_stream) with no host wait and no read-back.  Every call is a fixed sequence of launches,
+ *  none with a grid barrier.
+ * Memory: a mapper that never calls the section allocates and launches nothing.  The first call allocates one bit plane of opaque
+ *  cells with rows padded to 64-bit words (32 KiB for 512 x 512, 128 KiB for 1024 x 1024; gie_dalloc, freed by gie_destroy), of
+ *  which no reader may assume anything between calls.
+ * Cost: a call is two launches: the opaque plane (one pass over the type plane, which also writes the n scores' zeros and the mask's)
+ *  and the gain.  A workgroup of the gain takes a strip of a view's candidate rows, copies the opaque words between the view's cell
+ *  and its strip into LDS (at most the whole plane, 128 KiB) and walks each candidate's line there: a step is an LDS bit test.
+ * gie_profile_read: counted under "ground_query". */
+#define GIE_GROUND_VIEW_UNKNOWN_OPAQUE 1   /* UNKNOWN columns block sight too */
+#define GIE_GROUND_VIEW_UNION          2   /* n_planes == 2: a cell in EITHER half plane is inside (a sector wider than 180 degrees) */
+typedef struct gie_ground_view_param {     /* 32 bytes */
+    float r_min, r_max;     /* metres */
+    int32_t n_planes;       /* 0..2 half planes per view */
+    int32_t flags;          /* GIE_GROUND_VIEW_* */
+    int32_t reserved[4];    /* 0 */
+} gie_ground_view_param;
+int gie_ground_view_gain(gie_mapper *h, const float *xy, const int32_t *normals, int n, const gie_ground_view_param *p, gie_view_score *out);
+int gie_ground_view_gain_dev(gie_mapper *h, const float *d_xy, const int32_t *d_normals, int n, const gie_ground_view_param *p, gie_view_score *d_out);
+int gie_ground_view_mask(gie_mapper *h, const float *xy, const int32_t *normals, const gie_ground_view_param *p, uint8_t *mask, gie_view_score *score);
+int gie_ground_view_mask_dev(gie_mapper *h, const float *d_xy, const int32_t *d_normals, const gie_ground_view_param *p, uint8_t *d_mask, gie_view_score *d_score);
+
 /* ---- goal-to-goal cost matrix: the path lengths among up to 64 points (the robot and the goals of the frontier clusters, say), the
  * input of every tour-based explorer — in which order to visit the clusters.  n fields of gie_nf1_compute would give the same
  * numbers with n persistent launches and n whole fields; here ONE level-synchronous pass advances all searches, a 64-bit mask per
