@@ -162,6 +162,17 @@ class GroundViewParam(C.Structure):
     _fields_ = [("r_min", C.c_float), ("r_max", C.c_float), ("n_planes", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
+class GroundRolloutParam(C.Structure):
+    """gie_ground_rollout_param (include/gie.h): 32 bytes; clearance_sq and inflate_sq in squared cells."""
+    _fields_ = [("clearance_sq", C.c_int32), ("inflate_sq", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+class GroundRollout(C.Structure):
+    """gie_ground_rollout (include/gie.h): 48 bytes, one per trajectory."""
+    _fields_ = [("end", C.c_int32), ("poses", C.c_int32), ("hit", C.c_int32 * 2), ("cells", C.c_int32), ("min_dist_sq", C.c_int32), ("cost", C.c_int64),
+                ("nf1_end", C.c_int32), ("nf1_min", C.c_int32), ("nf1_min_at", C.c_int32), ("reserved", C.c_int32)]
+
+
 class GroundFrontierParam(C.Structure):
     """gie_ground_frontier_param (include/gie.h): 32 bytes; clearance_sq in squared cells."""
     _fields_ = [("clearance_sq", C.c_int32), ("min_size", C.c_int32), ("connectivity", C.c_int32), ("max_clusters", C.c_int32),
@@ -175,6 +186,7 @@ class GroundFrontierCluster(C.Structure):
 
 
 assert C.sizeof(GroundFrontierParam) == 32 and C.sizeof(GroundFrontierCluster) == 64 and GroundFrontierCluster.sum.offset == 40
+assert C.sizeof(GroundRolloutParam) == 32 and C.sizeof(GroundRollout) == 48 and GroundRollout.cost.offset == 24 and GroundRollout.nf1_end.offset == 32
 assert C.sizeof(GroundViewParam) == 32 and GroundViewParam.n_planes.offset == 8 and GroundViewParam.reserved.offset == 16
 assert C.sizeof(GroundLosParam) == 16 and C.sizeof(GroundHit) == 24 and C.sizeof(GroundShortcutParam) == 32 and C.sizeof(GroundWaypoint) == 24
 assert C.sizeof(GroundParam) == 32 and C.sizeof(GroundCell) == 16 and C.sizeof(GroundNf1Param) == 32
@@ -193,6 +205,9 @@ GROUND_NF1_FROM_FRONTIERS = 2
 GROUND_LOS_UNKNOWN_TRAVERSABLE = 1
 GROUND_VIEW_UNKNOWN_OPAQUE = 1
 GROUND_VIEW_UNION = 2
+GROUND_ROLLOUT_UNKNOWN_TRAVERSABLE = 1
+GROUND_ROLLOUT_NF1 = 2
+GROUND_ROLLOUT_MAX_POSES = 4096
 VOX_UNKNOWN, VOX_FREE, VOX_OCCUPIED, VOX_FNT = 0, 1, 2, 3
 
 
@@ -364,6 +379,9 @@ DEVICE_ONLY = {
     "ground_view_gain_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(GroundViewParam), C.c_void_p]),
     "ground_view_mask": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.POINTER(GroundViewParam), C.c_void_p, C.c_void_p]),
     "ground_view_mask_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.POINTER(GroundViewParam), C.c_void_p, C.c_void_p]),
+    # ground rollouts: batched trajectory scoring on the ground costmap (include/gie.h): device library only
+    "ground_rollouts": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.POINTER(GroundRolloutParam), C.c_void_p]),
+    "ground_rollouts_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.POINTER(GroundRolloutParam), C.c_void_p]),
     # goal-to-goal cost matrix of the local volume (include/gie.h): device library only
     "costmat_compute": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(Nf1Param), C.c_void_p, C.c_void_p]),
     "costmat_compute_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(Nf1Param), C.c_void_p, C.c_void_p]),

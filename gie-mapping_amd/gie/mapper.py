@@ -13,8 +13,8 @@ import sys
 import numpy as np
 
 from . import _capi
-from ._capi import CLOUD_DIST, CLOUD_TYPE, GROUND_LOS_UNKNOWN_TRAVERSABLE, GROUND_NF1_FROM_FRONTIERS, GROUND_NF1_UNKNOWN_TRAVERSABLE, GROUND_UNKNOWN_BLOCKS, GROUND_VIEW_UNION, GROUND_VIEW_UNKNOWN_OPAQUE, LOS_UNKNOWN_OPAQUE, NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE, VOX_FNT, VOX_FREE, VOX_OCCUPIED, VOX_UNKNOWN
-from ._capi import CamParam, CloudParam, Config, CostMapHdr, FrameStats, FrontierParam, GroundFrontierParam, GroundLosParam, GroundNf1Param, GroundParam, GroundShortcutParam, GroundViewParam, LosParam, MultiScanParam, Nf1Param, ScanParam, ShortcutParam, ViewParam, Voxel
+from ._capi import CLOUD_DIST, CLOUD_TYPE, GROUND_LOS_UNKNOWN_TRAVERSABLE, GROUND_NF1_FROM_FRONTIERS, GROUND_NF1_UNKNOWN_TRAVERSABLE, GROUND_ROLLOUT_MAX_POSES, GROUND_ROLLOUT_NF1, GROUND_ROLLOUT_UNKNOWN_TRAVERSABLE, GROUND_UNKNOWN_BLOCKS, GROUND_VIEW_UNION, GROUND_VIEW_UNKNOWN_OPAQUE, LOS_UNKNOWN_OPAQUE, NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE, VOX_FNT, VOX_FREE, VOX_OCCUPIED, VOX_UNKNOWN
+from ._capi import CamParam, CloudParam, Config, CostMapHdr, FrameStats, FrontierParam, GroundFrontierParam, GroundLosParam, GroundNf1Param, GroundParam, GroundRolloutParam, GroundShortcutParam, GroundViewParam, LosParam, MultiScanParam, Nf1Param, ScanParam, ShortcutParam, ViewParam, Voxel
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG, "csrc", "libgie_hip.so")
@@ -39,6 +39,9 @@ CLOUD_NO_BAND = (-2 ** 31, 2 ** 31 - 1)
 GROUND_CELL_DTYPE = np.dtype([("dist_sq", "<i4"), ("coc", "<i4", (2,)), ("type", "i1"), ("inside", "u1"), ("pad", "u1", (2,))])
 GROUND_HIT_DTYPE = np.dtype([("first", "<i4"), ("len", "<i4"), ("hit", "<i4", (2,)), ("min_dist_sq", "<i4"), ("reserved", "<i4")])
 GROUND_WAYPOINT_DTYPE = np.dtype([("xy", "<i4", (2,)), ("index", "<i4"), ("min_dist_sq", "<i4"), ("forced", "<i4"), ("reserved", "<i4")])
+# gie_ground_rollout (48 bytes)
+GROUND_ROLLOUT_DTYPE = np.dtype([("end", "<i4"), ("poses", "<i4"), ("hit", "<i4", (2,)), ("cells", "<i4"), ("min_dist_sq", "<i4"), ("cost", "<i8"),
+                                 ("nf1_end", "<i4"), ("nf1_min", "<i4"), ("nf1_min_at", "<i4"), ("reserved", "<i4")])
 # gie_ground_frontier_cluster: 64 bytes, the offsets of the C struct
 GROUND_FRONTIER_CLUSTER_DTYPE = np.dtype([("label", "<i4"), ("size", "<i4"), ("lo", "<i4", (2,)), ("hi", "<i4", (2,)), ("rep", "<i4", (2,)),
                                           ("centroid", "<f4", (2,)), ("sum", "<i8", (2,)), ("rep_dist_sq", "<i4"), ("reserved", "<i4")])
@@ -1081,6 +1084,32 @@ class Mapper(MapperBase):
         p = self.ground_view_param(r_min, r_max, n_planes, unknown_opaque, union)
         self._chk(self._f["ground_view_mask_dev"](self._h, C.c_void_p(d_xy or None), C.c_void_p(d_normals or None), C.byref(p), C.c_void_p(d_mask or None),
                                                   C.c_void_p(d_score or None)))
+
+    # --- ground rollouts: batched trajectory scoring on the ground costmap (include/gie.h) ---
+    def ground_rollout_param(self, clearance_sq=0, inflate_sq=0, unknown_traversable=False, nf1=False):
+        """gie_ground_rollout_param: clearance_sq and inflate_sq in squared CELLS, compared with the ground field's dist_sq."""
+        p = GroundRolloutParam()
+        p.clearance_sq, p.inflate_sq = int(clearance_sq), int(inflate_sq)
+        p.flags = (GROUND_ROLLOUT_UNKNOWN_TRAVERSABLE if unknown_traversable else 0) | (GROUND_ROLLOUT_NF1 if nf1 else 0)
+        return p
+
+    def ground_rollouts(self, xy, clearance_sq=0, inflate_sq=0, unknown_traversable=False, nf1=False):
+        """n trajectories of T poses (an (n, T, 2) float32 array, metres, world frame; a NaN tail ends a shorter one) over the current
+        ground field, with `nf1` also over its navigation function -> GROUND_ROLLOUT_DTYPE [n] (synchronises)."""
+        xy = np.ascontiguousarray(np.asarray(xy, dtype=np.float32))
+        if xy.ndim != 3 or xy.shape[2] != 2:
+            raise ValueError("ground_rollouts: an (n, T, 2) array")
+        n, T = xy.shape[0], xy.shape[1]
+        out = np.zeros(n, GROUND_ROLLOUT_DTYPE)
+        p = self.ground_rollout_param(clearance_sq, inflate_sq, unknown_traversable, nf1)
+        self._chk(self._f["ground_rollouts"](self._h, _ptr(xy) if n and T else None, n, T, C.byref(p), _ptr(out) if n else None))
+        return out
+
+    def ground_rollouts_dev(self, d_xy, n, T, d_out, clearance_sq=0, inflate_sq=0, unknown_traversable=False, nf1=False):
+        """n trajectories with poses (n x T x 2 float32) and records (n x 48 bytes) in DEVICE buffers (raw addresses), on the mapper's
+        stream."""
+        p = self.ground_rollout_param(clearance_sq, inflate_sq, unknown_traversable, nf1)
+        self._chk(self._f["ground_rollouts_dev"](self._h, C.c_void_p(d_xy or None), int(n), int(T), C.byref(p), C.c_void_p(d_out or None)))
 
     def read_costmap_ground_nf1(self):
         """The one-layer TYPE_NF1 CostMap of the ground navigation function: (SeenDist payload [Y][X], header) (synchronises)."""

@@ -657,6 +657,44 @@ public:
     }
     gie_shortcut_info ground_waypoints_info = { 0, 0, 0.f, 0 };   /* of the last ground_waypoints() */
 
+    /* The local half of that plan (include/gie.h "ground rollouts"): n unicycle arcs of T poses from the robot's position of the
+     * last publishMap at heading `yaw`, arc i driven at v[i] m/s and omega[i] rad/s in steps of dt seconds — pose 0 is the robot,
+     * then x += v dt cos(theta), y += v dt sin(theta), theta += omega dt, in double, stored as float — scored by
+     * gie_ground_rollouts on the ground field and NF1 that ground_plan() or ground_waypoints() left, at ground_clearance_sq(), with
+     * inflate_sq = ceil(inflate_radius / voxel_width)^2 and the NF1 flag.  poses holds the n * T * 2 floats that were scored,
+     * records their n records.  Returns the index of the best arc: among those with poses >= 2 and nf1_min >= 0 the least nf1_min,
+     * then the least cost, then the lowest index; -1 when there is none, and -1 with everything left alone while the band is not set. */
+    int ground_local_plan(float yaw, const float *v, const float *omega, int n, float dt, int T, float inflate_radius, std::vector<float> &poses,
+                          std::vector<gie_ground_rollout> &records)
+    {
+        if (param.ground_max_height < param.ground_min_height) return -1;
+        if (n < 0 || T < 1 || T > GIE_GROUND_ROLLOUT_MAX_POSES) throw std::invalid_argument("ground_local_plan: n >= 0, T in 1..4096");
+        poses.resize((size_t)n * T * 2);
+        for (int i = 0; i < n; i++) {
+            double x = robot_pos_[0], y = robot_pos_[1], th = yaw;
+            for (int k = 0; k < T; k++) {
+                float *q = poses.data() + 2 * ((size_t)i * T + k);
+                q[0] = (float)x; q[1] = (float)y;
+                x += (double)v[i] * dt * std::cos(th); y += (double)v[i] * dt * std::sin(th);
+                th += (double)omega[i] * dt;
+            }
+        }
+        gie_ground_rollout_param p = {};
+        p.clearance_sq = ground_clearance_sq();
+        const int cells = (int)ceilf(inflate_radius / cfg_.voxel_width);
+        p.inflate_sq = cells * cells;
+        p.flags = GIE_GROUND_ROLLOUT_NF1;
+        records.assign((size_t)n, gie_ground_rollout{});
+        chk(gie_ground_rollouts(m_, poses.data(), n, T, &p, records.data()));
+        int best = -1;
+        for (int i = 0; i < n; i++) {
+            const gie_ground_rollout &r = records[(size_t)i];
+            if (r.poses < 2 || r.nf1_min < 0) continue;
+            if (best < 0 || r.nf1_min < records[(size_t)best].nf1_min || (r.nf1_min == records[(size_t)best].nf1_min && r.cost < records[(size_t)best].cost)) best = i;
+        }
+        return best;
+    }
+
 #ifdef GIE_HOST_HAS_HIP
     /* A ground robot's goal selection on the map as it stands (include/gie.h "ground frontier clusters"): which frontiers exist, how
      * large they are, where to drive for each and how far that is.  Four steps chained through the _dev forms on the mapper's

@@ -1061,6 +1061,71 @@ int gie_ground_view_gain_dev(gie_mapper *h, const float *d_xy, const int32_t *d_
 int gie_ground_view_mask(gie_mapper *h, const float *xy, const int32_t *normals, const gie_ground_view_param *p, uint8_t *mask, gie_view_score *score);
 int gie_ground_view_mask_dev(gie_mapper *h, const float *d_xy, const int32_t *d_normals, const gie_ground_view_param *p, uint8_t *d_mask, gie_view_score *d_score);
 
+/* ---- ground rollouts: n candidate trajectories of T poses each, scored on the ground costmap in one call — the local half of a ground
+ * robot's navigation, beside the global half of "ground navigation function" and "ground line of sight".  A sampling-based local
+ * planner (DWA, trajectory rollout, MPPI) draws a few thousand short trajectories from the robot's pose, drops those that collide and
+ * scores the rest by how close they pass to obstacles and how far they get down the navigation function.  One call returns ONE record
+ * per trajectory; chaining gie_ground_segments_dev, gie_ground_query_dev and gie_ground_nf1_query_dev over the n * T poses instead
+ * returns n * T records of 24 + 16 + 4 bytes for the host to reduce, and cannot give the per-cell cost.  No counterpart in the
+ * reference's code.
+ *
+ * Every call refers to the ground field that is valid where the call is enqueued (the rule of "ground line of sight"): there is no
+ * prepare call and no kept result, a later gie_ground_compute* makes later calls see the new field, a map update changes nothing.
+ * With GIE_GROUND_ROLLOUT_NF1 the call also reads the ground navigation function of that field; it writes neither.  Everything is
+ * an integer: a result depends on no schedule.
+ *  poses         xy holds pose k of trajectory i at xy[2 * (i * T + k)], two floats, metres, world frame.
+ *  c_k           the cell of pose k, gie_ground_query's mapping: gie_pos2coord(xy, w) - pvt per axis.  A pose that is not finite (NaN,
+ *                +-inf), that no int32 coordinate holds, or that lies outside the field's rectangle has NO cell.
+ *  blocked(c)    the rule of "ground line of sight" with clearance_sq and GIE_GROUND_ROLLOUT_UNKNOWN_TRAVERSABLE.
+ *  reached       pose k is REACHED iff every pose 0 .. k has a cell, c_0 is not blocked, and no cell of L2(c_{j-1}, c_j) is blocked
+ *                for 1 <= j <= k; L2 is the cell line of "ground line of sight", tie rule included: a wall one cell thick between
+ *                two consecutive samples is found.
+ *  poses         m, the number of reached poses, 0 .. T.
+ *  end           0 when m == T; otherwise 2 when pose m has no cell; otherwise 1: leg m is blocked, and hit is its first blocked
+ *                cell in walking order from c_{m-1} (c_0 itself when m == 0), in GLOBAL cell coordinates (local + pivot).  A NaN
+ *                tail is the way to pass rollouts shorter than T: they end with 2.
+ *  the prefix's cells  c_0, then for j = 1 .. m - 1 the cells of L2(c_{j-1}, c_j) after its first.  Two equal consecutive cells add
+ *                nothing; a cell that two different legs cross counts twice.  cells is their number, min_dist_sq the minimum of the
+ *                field's dist_sq over them (-1 on a field without an obstacle column) and cost the sum of
+ *                max(0, inflate_sq - dist_sq) over them, a dist_sq of -1 costing 0: at most 2^22 per cell, a 64-bit sum.  With
+ *                m == 0 all three are 0.
+ *  NF1           with GIE_GROUND_ROLLOUT_NF1, the values gie_ground_nf1_query returns at c_0 .. c_{m-1}: nf1_end is the one at
+ *                c_{m-1} (-1 when that cell is unreachable or m == 0), nf1_min the least value >= 0 among them (-1 when there is
+ *                none) and nf1_min_at the FIRST pose that has it (-1).  Without the flag all three are -2.
+ * GIE_ERR_INVALID, nothing written: a NULL handle; a tiled mapper; no ground field yet; a NULL param; clearance_sq < 0; inflate_sq
+ *  outside 0 .. 1 << 22; an unknown flag; non-zero reserved; GIE_GROUND_ROLLOUT_NF1 without a valid ground navigation function (a
+ *  gie_ground_compute* invalidates it); n < 0; T outside 1 .. GIE_GROUND_ROLLOUT_MAX_POSES; n > 0 with a NULL buffer; in the host form,
+ *  n * T * 8 bytes beyond size_t.  n == 0 is valid and launches nothing; n has no upper limit.
+ * The host form stages through the two scratch slots of the host forms and synchronises.  The _dev form takes DEVICE buffers and is
+ *  enqueued on the mapper's stream (gie_get_stream) with no host wait, no read-back and no grid barrier.
+ * Memory: nothing of its own: the blocked bit plane is the one of "ground line of sight", allocated by the first call of either.
+ * Cost: a call is two launches: the blocked plane, as there, and the rollouts: a wave per trajectory, a lane per pose in chunks of 64,
+ *  each lane walking the leg that ends at its pose; the chunk with the first blocked leg is the last.
+ * gie_profile_read: counted under "ground_query". */
+#define GIE_GROUND_ROLLOUT_UNKNOWN_TRAVERSABLE 1   /* as GIE_GROUND_LOS_UNKNOWN_TRAVERSABLE */
+#define GIE_GROUND_ROLLOUT_NF1                 2   /* gather the ground NF1 at the poses; needs a valid ground NF1 */
+#define GIE_GROUND_ROLLOUT_MAX_POSES 4096
+typedef struct gie_ground_rollout_param {   /* 32 bytes */
+    int32_t clearance_sq;   /* blocked = ground line of sight's rule, squared cells, >= 0 */
+    int32_t inflate_sq;     /* 0 .. 1 << 22: a cell costs max(0, inflate_sq - dist_sq); 0 = no cost */
+    int32_t flags;          /* GIE_GROUND_ROLLOUT_* */
+    int32_t reserved[5];    /* must be 0 */
+} gie_ground_rollout_param;
+typedef struct gie_ground_rollout {         /* 48 bytes */
+    int32_t end;            /* 0 complete, 1 blocked, 2 left: pose `poses` has no cell (outside the field or not finite) */
+    int32_t poses;          /* m: the poses of the clear prefix, 0 .. T */
+    int32_t hit[2];         /* end == 1: the first blocked cell, in the field's global cell coordinates; otherwise 0, 0 */
+    int32_t cells;          /* cells of the prefix's polyline, every joint once; 0 when m == 0 */
+    int32_t min_dist_sq;    /* over those cells; -1 when the field has no obstacle column; 0 when m == 0 */
+    int64_t cost;           /* over those cells: sum of max(0, inflate_sq - dist_sq); a dist_sq of -1 costs 0 */
+    int32_t nf1_end;        /* ground NF1 at pose m - 1 (-1 unreachable or m == 0); -2 without GIE_GROUND_ROLLOUT_NF1 */
+    int32_t nf1_min;        /* the least value >= 0 at the prefix's poses, -1 if there is none; -2 without the flag */
+    int32_t nf1_min_at;     /* the first pose that has it, -1; -2 without the flag */
+    int32_t reserved;       /* 0 */
+} gie_ground_rollout;
+int gie_ground_rollouts(gie_mapper *h, const float *xy, int n, int T, const gie_ground_rollout_param *p, gie_ground_rollout *out);
+int gie_ground_rollouts_dev(gie_mapper *h, const float *d_xy, int n, int T, const gie_ground_rollout_param *p, gie_ground_rollout *d_out);
+
 /* ---- goal-to-goal cost matrix: the path lengths among up to 64 points (the robot and the goals of the frontier clusters, say), the
  * input of every tour-based explorer — in which order to visit the clusters.  n fields of gie_nf1_compute would give the same
  * numbers with n persistent launches and n whole fields; here ONE level-synchronous pass advances all searches, a 64-bit mask per
