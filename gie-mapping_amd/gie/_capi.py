@@ -173,6 +173,17 @@ class GroundRollout(C.Structure):
                 ("nf1_end", C.c_int32), ("nf1_min", C.c_int32), ("nf1_min_at", C.c_int32), ("reserved", C.c_int32)]
 
 
+class GroundFootprintParam(C.Structure):
+    """gie_ground_footprint_param (include/gie.h): 32 bytes; the three extents and clearance_sq in squared cells."""
+    _fields_ = [("front_sq", C.c_int32), ("back_sq", C.c_int32), ("side_sq", C.c_int32), ("clearance_sq", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class GroundFootprint(C.Structure):
+    """gie_ground_footprint (include/gie.h): 32 bytes, one per trajectory."""
+    _fields_ = [("end", C.c_int32), ("poses", C.c_int32), ("hit", C.c_int32 * 2), ("hit_cells", C.c_int32), ("min_dist_sq", C.c_int32), ("min_at", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class GroundFrontierParam(C.Structure):
     """gie_ground_frontier_param (include/gie.h): 32 bytes; clearance_sq in squared cells."""
     _fields_ = [("clearance_sq", C.c_int32), ("min_size", C.c_int32), ("connectivity", C.c_int32), ("max_clusters", C.c_int32),
@@ -186,6 +197,7 @@ class GroundFrontierCluster(C.Structure):
 
 
 assert C.sizeof(GroundFrontierParam) == 32 and C.sizeof(GroundFrontierCluster) == 64 and GroundFrontierCluster.sum.offset == 40
+assert C.sizeof(GroundFootprintParam) == 32 and C.sizeof(GroundFootprint) == 32 and GroundFootprintParam.flags.offset == 16 and GroundFootprint.hit_cells.offset == 16
 assert C.sizeof(GroundRolloutParam) == 32 and C.sizeof(GroundRollout) == 48 and GroundRollout.cost.offset == 24 and GroundRollout.nf1_end.offset == 32
 assert C.sizeof(GroundViewParam) == 32 and GroundViewParam.n_planes.offset == 8 and GroundViewParam.reserved.offset == 16
 assert C.sizeof(GroundLosParam) == 16 and C.sizeof(GroundHit) == 24 and C.sizeof(GroundShortcutParam) == 32 and C.sizeof(GroundWaypoint) == 24
@@ -208,6 +220,9 @@ GROUND_VIEW_UNION = 2
 GROUND_ROLLOUT_UNKNOWN_TRAVERSABLE = 1
 GROUND_ROLLOUT_NF1 = 2
 GROUND_ROLLOUT_MAX_POSES = 4096
+GROUND_FOOTPRINT_UNKNOWN_TRAVERSABLE = 1
+GROUND_FOOTPRINT_MARGIN = 2
+GROUND_FOOTPRINT_MAX_SQ = 1 << 16
 VOX_UNKNOWN, VOX_FREE, VOX_OCCUPIED, VOX_FNT = 0, 1, 2, 3
 
 
@@ -382,6 +397,11 @@ DEVICE_ONLY = {
     # ground rollouts: batched trajectory scoring on the ground costmap (include/gie.h): device library only
     "ground_rollouts": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.POINTER(GroundRolloutParam), C.c_void_p]),
     "ground_rollouts_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.POINTER(GroundRolloutParam), C.c_void_p]),
+    # ground footprints: oriented-rectangle pose checks on the ground costmap (include/gie.h): device library only
+    "ground_footprints": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(GroundFootprintParam), C.c_void_p]),
+    "ground_footprints_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(GroundFootprintParam), C.c_void_p]),
+    "ground_footprint_mask": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.POINTER(GroundFootprintParam), C.c_void_p, C.c_void_p]),
+    "ground_footprint_mask_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.POINTER(GroundFootprintParam), C.c_void_p, C.c_void_p]),
     # goal-to-goal cost matrix of the local volume (include/gie.h): device library only
     "costmat_compute": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(Nf1Param), C.c_void_p, C.c_void_p]),
     "costmat_compute_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(Nf1Param), C.c_void_p, C.c_void_p]),

@@ -13,8 +13,8 @@ import sys
 import numpy as np
 
 from . import _capi
-from ._capi import CLOUD_DIST, CLOUD_TYPE, GROUND_LOS_UNKNOWN_TRAVERSABLE, GROUND_NF1_FROM_FRONTIERS, GROUND_NF1_UNKNOWN_TRAVERSABLE, GROUND_ROLLOUT_MAX_POSES, GROUND_ROLLOUT_NF1, GROUND_ROLLOUT_UNKNOWN_TRAVERSABLE, GROUND_UNKNOWN_BLOCKS, GROUND_VIEW_UNION, GROUND_VIEW_UNKNOWN_OPAQUE, LOS_UNKNOWN_OPAQUE, NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE, VOX_FNT, VOX_FREE, VOX_OCCUPIED, VOX_UNKNOWN
-from ._capi import CamParam, CloudParam, Config, CostMapHdr, FrameStats, FrontierParam, GroundFrontierParam, GroundLosParam, GroundNf1Param, GroundParam, GroundRolloutParam, GroundShortcutParam, GroundViewParam, LosParam, MultiScanParam, Nf1Param, ScanParam, ShortcutParam, ViewParam, Voxel
+from ._capi import CLOUD_DIST, CLOUD_TYPE, GROUND_FOOTPRINT_MARGIN, GROUND_FOOTPRINT_MAX_SQ, GROUND_FOOTPRINT_UNKNOWN_TRAVERSABLE, GROUND_LOS_UNKNOWN_TRAVERSABLE, GROUND_NF1_FROM_FRONTIERS, GROUND_NF1_UNKNOWN_TRAVERSABLE, GROUND_ROLLOUT_MAX_POSES, GROUND_ROLLOUT_NF1, GROUND_ROLLOUT_UNKNOWN_TRAVERSABLE, GROUND_UNKNOWN_BLOCKS, GROUND_VIEW_UNION, GROUND_VIEW_UNKNOWN_OPAQUE, LOS_UNKNOWN_OPAQUE, NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE, VOX_FNT, VOX_FREE, VOX_OCCUPIED, VOX_UNKNOWN
+from ._capi import CamParam, CloudParam, Config, CostMapHdr, FrameStats, FrontierParam, GroundFootprintParam, GroundFrontierParam, GroundLosParam, GroundNf1Param, GroundParam, GroundRolloutParam, GroundShortcutParam, GroundViewParam, LosParam, MultiScanParam, Nf1Param, ScanParam, ShortcutParam, ViewParam, Voxel
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG, "csrc", "libgie_hip.so")
@@ -42,6 +42,8 @@ GROUND_WAYPOINT_DTYPE = np.dtype([("xy", "<i4", (2,)), ("index", "<i4"), ("min_d
 # gie_ground_rollout (48 bytes)
 GROUND_ROLLOUT_DTYPE = np.dtype([("end", "<i4"), ("poses", "<i4"), ("hit", "<i4", (2,)), ("cells", "<i4"), ("min_dist_sq", "<i4"), ("cost", "<i8"),
                                  ("nf1_end", "<i4"), ("nf1_min", "<i4"), ("nf1_min_at", "<i4"), ("reserved", "<i4")])
+# gie_ground_footprint (32 bytes)
+GROUND_FOOTPRINT_DTYPE = np.dtype([("end", "<i4"), ("poses", "<i4"), ("hit", "<i4", (2,)), ("hit_cells", "<i4"), ("min_dist_sq", "<i4"), ("min_at", "<i4"), ("reserved", "<i4")])
 # gie_ground_frontier_cluster: 64 bytes, the offsets of the C struct
 GROUND_FRONTIER_CLUSTER_DTYPE = np.dtype([("label", "<i4"), ("size", "<i4"), ("lo", "<i4", (2,)), ("hi", "<i4", (2,)), ("rep", "<i4", (2,)),
                                           ("centroid", "<f4", (2,)), ("sum", "<i8", (2,)), ("rep_dist_sq", "<i4"), ("reserved", "<i4")])
@@ -1110,6 +1112,52 @@ class Mapper(MapperBase):
         stream."""
         p = self.ground_rollout_param(clearance_sq, inflate_sq, unknown_traversable, nf1)
         self._chk(self._f["ground_rollouts_dev"](self._h, C.c_void_p(d_xy or None), int(n), int(T), C.byref(p), C.c_void_p(d_out or None)))
+
+    # --- ground footprints: oriented-rectangle pose checks on the ground costmap (include/gie.h) ---
+    def ground_footprint_param(self, front_sq, back_sq, side_sq, clearance_sq=0, unknown_traversable=False, margin=False):
+        """gie_ground_footprint_param: the extents and clearance_sq in squared CELLS."""
+        p = GroundFootprintParam()
+        p.front_sq, p.back_sq, p.side_sq, p.clearance_sq = int(front_sq), int(back_sq), int(side_sq), int(clearance_sq)
+        p.flags = (GROUND_FOOTPRINT_UNKNOWN_TRAVERSABLE if unknown_traversable else 0) | (GROUND_FOOTPRINT_MARGIN if margin else 0)
+        return p
+
+    def ground_footprints(self, xy, heading, front_sq, back_sq, side_sq, clearance_sq=0, unknown_traversable=False, margin=False):
+        """n trajectories of T poses (xy: an (n, T, 2) float32 array, metres, world frame; heading: (n, T, 2) int32 direction vectors; a
+        NaN or zero-heading tail ends a shorter one), each pose an oriented rectangle of cells on the current ground field
+        -> GROUND_FOOTPRINT_DTYPE [n] (synchronises)."""
+        xy = np.ascontiguousarray(np.asarray(xy, dtype=np.float32))
+        heading = np.ascontiguousarray(np.asarray(heading, dtype=np.int32))
+        if xy.ndim != 3 or xy.shape[2] != 2 or heading.shape != xy.shape:
+            raise ValueError("ground_footprints: two (n, T, 2) arrays")
+        n, T = xy.shape[0], xy.shape[1]
+        out = np.zeros(n, GROUND_FOOTPRINT_DTYPE)
+        p = self.ground_footprint_param(front_sq, back_sq, side_sq, clearance_sq, unknown_traversable, margin)
+        some = n and T
+        self._chk(self._f["ground_footprints"](self._h, _ptr(xy) if some else None, _ptr(heading) if some else None, n, T, C.byref(p), _ptr(out) if n else None))
+        return out
+
+    def ground_footprints_dev(self, d_xy, d_heading, n, T, d_out, front_sq, back_sq, side_sq, clearance_sq=0, unknown_traversable=False, margin=False):
+        """n trajectories with poses (n x T x 2 float32), headings (n x T x 2 int32) and records (n x 32 bytes) in DEVICE buffers (raw
+        addresses), on the mapper's stream."""
+        p = self.ground_footprint_param(front_sq, back_sq, side_sq, clearance_sq, unknown_traversable, margin)
+        self._chk(self._f["ground_footprints_dev"](self._h, C.c_void_p(d_xy or None), C.c_void_p(d_heading or None), int(n), int(T), C.byref(p), C.c_void_p(d_out or None)))
+
+    def ground_footprint_mask(self, xy, heading, front_sq, back_sq, side_sq, clearance_sq=0, unknown_traversable=False, margin=False):
+        """The footprint of ONE pose (xy: 2 floats, heading: 2 ints) -> (mask uint8 [Y][X]: 0 / 1 footprint / 2 blocked footprint, its
+        GROUND_FOOTPRINT_DTYPE record) (synchronises)."""
+        xy = np.ascontiguousarray(np.asarray(xy, dtype=np.float32).reshape(2))
+        heading = np.ascontiguousarray(np.asarray(heading, dtype=np.int32).reshape(2))
+        mask = np.empty((self.size[1], self.size[0]), np.uint8)
+        rec = np.zeros(1, GROUND_FOOTPRINT_DTYPE)
+        p = self.ground_footprint_param(front_sq, back_sq, side_sq, clearance_sq, unknown_traversable, margin)
+        self._chk(self._f["ground_footprint_mask"](self._h, _ptr(xy), _ptr(heading), C.byref(p), _ptr(mask), _ptr(rec)))
+        return mask, rec[0]
+
+    def ground_footprint_mask_dev(self, d_xy, d_heading, d_mask, d_rec, front_sq, back_sq, side_sq, clearance_sq=0, unknown_traversable=False, margin=False):
+        """One pose, its mask (X * Y bytes) and its record (32 bytes, or 0) in DEVICE buffers (raw addresses), on the mapper's stream."""
+        p = self.ground_footprint_param(front_sq, back_sq, side_sq, clearance_sq, unknown_traversable, margin)
+        self._chk(self._f["ground_footprint_mask_dev"](self._h, C.c_void_p(d_xy or None), C.c_void_p(d_heading or None), C.byref(p), C.c_void_p(d_mask or None),
+                                                       C.c_void_p(d_rec or None)))
 
     def read_costmap_ground_nf1(self):
         """The one-layer TYPE_NF1 CostMap of the ground navigation function: (SeenDist payload [Y][X], header) (synchronises)."""

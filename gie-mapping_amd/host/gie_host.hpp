@@ -64,6 +64,8 @@ struct Parameters {
                                                                  * "ground/min_height", "ground/max_height"; off while max < min (the default) */
     int ground_min_known = 1;            /* "ground/min_known": gie_ground_param.min_known */
     float ground_robot_radius = 0.f;     /* "ground/robot_radius" (metres): ground_plan() keeps ceil(radius / voxel_width) cells away from every obstacle column */
+    float ground_footprint[3] = { -1.f, -1.f, -1.f };   /* "ground/footprint": front, back, half width (metres) of the robot's rectangle around its reference
+                                                          * point, three numbers ("0.7 0.3 0.3" or "[0.7, 0.3, 0.3]"); unset (the default) while one is negative */
     bool profile_loc_rms = false, profile_glb_rms = false;
     std::string log_name = "GIE_log.csv";
     std::string data_case = "ugv_corridor";
@@ -123,6 +125,14 @@ struct Parameters {
         else if (k == "ground/min_height") ground_min_height = fl(); else if (k == "ground/max_height") ground_max_height = fl();
         else if (k == "ground/min_known") ground_min_known = in();
         else if (k == "ground/robot_radius") ground_robot_radius = fl();
+        else if (k == "ground/footprint") {
+            std::string t = v;
+            for (char &ch : t) if (ch == '[' || ch == ']' || ch == ',') ch = ' ';
+            std::istringstream is(t);
+            float f3[3];
+            if (!(is >> f3[0] >> f3[1] >> f3[2])) throw std::invalid_argument("ground/footprint: three numbers (front, back, half width)");
+            for (int i = 0; i < 3; i++) ground_footprint[i] = f3[i];
+        }
         else if (k == "wave/fast_mode") fast_mode = b(); else if (k == "wave/cutoff_dist") cutoff_dist = fl();
         else if (k == "hash/bucket_max") max_bucket = in(); else if (k == "hash/block_max") max_block = in();
         else if (k == "gpu/wave_workgroups") wave_workgroups = in(); else if (k == "gpu/place_tries") place_tries = in();
@@ -669,27 +679,53 @@ public:
     {
         if (param.ground_max_height < param.ground_min_height) return -1;
         if (n < 0 || T < 1 || T > GIE_GROUND_ROLLOUT_MAX_POSES) throw std::invalid_argument("ground_local_plan: n >= 0, T in 1..4096");
-        poses.resize((size_t)n * T * 2);
-        for (int i = 0; i < n; i++) {
-            double x = robot_pos_[0], y = robot_pos_[1], th = yaw;
-            for (int k = 0; k < T; k++) {
-                float *q = poses.data() + 2 * ((size_t)i * T + k);
-                q[0] = (float)x; q[1] = (float)y;
-                x += (double)v[i] * dt * std::cos(th); y += (double)v[i] * dt * std::sin(th);
-                th += (double)omega[i] * dt;
-            }
-        }
-        gie_ground_rollout_param p = {};
-        p.clearance_sq = ground_clearance_sq();
-        const int cells = (int)ceilf(inflate_radius / cfg_.voxel_width);
-        p.inflate_sq = cells * cells;
-        p.flags = GIE_GROUND_ROLLOUT_NF1;
-        records.assign((size_t)n, gie_ground_rollout{});
-        chk(gie_ground_rollouts(m_, poses.data(), n, T, &p, records.data()));
+        ground_arcs_(yaw, v, omega, n, dt, T, poses, nullptr);
+        ground_score_arcs_(poses, n, T, inflate_radius, records);
         int best = -1;
         for (int i = 0; i < n; i++) {
             const gie_ground_rollout &r = records[(size_t)i];
             if (r.poses < 2 || r.nf1_min < 0) continue;
+            if (best < 0 || r.nf1_min < records[(size_t)best].nf1_min || (r.nf1_min == records[(size_t)best].nf1_min && r.cost < records[(size_t)best].cost)) best = i;
+        }
+        return best;
+    }
+
+    /* The squared extents of "ground/footprint" in cells, as gie_ground_footprint_param takes them: front_sq, back_sq, side_sq, each
+     * floor((metres / voxel_width)^2) in float; -1, -1, -1 while "ground/footprint" is not set (one of the three negative). */
+    std::array<int32_t, 3> ground_footprint_sq() const
+    {
+        std::array<int32_t, 3> sq = { -1, -1, -1 };
+        if (param.ground_footprint[0] < 0.f || param.ground_footprint[1] < 0.f || param.ground_footprint[2] < 0.f) return sq;
+        for (int i = 0; i < 3; i++) { const float c = param.ground_footprint[i] / cfg_.voxel_width; sq[(size_t)i] = (int32_t)floorf(c * c); }
+        return sq;
+    }
+
+    /* ground_local_plan() for a robot that is a rectangle (include/gie.h "ground footprints"): the same n arcs, and beside every pose
+     * its heading (lround(32767 cos theta), lround(32767 sin theta)) in `headings` (n * T * 2 int32).  The arcs are scored by
+     * gie_ground_rollouts exactly as ground_local_plan() scores them (records), then by gie_ground_footprints with
+     * ground_footprint_sq(), the margin flag and clearance_sq = 0 (footprints: the rectangle itself, no disc around it).  Returns
+     * the best arc by ground_local_plan()'s order among those it admits whose footprint record has poses >= 2 as well: as there, an
+     * arc that is blocked further on is still a motion to command now, the next call looks again; -1 when there is none, and -1 with
+     * everything left alone while the band or "ground/footprint" is not set. */
+    int ground_local_plan_footprint(float yaw, const float *v, const float *omega, int n, float dt, int T, float inflate_radius, std::vector<float> &poses,
+                                    std::vector<int32_t> &headings, std::vector<gie_ground_rollout> &records, std::vector<gie_ground_footprint> &footprints)
+    {
+        if (param.ground_max_height < param.ground_min_height) return -1;
+        if (param.ground_footprint[0] < 0.f || param.ground_footprint[1] < 0.f || param.ground_footprint[2] < 0.f) return -1;
+        if (n < 0 || T < 1 || T > GIE_GROUND_ROLLOUT_MAX_POSES) throw std::invalid_argument("ground_local_plan_footprint: n >= 0, T in 1..4096");
+        ground_arcs_(yaw, v, omega, n, dt, T, poses, &headings);
+        ground_score_arcs_(poses, n, T, inflate_radius, records);
+        const std::array<int32_t, 3> sq = ground_footprint_sq();
+        gie_ground_footprint_param p = {};
+        p.front_sq = sq[0]; p.back_sq = sq[1]; p.side_sq = sq[2];
+        p.clearance_sq = 0;
+        p.flags = GIE_GROUND_FOOTPRINT_MARGIN;
+        footprints.assign((size_t)n, gie_ground_footprint{});
+        chk(gie_ground_footprints(m_, poses.data(), headings.data(), n, T, &p, footprints.data()));
+        int best = -1;
+        for (int i = 0; i < n; i++) {
+            const gie_ground_rollout &r = records[(size_t)i];
+            if (r.poses < 2 || r.nf1_min < 0 || footprints[(size_t)i].poses < 2) continue;
             if (best < 0 || r.nf1_min < records[(size_t)best].nf1_min || (r.nf1_min == records[(size_t)best].nf1_min && r.cost < records[(size_t)best].cost)) best = i;
         }
         return best;
@@ -930,6 +966,38 @@ private:
     gie_config cfg_;
     gie_mapper *m_ = nullptr;
     float robot_pos_[3] = { 0.f, 0.f, 0.f };      /* of the last publishMap (after ugv_height) */
+
+    /* the arcs of ground_local_plan(): pose 0 is the robot, then x += v dt cos(theta), y += v dt sin(theta), theta += omega dt, in
+     * double, stored as float; with `headings` the heading of every pose too */
+    void ground_arcs_(float yaw, const float *v, const float *omega, int n, float dt, int T, std::vector<float> &poses, std::vector<int32_t> *headings) const
+    {
+        poses.resize((size_t)n * T * 2);
+        if (headings) headings->resize((size_t)n * T * 2);
+        for (int i = 0; i < n; i++) {
+            double x = robot_pos_[0], y = robot_pos_[1], th = yaw;
+            for (int k = 0; k < T; k++) {
+                float *q = poses.data() + 2 * ((size_t)i * T + k);
+                q[0] = (float)x; q[1] = (float)y;
+                if (headings) {
+                    int32_t *h = headings->data() + 2 * ((size_t)i * T + k);
+                    h[0] = (int32_t)std::lround(32767.0 * std::cos(th)); h[1] = (int32_t)std::lround(32767.0 * std::sin(th));
+                }
+                x += (double)v[i] * dt * std::cos(th); y += (double)v[i] * dt * std::sin(th);
+                th += (double)omega[i] * dt;
+            }
+        }
+    }
+    /* ground_local_plan()'s scoring: gie_ground_rollouts at ground_clearance_sq() with the NF1 flag */
+    void ground_score_arcs_(const std::vector<float> &poses, int n, int T, float inflate_radius, std::vector<gie_ground_rollout> &records)
+    {
+        gie_ground_rollout_param p = {};
+        p.clearance_sq = ground_clearance_sq();
+        const int cells = (int)ceilf(inflate_radius / cfg_.voxel_width);
+        p.inflate_sq = cells * cells;
+        p.flags = GIE_GROUND_ROLLOUT_NF1;
+        records.assign((size_t)n, gie_ground_rollout{});
+        chk(gie_ground_rollouts(m_, poses.data(), n, T, &p, records.data()));
+    }
     void *explore_dev_ = nullptr; size_t explore_cap_ = 0;     /* exploration_costs' device buffer and its host copy */
     std::vector<char> explore_host_;
     bool streaming_ = false;

@@ -1126,6 +1126,82 @@ typedef struct gie_ground_rollout {         /* 48 bytes */
 int gie_ground_rollouts(gie_mapper *h, const float *xy, int n, int T, const gie_ground_rollout_param *p, gie_ground_rollout *out);
 int gie_ground_rollouts_dev(gie_mapper *h, const float *d_xy, int n, int T, const gie_ground_rollout_param *p, gie_ground_rollout *d_out);
 
+/* ---- ground footprints: the poses of n candidate trajectories tested as ORIENTED RECTANGLES of cells on the ground costmap — the
+ * step of a costmap-based local planner (DWA, trajectory rollout, MPPI with a footprint critic) between "sampled a trajectory" and
+ * "scored it".  Every other rule of the ground stack takes the robot for a disc and tests one cell against clearance_sq; a
+ * 1.0 m x 0.6 m base does not enter a 0.8 m corridor at its circumscribed radius, and its corners pass through walls at its
+ * inscribed one.  Here a pose has a heading, the reference point may lie anywhere on the long axis (front and back extents), and
+ * one call returns ONE record per trajectory.  No counterpart in the reference's code.
+ *
+ * Every call refers to the ground field that is valid where the call is enqueued (the rule of "ground line of sight"): there is no
+ * prepare call and no kept result, a later gie_ground_compute* makes later calls see the new field, a map update changes nothing.
+ * Neither the field nor the ground navigation function is written.  Everything is an integer and exact: a result depends on no
+ * schedule.  The poses are tested one by one, not the area swept between them: sample at a cell or less.
+ *  poses         xy and heading are laid out as the rollouts' xy: pose k of trajectory i is at xy[2 * (i * T + k)] (two floats,
+ *                metres, world frame) and heading[2 * (i * T + k)] (two int32, hx, hy: a direction vector of any length).
+ *  placement     a pose has NO placement when its xy has no cell by the rollouts' rule (not finite, beyond int32, outside the
+ *                field's rectangle), when its heading is (0, 0), or when a heading component is beyond +-32767.  The same in the
+ *                host and _dev forms: neither scans the arrays on the host.  A NaN or zero-heading tail is the way to pass
+ *                trajectories shorter than T.
+ *  footprint     with c the pose's cell and, for any cell v inside the rectangle or not, d = v - c, n2 = hx^2 + hy^2,
+ *                a = dx hx + dy hy, b = dx hy - dy hx: v is a FOOTPRINT cell iff, in int64 arithmetic, b^2 <= side_sq n2 and
+ *                a^2 <= (a >= 0 ? front_sq : back_sq) n2.  front_sq, back_sq, side_sq are squared cells in
+ *                0 .. GIE_GROUND_FOOTPRINT_MAX_SQ (no product reaches 2^63).  c is always a footprint cell; every footprint cell has
+ *                |d|^2 <= max(front_sq, back_sq) + side_sq (a^2 + b^2 = |d|^2 n2); every row of the footprint is one interval of
+ *                x.  A positive integer multiple of the heading gives the same set; with all three extents 0 it is c alone.
+ *  blocked       a footprint cell inside the rectangle: the rule of "ground line of sight" with clearance_sq and
+ *                GIE_GROUND_FOOTPRINT_UNKNOWN_TRAVERSABLE — clearance_sq pads the rectangle by a disc.  A footprint cell outside
+ *                the rectangle is an UNKNOWN column without a dist_sq: blocked without the flag, not blocked with it.
+ *  poses         m, the number of leading poses that have a placement and no blocked footprint cell, 0 .. T.
+ *  end           0 when m == T; otherwise 2 when pose m has no placement; otherwise 1: hit is the blocked footprint cell of pose m
+ *                that is least in (y, x) lexicographic order of signed local coordinates, reported in GLOBAL cell coordinates
+ *                (local + pivot; it may lie outside the rectangle), and hit_cells the number of blocked footprint cells of pose
+ *                m.  In the other cases hit is 0, 0 and hit_cells 0.
+ *  margin        with GIE_GROUND_FOOTPRINT_MARGIN, min_dist_sq is the minimum of the field's dist_sq over the footprint cells of
+ *                poses 0 .. m - 1 that lie inside the rectangle (-1 on a field without an obstacle column) and min_at the FIRST
+ *                pose that attains it: the footprint critic's score.  With m == 0 they are 0 and -1.  Without the flag both are
+ *                -2 and dist_sq is not read.
+ *  mask          gie_ground_footprint_mask*: ONE pose (T = 1); mask is X * Y bytes, x fastest: 0 not a footprint cell, 1 a
+ *                footprint cell that is not blocked, 2 a blocked footprint cell.  Footprint cells outside the rectangle have no
+ *                byte but count in the record, which is the T = 1 record of that pose.  A pose without a placement gives an all-0
+ *                mask and end = 2.  rec may be NULL.
+ * GIE_ERR_INVALID, nothing written: a NULL handle or param; a tiled mapper; no ground field yet; an extent outside its range;
+ *  clearance_sq < 0; an unknown flag; non-zero reserved; n < 0; T outside 1 .. GIE_GROUND_ROLLOUT_MAX_POSES; n > 0 with a NULL xy,
+ *  heading or out; a NULL mask; in the host form, n * T * 16 bytes beyond size_t.  n == 0 is valid and launches nothing; n has no
+ *  upper limit.
+ * The host forms stage through the two scratch slots of the host forms (the poses and the headings share the first) and synchronise.
+ *  The _dev forms take DEVICE buffers and are enqueued on the mapper's stream (gie_get_stream) with no host wait, no read-back and
+ *  no grid barrier.
+ * Memory: nothing of its own: the blocked bit plane is the one of "ground line of sight", allocated by the first call of either.
+ * Cost: a call is two launches: the blocked plane, as there, and the footprints: a wave per trajectory, the poses in order, a lane
+ *  per footprint row testing the masked 64-bit words of its interval; the first pose that ends the prefix is the last one looked
+ *  at.  The mask forms zero the mask with a memset in front of the two launches.
+ * gie_profile_read: counted under "ground_query". */
+#define GIE_GROUND_FOOTPRINT_UNKNOWN_TRAVERSABLE 1   /* as GIE_GROUND_LOS_UNKNOWN_TRAVERSABLE; footprint cells outside the rectangle do not block */
+#define GIE_GROUND_FOOTPRINT_MARGIN              2   /* min_dist_sq and min_at over the clear prefix's footprints */
+#define GIE_GROUND_FOOTPRINT_MAX_SQ (1 << 16)
+typedef struct gie_ground_footprint_param {  /* 32 bytes */
+    int32_t front_sq;       /* squared cells ahead of the reference point along the heading, 0 .. GIE_GROUND_FOOTPRINT_MAX_SQ */
+    int32_t back_sq;        /* behind it */
+    int32_t side_sq;        /* to either side: the half width */
+    int32_t clearance_sq;   /* blocked = ground line of sight's rule, squared cells, >= 0 */
+    int32_t flags;          /* GIE_GROUND_FOOTPRINT_* */
+    int32_t reserved[3];    /* must be 0 */
+} gie_ground_footprint_param;
+typedef struct gie_ground_footprint {        /* 32 bytes */
+    int32_t end;            /* 0 complete, 1 blocked, 2 pose `poses` has no placement */
+    int32_t poses;          /* m: the poses of the clear prefix, 0 .. T */
+    int32_t hit[2];         /* end == 1: the least blocked footprint cell of pose m in (y, x) order, global cell coordinates; otherwise 0, 0 */
+    int32_t hit_cells;      /* end == 1: the blocked footprint cells of pose m; otherwise 0 */
+    int32_t min_dist_sq;    /* over the inside footprint cells of poses 0 .. m - 1; -1 no obstacle column; 0 when m == 0; -2 without the flag */
+    int32_t min_at;         /* the first pose that attains it; -1 when m == 0; -2 without the flag */
+    int32_t reserved;       /* 0 */
+} gie_ground_footprint;
+int gie_ground_footprints(gie_mapper *h, const float *xy, const int32_t *heading, int n, int T, const gie_ground_footprint_param *p, gie_ground_footprint *out);
+int gie_ground_footprints_dev(gie_mapper *h, const float *d_xy, const int32_t *d_heading, int n, int T, const gie_ground_footprint_param *p, gie_ground_footprint *d_out);
+int gie_ground_footprint_mask(gie_mapper *h, const float *xy, const int32_t *heading, const gie_ground_footprint_param *p, uint8_t *mask, gie_ground_footprint *rec);
+int gie_ground_footprint_mask_dev(gie_mapper *h, const float *d_xy, const int32_t *d_heading, const gie_ground_footprint_param *p, uint8_t *d_mask, gie_ground_footprint *d_rec);
+
 /* ---- goal-to-goal cost matrix: the path lengths among up to 64 points (the robot and the goals of the frontier clusters, say), the
  * input of every tour-based explorer — in which order to visit the clusters.  n fields of gie_nf1_compute would give the same
  * numbers with n persistent launches and n whole fields; here ONE level-synchronous pass advances all searches, a 64-bit mask per
