@@ -100,6 +100,15 @@ struct gie_gnf1_cache {
     int32_t *words = nullptr;             /* control words */
     int valid = 0;                        /* a compute has been enqueued on the current ground field */
 };
+/* the ground pose navigation function (gie_ground_pose_nf1.inc.h): allocated at its first compute through gie_dalloc, kept until the
+ * next compute; it refers to the ground field's pivot and is invalidated by the next gie_ground_compute* */
+struct gie_gpose_cache {
+    int32_t *f = nullptr;                 /* the field, 8 * X * Y */
+    uint64_t *bits = nullptr;             /* four bit planes of eight layers */
+    int32_t *words = nullptr;             /* control words */
+    int valid = 0;                        /* a compute has been enqueued on the current ground field */
+    int reverse = 0;                      /* that compute had GIE_GROUND_POSE_NF1_REVERSE */
+};
 /* the ground frontier clusters (gie_ground_frontier.inc.h): allocated at their first compute through gie_dalloc, kept until the next
  * compute; they refer to the ground field's pivot and are invalidated by the next gie_ground_compute* */
 struct gie_gfr_cache {
@@ -162,6 +171,7 @@ struct gie_mapper {
     gie_los_cache los;                    /* line of sight (HIP backend: gie_los.inc.h) */
     gie_ground_cache ground;              /* the ground costmap (HIP backend: gie_ground.inc.h) */
     gie_gnf1_cache gnf1;                  /* the ground navigation function (HIP backend: gie_ground_nf1.inc.h) */
+    gie_gpose_cache gpose;                /* the ground pose navigation function (HIP backend: gie_ground_pose_nf1.inc.h) */
     uint64_t *glos_blk = nullptr;         /* ground line of sight (HIP backend: gie_ground_los.inc.h): the blocked bit plane, allocated at the first call and rebuilt by every call */
     gie_gfr_cache gfr;                    /* the ground frontier clusters (HIP backend: gie_ground_frontier.inc.h) */
     gie_gcm_cache gcm;                    /* the ground cost matrix's scratch (HIP backend: gie_ground_costmat.inc.h) */

@@ -184,6 +184,11 @@ class GroundFootprint(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class GroundPoseNf1Param(C.Structure):
+    """gie_ground_pose_nf1_param (include/gie.h): 32 bytes; the three extents and clearance_sq in squared cells."""
+    _fields_ = [("front_sq", C.c_int32), ("back_sq", C.c_int32), ("side_sq", C.c_int32), ("clearance_sq", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 class GroundFrontierParam(C.Structure):
     """gie_ground_frontier_param (include/gie.h): 32 bytes; clearance_sq in squared cells."""
     _fields_ = [("clearance_sq", C.c_int32), ("min_size", C.c_int32), ("connectivity", C.c_int32), ("max_clusters", C.c_int32),
@@ -197,6 +202,7 @@ class GroundFrontierCluster(C.Structure):
 
 
 assert C.sizeof(GroundFrontierParam) == 32 and C.sizeof(GroundFrontierCluster) == 64 and GroundFrontierCluster.sum.offset == 40
+assert C.sizeof(GroundPoseNf1Param) == 32 and GroundPoseNf1Param.flags.offset == 16
 assert C.sizeof(GroundFootprintParam) == 32 and C.sizeof(GroundFootprint) == 32 and GroundFootprintParam.flags.offset == 16 and GroundFootprint.hit_cells.offset == 16
 assert C.sizeof(GroundRolloutParam) == 32 and C.sizeof(GroundRollout) == 48 and GroundRollout.cost.offset == 24 and GroundRollout.nf1_end.offset == 32
 assert C.sizeof(GroundViewParam) == 32 and GroundViewParam.n_planes.offset == 8 and GroundViewParam.reserved.offset == 16
@@ -223,6 +229,11 @@ GROUND_ROLLOUT_MAX_POSES = 4096
 GROUND_FOOTPRINT_UNKNOWN_TRAVERSABLE = 1
 GROUND_FOOTPRINT_MARGIN = 2
 GROUND_FOOTPRINT_MAX_SQ = 1 << 16
+GROUND_POSE_NF1_UNKNOWN_TRAVERSABLE = 1
+GROUND_POSE_NF1_FROM_FRONTIERS = 2
+GROUND_POSE_NF1_REVERSE = 4
+GROUND_POSE_HEADINGS = 8
+GROUND_POSE_MAX_SQ = 1 << 12
 VOX_UNKNOWN, VOX_FREE, VOX_OCCUPIED, VOX_FNT = 0, 1, 2, 3
 
 
@@ -402,6 +413,15 @@ DEVICE_ONLY = {
     "ground_footprints_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(GroundFootprintParam), C.c_void_p]),
     "ground_footprint_mask": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.POINTER(GroundFootprintParam), C.c_void_p, C.c_void_p]),
     "ground_footprint_mask_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.POINTER(GroundFootprintParam), C.c_void_p, C.c_void_p]),
+    # ground pose navigation function: NF1 over (cell, heading) states of an oriented rectangle (include/gie.h): device library only
+    "ground_pose_nf1_compute": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(GroundPoseNf1Param), C.c_void_p]),
+    "ground_pose_nf1_compute_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(GroundPoseNf1Param), C.c_void_p]),
+    "read_ground_pose_nf1": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
+    "read_ground_pose_nf1_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
+    "ground_pose_nf1_query": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "ground_pose_nf1_query_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "ground_pose_nf1_path": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "ground_pose_nf1_path_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     # goal-to-goal cost matrix of the local volume (include/gie.h): device library only
     "costmat_compute": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(Nf1Param), C.c_void_p, C.c_void_p]),
     "costmat_compute_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(Nf1Param), C.c_void_p, C.c_void_p]),

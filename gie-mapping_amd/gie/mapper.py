@@ -13,8 +13,8 @@ import sys
 import numpy as np
 
 from . import _capi
-from ._capi import CLOUD_DIST, CLOUD_TYPE, GROUND_FOOTPRINT_MARGIN, GROUND_FOOTPRINT_MAX_SQ, GROUND_FOOTPRINT_UNKNOWN_TRAVERSABLE, GROUND_LOS_UNKNOWN_TRAVERSABLE, GROUND_NF1_FROM_FRONTIERS, GROUND_NF1_UNKNOWN_TRAVERSABLE, GROUND_ROLLOUT_MAX_POSES, GROUND_ROLLOUT_NF1, GROUND_ROLLOUT_UNKNOWN_TRAVERSABLE, GROUND_UNKNOWN_BLOCKS, GROUND_VIEW_UNION, GROUND_VIEW_UNKNOWN_OPAQUE, LOS_UNKNOWN_OPAQUE, NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE, VOX_FNT, VOX_FREE, VOX_OCCUPIED, VOX_UNKNOWN
-from ._capi import CamParam, CloudParam, Config, CostMapHdr, FrameStats, FrontierParam, GroundFootprintParam, GroundFrontierParam, GroundLosParam, GroundNf1Param, GroundParam, GroundRolloutParam, GroundShortcutParam, GroundViewParam, LosParam, MultiScanParam, Nf1Param, ScanParam, ShortcutParam, ViewParam, Voxel
+from ._capi import CLOUD_DIST, CLOUD_TYPE, GROUND_POSE_HEADINGS, GROUND_POSE_MAX_SQ, GROUND_POSE_NF1_FROM_FRONTIERS, GROUND_POSE_NF1_REVERSE, GROUND_POSE_NF1_UNKNOWN_TRAVERSABLE, GROUND_FOOTPRINT_MARGIN, GROUND_FOOTPRINT_MAX_SQ, GROUND_FOOTPRINT_UNKNOWN_TRAVERSABLE, GROUND_LOS_UNKNOWN_TRAVERSABLE, GROUND_NF1_FROM_FRONTIERS, GROUND_NF1_UNKNOWN_TRAVERSABLE, GROUND_ROLLOUT_MAX_POSES, GROUND_ROLLOUT_NF1, GROUND_ROLLOUT_UNKNOWN_TRAVERSABLE, GROUND_UNKNOWN_BLOCKS, GROUND_VIEW_UNION, GROUND_VIEW_UNKNOWN_OPAQUE, LOS_UNKNOWN_OPAQUE, NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE, VOX_FNT, VOX_FREE, VOX_OCCUPIED, VOX_UNKNOWN
+from ._capi import CamParam, CloudParam, Config, CostMapHdr, FrameStats, FrontierParam, GroundFootprintParam, GroundFrontierParam, GroundLosParam, GroundNf1Param, GroundParam, GroundPoseNf1Param, GroundRolloutParam, GroundShortcutParam, GroundViewParam, LosParam, MultiScanParam, Nf1Param, ScanParam, ShortcutParam, ViewParam, Voxel
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG, "csrc", "libgie_hip.so")
@@ -1158,6 +1158,85 @@ class Mapper(MapperBase):
         p = self.ground_footprint_param(front_sq, back_sq, side_sq, clearance_sq, unknown_traversable, margin)
         self._chk(self._f["ground_footprint_mask_dev"](self._h, C.c_void_p(d_xy or None), C.c_void_p(d_heading or None), C.byref(p), C.c_void_p(d_mask or None),
                                                        C.c_void_p(d_rec or None)))
+
+    # --- ground pose navigation function: NF1 over (cell, heading) states of an oriented rectangle (include/gie.h) ---
+    def ground_pose_nf1_param(self, front_sq, back_sq, side_sq, clearance_sq=0, unknown_traversable=False, from_frontiers=False, reverse=False):
+        """gie_ground_pose_nf1_param: the extents and clearance_sq in squared CELLS."""
+        p = GroundPoseNf1Param()
+        p.front_sq, p.back_sq, p.side_sq, p.clearance_sq = int(front_sq), int(back_sq), int(side_sq), int(clearance_sq)
+        p.flags = ((GROUND_POSE_NF1_UNKNOWN_TRAVERSABLE if unknown_traversable else 0) | (GROUND_POSE_NF1_FROM_FRONTIERS if from_frontiers else 0) |
+                   (GROUND_POSE_NF1_REVERSE if reverse else 0))
+        return p
+
+    @staticmethod
+    def _pose_arrays(who, xy, k):
+        xy = np.ascontiguousarray(np.asarray(xy if xy is not None else [], dtype=np.float32).reshape(-1, 2))
+        if k is not None:
+            k = np.ascontiguousarray(np.asarray(k, dtype=np.int32).reshape(-1))
+            if len(k) != len(xy):
+                raise ValueError(who + ": one heading index per point")
+        return xy, k
+
+    def ground_pose_nf1_compute(self, goals, goal_k, front_sq, back_sq, side_sq, clearance_sq=0, unknown_traversable=False, from_frontiers=False,
+                                reverse=False):
+        """The pose navigation function of the current ground field from n goals (n x 2 metres, world frame; goal_k: n heading
+        indices 0..7, -1 = all eight, or None) -> [source states, free states] (synchronises)."""
+        xy, k = self._pose_arrays("ground_pose_nf1_compute", goals, goal_k)
+        n = len(xy)
+        counts = np.zeros(2, np.int32)
+        p = self.ground_pose_nf1_param(front_sq, back_sq, side_sq, clearance_sq, unknown_traversable, from_frontiers, reverse)
+        self._chk(self._f["ground_pose_nf1_compute"](self._h, _ptr(xy) if n else None, _ptr(k) if k is not None and n else None, n, C.byref(p), _ptr(counts)))
+        return [int(counts[0]), int(counts[1])]
+
+    def ground_pose_nf1_compute_dev(self, d_goals, d_goal_k, n, d_counts, front_sq, back_sq, side_sq, clearance_sq=0, unknown_traversable=False,
+                                    from_frontiers=False, reverse=False):
+        """The same with the goals (n x 2 float32), their heading indices (n int32; 0 = all eight) and the counts (2 int32; 0 = not
+        wanted) in DEVICE buffers (raw addresses), on the mapper's stream; the host does not wait."""
+        p = self.ground_pose_nf1_param(front_sq, back_sq, side_sq, clearance_sq, unknown_traversable, from_frontiers, reverse)
+        self._chk(self._f["ground_pose_nf1_compute_dev"](self._h, C.c_void_p(d_goals or None), C.c_void_p(d_goal_k or None), int(n), C.byref(p),
+                                                         C.c_void_p(d_counts or None)))
+
+    def read_ground_pose_nf1(self):
+        """(pnf1 int32 [8][Y][X], cspace uint8 [Y][X]: bit k set iff (cell, k) is not free) (synchronises)."""
+        f = np.empty((GROUND_POSE_HEADINGS, self.size[1], self.size[0]), np.int32)
+        cs = np.empty((self.size[1], self.size[0]), np.uint8)
+        self._chk(self._f["read_ground_pose_nf1"](self._h, _ptr(f), _ptr(cs)))
+        return f, cs
+
+    def read_ground_pose_nf1_dev(self, d_pnf1, d_cspace):
+        """The field (8 * X * Y int32) and the C-space bytes (X * Y) into DEVICE buffers (raw addresses; 0 = not wanted, not both),
+        asynchronous on the mapper's stream."""
+        self._chk(self._f["read_ground_pose_nf1_dev"](self._h, C.c_void_p(d_pnf1 or None), C.c_void_p(d_cspace or None)))
+
+    def ground_pose_nf1_query(self, xy, k=None):
+        """The current pose navigation function at n states (xy: n x 2 metres; k: n heading indices, -1 = the least over the eight,
+        None = -1 for all): int32 [n] moves, -1 where there is none (synchronises)."""
+        xy, k = self._pose_arrays("ground_pose_nf1_query", xy, k)
+        n = len(xy)
+        out = np.zeros(n, np.int32)
+        self._chk(self._f["ground_pose_nf1_query"](self._h, _ptr(xy) if n else None, _ptr(k) if k is not None and n else None, n, _ptr(out) if n else None))
+        return out
+
+    def ground_pose_nf1_query_dev(self, d_xy, d_k, n, d_steps):
+        """n points (n x 2 float32), their heading indices (n int32, or 0) and the moves (n int32) in DEVICE buffers, on the mapper's stream."""
+        self._chk(self._f["ground_pose_nf1_query_dev"](self._h, C.c_void_p(d_xy or None), C.c_void_p(d_k or None), int(n), C.c_void_p(d_steps or None)))
+
+    def ground_pose_nf1_path(self, starts, start_k, max_len, fill=0):
+        """Descents from n start states -> (path int32 [n][max_len][3] GLOBAL x, y and heading index, len int32 [n]); triples beyond
+        min(len, max_len) keep `fill` (synchronises)."""
+        xy, k = self._pose_arrays("ground_pose_nf1_path", starts, start_k)
+        n = len(xy)
+        path = np.full((n, int(max_len), 3), fill, np.int32)
+        ln = np.zeros(n, np.int32)
+        self._chk(self._f["ground_pose_nf1_path"](self._h, _ptr(xy) if n else None, _ptr(k) if k is not None and n else None, n, int(max_len),
+                                                  _ptr(path) if n else None, _ptr(ln) if n else None))
+        return path, ln
+
+    def ground_pose_nf1_path_dev(self, d_starts, d_start_k, n, max_len, d_path, d_len):
+        """n starts (n x 2 float32), their heading indices (n int32, or 0), the triples (n x max_len x 3 int32) and the lengths (n
+        int32) in DEVICE buffers (raw addresses), on the mapper's stream."""
+        self._chk(self._f["ground_pose_nf1_path_dev"](self._h, C.c_void_p(d_starts or None), C.c_void_p(d_start_k or None), int(n), int(max_len),
+                                                      C.c_void_p(d_path or None), C.c_void_p(d_len or None)))
 
     def read_costmap_ground_nf1(self):
         """The one-layer TYPE_NF1 CostMap of the ground navigation function: (SeenDist payload [Y][X], header) (synchronises)."""

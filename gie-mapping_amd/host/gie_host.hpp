@@ -731,6 +731,57 @@ public:
         return best;
     }
 
+    /* The heading index of "ground pose navigation function" nearest to yaw (radians): lround(yaw / (pi / 4)) taken mod 8 into 0..7;
+     * index k looks along d_k, counter-clockwise from +x. */
+    static int ground_heading_index(double yaw)
+    {
+        const long r = std::lround(yaw / 0.78539816339744830962);
+        return (int)(((r % 8) + 8) % 8);
+    }
+
+    /* ground_plan() for a robot that is a rectangle (include/gie.h "ground pose navigation function"): the ground field of the band
+     * exactly as ground_plan() computes it, then the pose navigation function with ground_footprint_sq() and clearance_sq = 0 (the
+     * rectangle itself, no disc around it; an extent beyond GIE_GROUND_POSE_MAX_SQ is refused by the library: the call throws) from
+     * n goals — goal_yaw may be NULL, and a NaN entry means any heading; otherwise goal i counts at ground_heading_index(goal_yaw[i])
+     * — or, with from_frontiers, from the FNT cells too; with `reverse` the robot may back up.  ONE descent from the robot's position
+     * of the last publishMap at ground_heading_index(yaw): at most max_len triples GLOBAL cell x, y and heading index, the robot's
+     * state first; empty when no source can be reached.  ground_pose_plan_len = the descent's full length (moves + 1),
+     * ground_pose_plan_sources = the number of source states.  ground_plan()'s own field and results are not touched.  Returns false,
+     * and leaves everything alone, while the band or "ground/footprint" is not set. */
+    bool ground_plan_footprint(float yaw, const float *goal_xy, const float *goal_yaw, int n, bool from_frontiers, bool reverse, int max_len,
+                               std::vector<std::array<int32_t, 3>> &path)
+    {
+        if (param.ground_max_height < param.ground_min_height) return false;
+        if (param.ground_footprint[0] < 0.f || param.ground_footprint[1] < 0.f || param.ground_footprint[2] < 0.f) return false;
+        const float w = cfg_.voxel_width;
+        gie_ground_param g = {};
+        g.z_lo = (int32_t)std::floor(param.ground_min_height / w + 0.5f);      /* as ground_plan() */
+        g.z_hi = (int32_t)std::floor(param.ground_max_height / w + 0.5f);
+        g.min_known = param.ground_min_known;
+        chk(gie_ground_compute(m_, &g, ground_counts));
+        const std::array<int32_t, 3> sq = ground_footprint_sq();
+        gie_ground_pose_nf1_param p = {};
+        p.front_sq = sq[0]; p.back_sq = sq[1]; p.side_sq = sq[2];
+        p.clearance_sq = 0;
+        p.flags = (from_frontiers ? GIE_GROUND_POSE_NF1_FROM_FRONTIERS : 0) | (reverse ? GIE_GROUND_POSE_NF1_REVERSE : 0);
+        std::vector<int32_t> gk;
+        if (goal_yaw) {
+            gk.resize((size_t)std::max(n, 0));
+            for (size_t i = 0; i < gk.size(); i++) gk[i] = std::isnan(goal_yaw[i]) ? -1 : ground_heading_index((double)goal_yaw[i]);
+        }
+        int32_t counts[2] = { 0, 0 };
+        chk(gie_ground_pose_nf1_compute(m_, goal_xy, goal_yaw ? gk.data() : nullptr, n, &p, counts));
+        ground_pose_plan_sources = counts[0];
+        std::vector<int32_t> xyk((size_t)std::max(max_len, 1) * 3);
+        const int32_t k0 = ground_heading_index((double)yaw);
+        ground_pose_plan_len = 0;
+        chk(gie_ground_pose_nf1_path(m_, robot_pos_, &k0, 1, max_len, xyk.data(), &ground_pose_plan_len));
+        path.resize((size_t)std::min(ground_pose_plan_len, max_len));
+        for (size_t i = 0; i < path.size(); i++) path[i] = { xyk[3 * i], xyk[3 * i + 1], xyk[3 * i + 2] };
+        return true;
+    }
+    int32_t ground_pose_plan_len = 0, ground_pose_plan_sources = 0;      /* of the last ground_plan_footprint() */
+
 #ifdef GIE_HOST_HAS_HIP
     /* A ground robot's goal selection on the map as it stands (include/gie.h "ground frontier clusters"): which frontiers exist, how
      * large they are, where to drive for each and how far that is.  Four steps chained through the _dev forms on the mapper's

@@ -1202,6 +1202,83 @@ int gie_ground_footprints_dev(gie_mapper *h, const float *d_xy, const int32_t *d
 int gie_ground_footprint_mask(gie_mapper *h, const float *xy, const int32_t *heading, const gie_ground_footprint_param *p, uint8_t *mask, gie_ground_footprint *rec);
 int gie_ground_footprint_mask_dev(gie_mapper *h, const float *d_xy, const int32_t *d_heading, const gie_ground_footprint_param *p, uint8_t *d_mask, gie_ground_footprint *d_rec);
 
+/* ---- ground pose navigation function: NF1 over (cell, heading) STATES of an oriented rectangle on the ground costmap — the global
+ * planner of a base that is no disc.  "ground navigation function", "ground cost matrix" and the host layer's ground_plan() know
+ * one number, clearance_sq: at the circumscribed radius a 1.0 m x 0.6 m base finds no route through a door it fits through
+ * lengthwise, at the inscribed one it is sent round a corner it cannot turn in.  This section is the navigation function of the
+ * configuration space "ground footprints" defines: the route length from every pose to the goal, and a descent a rectangular
+ * robot can follow pose by pose.  No counterpart in the reference's code.
+ *
+ * Everything refers to the ground field that is valid where gie_ground_pose_nf1_compute* is enqueued (the rule of "ground
+ * navigation function").  Integers only and exact: a result depends on no schedule.
+ *  states        (c, k): c a cell of the field's X x Y rectangle, k in 0 .. GIE_GROUND_POSE_HEADINGS - 1 a heading, counter-clockwise
+ *                from +x: d_0 = (1, 0), d_1 = (1, 1), d_2 = (0, 1), d_3 = (-1, 1), d_4 = (-1, 0), d_5 = (-1, -1), d_6 = (0, -1),
+ *                d_7 = (1, -1).
+ *  free          (c, k) is free iff the footprint of "ground footprints" placed at c with heading d_k (front_sq, back_sq, side_sq,
+ *                clearance_sq, GIE_GROUND_POSE_NF1_UNKNOWN_TRAVERSABLE with the meaning of GIE_GROUND_FOOTPRINT_UNKNOWN_TRAVERSABLE)
+ *                has no blocked footprint cell; that section's predicate, blocked rule and treatment of footprint cells outside
+ *                the rectangle apply word for word: gie_ground_footprints with T = 1 returns end == 1 for a pose in cell c with
+ *                heading d_k iff (c, k) is not free.  With all three extents 0 a state is free iff its cell is not blocked and
+ *                the eight layers are equal.  The extents are in 0 .. GIE_GROUND_POSE_MAX_SQ (64 cells: every footprint cell within
+ *                90 cells of c, a footprint row at most 181 cells).
+ *  moves         from (c, k): F to (c + d_k, k); B to (c - d_k, k), only with GIE_GROUND_POSE_NF1_REVERSE; L to (c, (k + 1) & 7);
+ *                R to (c, (k + 7) & 7).  A move is admissible when its target lies inside the rectangle and is free.  Only the
+ *                two states are tested, not the area swept between them (as "ground footprints" tests poses one by one).  Every
+ *                move costs 1; a diagonal F covers more ground than an axial one for the same cost.
+ *  sources       the free states among: for goal i, the cell of goal_xy[2i ..] by gie_ground_query's mapping (a goal without a
+ *                cell is ignored: a NaN tail passes) with heading goal_k[i] — 0 .. 7 that one state, -1 all eight, any other value
+ *                the goal is ignored; goal_k == NULL means -1 for every goal — and, with GIE_GROUND_POSE_NF1_FROM_FRONTIERS, every
+ *                (c, k) whose cell is FNT.  n == 0 is valid.
+ *  pnf1          pnf1(c, k) = the least number of admissible moves from (c, k) to a source: 0 on sources, -1 where there is none
+ *                (states that are not free included).  8 * X * Y int32, k slowest: (k * Y + y) * X + x.  Without REVERSE the
+ *                moves are not symmetric: the propagation expands predecessors.
+ *  cspace        X * Y bytes, x fastest: bit k set iff (c, k) is not free.
+ *  counts        two int32: the distinct source states, the free states.  May be NULL.
+ *  query         for each of n (xy, k): k in 0 .. 7 pnf1 at that state; k == -1 the least value >= 0 over the eight headings, or
+ *                -1; no cell, or any other k, -1.  k == NULL means -1 for every point.
+ *  path          for each of n starts (xy, k): len = 0 for a start without a cell, a k outside -1 .. 7 or a value < 0; k == -1 (and
+ *                start_k == NULL) picks the lowest k among those with the least value >= 0.  v_0 is the start state, v_{i+1} the
+ *                first among F, B, L, R of v_i whose value is pnf1(v_i) - 1 (B only if the field was computed with REVERSE).
+ *                len = pnf1 + 1, also when that exceeds max_len.  path_xyk holds max_len triples per start: GLOBAL x, y and k;
+ *                exactly min(len, max_len) are written, the rest is left as it was.
+ * Lifetime: the field is kept until the next gie_ground_pose_nf1_compute*; a gie_ground_compute* invalidates it, as it does the
+ *  ground navigation function (readers, query and path then return GIE_ERR_INVALID); a map update changes nothing.  The ground
+ *  navigation function and this field neither read nor invalidate each other; the ground field and the ground navigation function
+ *  are byte-identical before and after every call of this section.
+ * GIE_ERR_INVALID, nothing written: a NULL handle or param; a tiled mapper; no ground field yet; an extent outside its range;
+ *  clearance_sq < 0; an unknown flag; non-zero reserved; n < 0; n > 0 with a NULL xy or output; max_len < 1; both outputs of the
+ *  reader NULL; a read, query or path before a compute or after an invalidation.
+ * The host forms stage through the two scratch slots of the host forms and synchronise.  The _dev forms take DEVICE buffers and are
+ *  enqueued on the mapper's stream (gie_get_stream) with no host wait, no read-back and no grid barrier; the _dev goal array is
+ *  gie_read_ground_frontier_clusters_dev's goal array, taken with its NaN tail as it is.
+ * Memory: allocated at the first compute, freed by gie_destroy: 36 bytes per cell (the field 32, four bit planes of eight
+ *  layers 4) and four control words; the blocked plane is the one of "ground line of sight".  A mapper that never calls the section
+ *  allocates and launches nothing.
+ * Cost: a compute is the blocked plane, the C-space (bit-parallel: shifted ORs of blocked words), the sources, and ONE workgroup
+ *  that runs the levels with one workgroup barrier each, in LDS up to 768 words per layer, on global planes beyond.
+ * gie_profile_read: the section adds no name; every call is counted under "ground_nf1", one entry per call. */
+#define GIE_GROUND_POSE_NF1_UNKNOWN_TRAVERSABLE 1   /* as GIE_GROUND_FOOTPRINT_UNKNOWN_TRAVERSABLE */
+#define GIE_GROUND_POSE_NF1_FROM_FRONTIERS      2   /* every state of an FNT cell is a source candidate */
+#define GIE_GROUND_POSE_NF1_REVERSE             4   /* the move B */
+#define GIE_GROUND_POSE_HEADINGS 8
+#define GIE_GROUND_POSE_MAX_SQ (1 << 12)
+typedef struct gie_ground_pose_nf1_param {   /* 32 bytes */
+    int32_t front_sq;       /* squared cells ahead of the reference point along the heading, 0 .. GIE_GROUND_POSE_MAX_SQ */
+    int32_t back_sq;        /* behind it */
+    int32_t side_sq;        /* to either side: the half width */
+    int32_t clearance_sq;   /* blocked = ground line of sight's rule, squared cells, >= 0 */
+    int32_t flags;          /* GIE_GROUND_POSE_NF1_* */
+    int32_t reserved[3];    /* must be 0 */
+} gie_ground_pose_nf1_param;
+int gie_ground_pose_nf1_compute(gie_mapper *h, const float *goal_xy, const int32_t *goal_k, int n, const gie_ground_pose_nf1_param *p, int32_t *counts);
+int gie_ground_pose_nf1_compute_dev(gie_mapper *h, const float *d_goal_xy, const int32_t *d_goal_k, int n, const gie_ground_pose_nf1_param *p, int32_t *d_counts);
+int gie_read_ground_pose_nf1(gie_mapper *h, int32_t *pnf1, uint8_t *cspace);
+int gie_read_ground_pose_nf1_dev(gie_mapper *h, int32_t *d_pnf1, uint8_t *d_cspace);
+int gie_ground_pose_nf1_query(gie_mapper *h, const float *xy, const int32_t *k, int n, int32_t *steps);
+int gie_ground_pose_nf1_query_dev(gie_mapper *h, const float *d_xy, const int32_t *d_k, int n, int32_t *d_steps);
+int gie_ground_pose_nf1_path(gie_mapper *h, const float *start_xy, const int32_t *start_k, int n, int max_len, int32_t *path_xyk, int32_t *len);
+int gie_ground_pose_nf1_path_dev(gie_mapper *h, const float *d_start_xy, const int32_t *d_start_k, int n, int max_len, int32_t *d_path_xyk, int32_t *d_len);
+
 /* ---- goal-to-goal cost matrix: the path lengths among up to 64 points (the robot and the goals of the frontier clusters, say), the
  * input of every tour-based explorer — in which order to visit the clusters.  n fields of gie_nf1_compute would give the same
  * numbers with n persistent launches and n whole fields; here ONE level-synchronous pass advances all searches, a 64-bit mask per
