@@ -41,6 +41,59 @@ GIE_DEV int gie_ground_nobs(const gie_ground_dev &s)
     const volatile int32_t *n = s.cnt;
     return n[GIE_VOX_OCCUPIED] + ((s.flags & GIE_GROUND_UNKNOWN_BLOCKS) ? n[GIE_VOX_UNKNOWN] : 0);
 }
+/* THE cell of a point (metres) for every ground entry: gie_pos2coord less the field's pivot; false outside the rectangle and for a
+ * coordinate that is NaN, inf or beyond what an int32 holds (v[k] = 0 there; outside the rectangle v holds the cell all the same).
+ * Five kernels spell the same loop out.  k_ground_query, k_gnf1_goals, k_gnf1_path, k_gnf1_query: the compiler makes the function
+ * branch-free, which costs those four 3 to 5 registers (profiles/r28_ground_helpers_kernels.txt).  k_gcostmat: with the function one
+ * of its times lay above the parent's range (profiles/r28_ground_helpers_times.txt).  tests/test_ground_gpu.py holds all of them and
+ * the callers of this function to one table of points */
+GIE_DEV bool gie_ground_cell_of(const float w, const int X, const int Y, const int *pvt, const float *xy, int v[2])
+{
+    const int S[2] = { X, Y };
+    int r[2] = { 0, 0 };
+    bool in = true;
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        const float u = floorf(xy[k] / w + 0.5f);               /* gie_pos2coord */
+        if (!(u >= -1.0e9f && u <= 1.0e9f)) { in = false; continue; }
+        r[k] = (int)u - pvt[k];
+        in &= r[k] >= 0 && r[k] < S[k];
+    }
+    v[0] = r[0]; v[1] = r[1];
+    return in;
+}
+/* a robot may stand on cell id: FREE or FNT (UNKNOWN too with unknown_ok), and no obstacle column nearer than clearance_sq */
+GIE_DEV bool gie_ground_traversable(const gie_ground_dev &g, const int id, const bool none, const int clearance_sq, const int unknown_ok)
+{
+    const int8_t ty = g.type[id];
+    const bool open = ty == GIE_VOX_FREE || ty == GIE_VOX_FNT || (ty == GIE_VOX_UNKNOWN && unknown_ok);
+    return open && (none || g.dist[id] >= clearance_sq);
+}
+/* the 4-neighbour dilation of word wd (word column tx, row y) of a bit plane of W words a row and Y rows */
+GIE_DEV uint64_t gie_ground_dilate4(const uint64_t *F, const int wd, const int tx, const int y, const int W, const int Y)
+{
+    const uint64_t f = F[wd];
+    uint64_t d = f | (f << 1) | (f >> 1);
+    if (tx > 0) d |= F[wd - 1] >> 63;
+    if (tx < W - 1) d |= F[wd + 1] << 63;
+    if (y > 0) d |= F[wd - W];
+    if (y < Y - 1) d |= F[wd + W];
+    return d;
+}
+/* thread tid of T owns the words tid + T k of such a plane: word column and row of the first, and the step between two, without a
+ * division per word */
+struct gie_ground_words { int y, tx, dy, dtx; };
+GIE_DEV gie_ground_words gie_ground_words_first(const int tid, const int T, const int W)
+{
+    gie_ground_words t;
+    t.y = tid / W; t.tx = tid - t.y * W; t.dy = T / W; t.dtx = T - t.dy * W;
+    return t;
+}
+GIE_DEV void gie_ground_words_next(gie_ground_words &t, const int W)
+{
+    t.y += t.dy; t.tx += t.dtx;
+    if (t.tx >= W) { t.tx -= W; t.y++; }
+}
 
 /* one voxel of a column into its reduction: bit k of occ / fnt, the count of known voxels, the highest occupied layer */
 GIE_DEV void gie_ground_voxel(const uint32_t ty, const int k, const int gz, uint32_t &occ, uint32_t &fnt, int &known, int &top)
@@ -247,10 +300,10 @@ __global__ __launch_bounds__(256) void k_ground_query(const gie_ctx c, const gie
     int v[2];
     bool in = true;
 #pragma unroll
-    for (int k = 0; k < 2; k++) {
-        const float u = floorf(xy[2 * (size_t)p + k] / c.voxel_width + 0.5f);      /* gie_pos2coord */
+    for (int k = 0; k < 2; k++) {                               /* gie_ground_cell_of, written out: through the function the kernel takes 18 registers for 13 */
+        const float u = floorf(xy[2 * (size_t)p + k] / c.voxel_width + 0.5f);
         v[k] = 0;
-        if (!(u >= -1.0e9f && u <= 1.0e9f)) { in = false; continue; }             /* (NaN, inf, and what no int32 coordinate holds) */
+        if (!(u >= -1.0e9f && u <= 1.0e9f)) { in = false; continue; }
         v[k] = (int)u - s.pvt[k];
         in &= v[k] >= 0 && v[k] < S[k];
     }
@@ -261,12 +314,23 @@ __global__ __launch_bounds__(256) void k_ground_query(const gie_ctx c, const gie
 }
 
 /* ---- host side */
-static int gie_ground_check(gie_mapper *m, const char *who, bool need_field)
+/* what every ground entry asks first; `what` is the stage's noun for that which a tile's faces would cut */
+static int gie_ground_check(gie_mapper *m, const char *who, bool need_field, const char *what = "field")
 {
     static_assert(sizeof(gie_ground_param) == 32 && sizeof(gie_ground_cell) == 16, "the sizes include/gie.h states");
     if (!m) { gie_set_err(std::string(who) + ": null handle"); return GIE_ERR_INVALID; }
-    if (gie_tiled(m)) { gie_set_err(std::string(who) + ": not for a tiled mapper (its field would stop at the tile's faces)"); return GIE_ERR_INVALID; }
+    if (gie_tiled(m)) { gie_set_err(std::string(who) + ": not for a tiled mapper (its " + what + " would stop at the tile's faces)"); return GIE_ERR_INVALID; }
     if (need_field && !m->ground.valid) { gie_set_err(std::string(who) + ": no ground field yet (gie_ground_compute first)"); return GIE_ERR_INVALID; }
+    return GIE_OK;
+}
+/* a kernel pair's dynamic LDS limit raised once (k1 may be null); `done` is the call site's own flag */
+static int gie_ground_lds_limit(bool *done, const char *who, const void *k0, const void *k1, int bytes)
+{
+    if (*done) return GIE_OK;
+    hipError_t e = hipFuncSetAttribute(k0, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess && k1) e = hipFuncSetAttribute(k1, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) { gie_set_err(std::string(who) + ": hipFuncSetAttribute: " + hipGetErrorString(e)); return GIE_ERR_DEVICE; }
+    *done = true;
     return GIE_OK;
 }
 /* the field's view, with the mapper's context free of a halo round's gate (no business of this section) */

@@ -53,7 +53,7 @@ __global__ __launch_bounds__(GIE_GNF1_THREADS) void k_gcostmat(const gie_ctx c, 
         int v[2] = { 0, 0 };
         bool in = true;
 #pragma unroll
-        for (int k = 0; k < 2; k++) {
+        for (int k = 0; k < 2; k++) {                           /* (gie_ground_cell_of, written out: profiles/r28_ground_helpers_times.txt, second state) */
             const float u = floorf(xy[2 * (size_t)tid + k] / c.voxel_width + 0.5f);    /* gie_pos2coord */
             if (!(u >= -1.0e9f && u <= 1.0e9f)) { in = false; continue; }             /* (NaN, inf, and what no int32 coordinate holds) */
             v[k] = (int)u - s.pvt[k];
@@ -84,7 +84,9 @@ __global__ __launch_bounds__(GIE_GNF1_THREADS) void k_gcostmat(const gie_ctx c, 
     if (tid == 0) { F[swd] = 1ull << sbit; B[swd] |= 1ull << sbit; }
     __syncthreads();
     if (!s_left[0]) return;                                     /* (workgroup-uniform) no valid point on another cell: the row is complete */
-    /* a thread's words are tid + 1024 k: word column and row of the first, and the step between two, without a division per word */
+    /* a thread's words are tid + 1024 k: word column and row of the first, and the step between two, without a division per word
+     * (gie_ground_words and gie_ground_dilate4, written out: with them the global form measured above the parent's range,
+     * profiles/r28_ground_helpers_times.txt, first state) */
     const int y0 = tid / W, tx0 = tid - y0 * W, dy = GIE_GNF1_THREADS / W, dtx = GIE_GNF1_THREADS - dy * W;
     const int max_levels = X * Y;                               /* no path is longer: the loop ends here whatever the planes hold */
 #pragma unroll 1
@@ -145,15 +147,10 @@ extern "C" int gie_ground_costmat_compute_dev(gie_mapper *m, const float *d_xy, 
     const gie_ground_dev g = gie_ground_view(m, &c);
     const int nwords = g.W * c.Y;
     const bool lds = nwords <= GIE_GNF1_LDS_WORDS;              /* by the size alone (sides <= 1024: one plane is 128 KiB at most, next always fits the LDS) */
-    {
-        static bool attr_done = false;
-        if (!attr_done) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gcostmat<true>), hipFuncAttributeMaxDynamicSharedMemorySize, GIE_GNF1_LDS_BYTES);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gcostmat<false>), hipFuncAttributeMaxDynamicSharedMemorySize, GIE_GNF1_LDS_BYTES);
-            if (e != hipSuccess) { gie_set_err(std::string("gie_ground_costmat_compute_dev: hipFuncSetAttribute: ") + hipGetErrorString(e)); return GIE_ERR_DEVICE; }
-            attr_done = true;
-        }
-    }
+    static bool attr_done = false;
+    const int ra = gie_ground_lds_limit(&attr_done, "gie_ground_costmat_compute_dev", reinterpret_cast<const void *>(&k_gcostmat<true>),
+                                        reinterpret_cast<const void *>(&k_gcostmat<false>), GIE_GNF1_LDS_BYTES);
+    if (ra) return ra;
     if (!m->gcm.blk0) {
         m->gcm.blk0 = gie_dalloc<uint64_t>(m, (size_t)nwords, false);
         if (!m->gcm.blk0) { gie_set_err("gie_ground_costmat_compute_dev: device allocation of the blocked plane failed"); return GIE_ERR_DEVICE; }

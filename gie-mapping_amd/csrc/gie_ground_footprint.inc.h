@@ -5,7 +5,7 @@
  * writes nothing of the map, of that field or of the ground navigation function; it has no plane of its own: the blocked plane is
  * ground line of sight's (glos_blk, k_glos_prep), rebuilt in front of the one query launch.
  *   k_ground_footprints<MARGIN>  a wave per trajectory, four trajectories per workgroup (k_ground_rollouts' shape).  The poses
- *                      are LOADED in chunks of 64 (lane l: pose base + l, its cell by gie_glos_cell and its heading) and TAKEN one
+ *                      are LOADED in chunks of 64 (lane l: pose base + l, its cell by gie_ground_cell_of and its heading) and TAKEN one
  *                      at a time, in order, their seven values broadcast from the owning lane; the first pose without a placement
  *                      or with a blocked footprint cell ends both loops (wave-uniform breaks: a colliding trajectory is cheap).
  *                      Within a pose lane l takes the footprint row dy = -R + l (+ 64 per chunk of rows; R <= 362, 12 chunks at
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void k_ground_footprints(const gie_ctx c, cons
             const float2 q = pts[k];
             const int2 d = hds[k];
             const float p[2] = { q.x, q.y };
-            has = gie_glos_cell(c, s, p, v);
+            has = gie_ground_cell_of(c.voxel_width, s.X, s.Y, s.pvt, p, v);
             has = has && (d.x != 0 || d.y != 0) && d.x >= -32767 && d.x <= 32767 && d.y >= -32767 && d.y <= 32767;
             h[0] = has ? d.x : 0; h[1] = has ? d.y : 0;
             if (has) {                                          /* the three roots here, 64 poses at a time, not in the loop over the poses */

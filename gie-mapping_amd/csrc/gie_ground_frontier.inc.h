@@ -1,9 +1,9 @@
 /*
  * gie_ground_frontier.inc.h — ground frontier clusters: the connected components of the ground field's FNT cells, filtered by size,
- * with a record (size, box, centroid, representative cell and its dist_sq) per kept component, and the gather of the ground
- * navigation function at points (include/gie.h "ground frontier clusters").
- * HIP backend only: included by gie_hip.hip after gie_ground_los.inc.h.  It reads the ground field's type and dist_sq planes (the
- * gather: the ground navigation function's field) and writes nothing of the map or of those fields.
+ * with a record (size, box, centroid, representative cell and its dist_sq) per kept component (include/gie.h "ground frontier
+ * clusters"; the gather of the ground navigation function at their goals, gie_ground_nf1_query, is in gie_ground_nf1.inc.h).
+ * HIP backend only: included by gie_hip.hip after gie_ground_los.inc.h.  It reads the ground field's type and dist_sq planes and
+ * writes nothing of the map or of that field.
  *
  * The cache (gie_mapper::gfr), per CELL, allocated at the first compute:
  *   par    int32 per cell, written at members only: the union-find forest.  A member that is not the first cell of its x-run
@@ -334,24 +334,6 @@ struct op_gfr_labels {
     }
 };
 
-/* gie_ground_nf1_query: one lane per point, gie_ground_query's mapping */
-__global__ __launch_bounds__(256) void k_gnf1_query(const gie_ctx c, const int32_t *f, const int pvt0, const int pvt1, const float *xy, const int n, int32_t *steps)
-{
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= n) return;
-    const int S[2] = { c.X, c.Y }, P[2] = { pvt0, pvt1 };
-    int v[2] = { 0, 0 };
-    bool in = true;
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-        const float u = floorf(xy[2 * (size_t)p + k] / c.voxel_width + 0.5f);      /* gie_pos2coord */
-        if (!(u >= -1.0e9f && u <= 1.0e9f)) { in = false; continue; }             /* (NaN, inf, and what no int32 coordinate holds) */
-        v[k] = (int)u - P[k];
-        in &= v[k] >= 0 && v[k] < S[k];
-    }
-    steps[p] = in ? f[v[1] * c.X + v[0]] : -1;
-}
-
 /* ---- host side */
 static gie_gfr_dev gie_gfr_view(const gie_mapper *m)
 {
@@ -370,9 +352,7 @@ static int gie_gfr_check(gie_mapper *m, const char *who, bool need_result)
 {
     static_assert(sizeof(gie_ground_frontier_cluster) == 64 && offsetof(gie_ground_frontier_cluster, sum) == 40 && offsetof(gie_ground_frontier_cluster, rep) == 24 &&
                   sizeof(gie_ground_frontier_param) == 32, "the sizes include/gie.h states");
-    if (!m) { gie_set_err(std::string(who) + ": null handle"); return GIE_ERR_INVALID; }
-    if (gie_tiled(m)) { gie_set_err(std::string(who) + ": not for a tiled mapper (its components would stop at the tile's faces)"); return GIE_ERR_INVALID; }
-    if (!m->ground.valid) { gie_set_err(std::string(who) + ": no ground field yet (gie_ground_compute first)"); return GIE_ERR_INVALID; }
+    const int rc = gie_ground_check(m, who, true, "components"); if (rc) return rc;
     if (need_result && !m->gfr.valid) { gie_set_err(std::string(who) + ": no frontier clusters of this ground field (gie_ground_frontier_compute first)"); return GIE_ERR_INVALID; }
     return GIE_OK;
 }
@@ -496,37 +476,6 @@ extern "C" int gie_read_ground_frontier_labels(gie_mapper *m, int32_t *labels)
     if (!d) return GIE_ERR_DEVICE;
     rc = gie_read_ground_frontier_labels_dev(m, d); if (rc) return rc;
     be_d2h(&m->be, labels, d, n * 4);
-    gie_scratch_trim(m);
-    return gie_sync(m);
-}
-
-static int gie_gnf1_check_query(gie_mapper *m, const char *who, const float *xy, int n, const int32_t *steps)
-{
-    const int rc = gie_gnf1_check(m, who, true); if (rc) return rc;
-    if (n < 0 || (n > 0 && (!xy || !steps))) { gie_set_err(std::string(who) + ": n < 0, or n > 0 with a null array"); return GIE_ERR_INVALID; }
-    return GIE_OK;
-}
-extern "C" int gie_ground_nf1_query_dev(gie_mapper *m, const float *d_xy, int n, int32_t *d_steps)
-{
-    const int rc = gie_gnf1_check_query(m, "gie_ground_nf1_query_dev", d_xy, n, d_steps); if (rc) return rc;
-    if (n == 0) return GIE_OK;
-    gie_ctx c;
-    (void)gie_ground_view(m, &c);
-    be_prof(&m->be, GIE_K_GROUND_NF1, 0);
-    GIE_LAUNCH(&m->be, k_gnf1_query, dim3((n + 255) / 256), dim3(256), 0, c, m->gnf1.f, m->ground.pvt[0], m->ground.pvt[1], d_xy, n, d_steps);
-    be_prof(&m->be, GIE_K_GROUND_NF1, 1);
-    return GIE_OK;
-}
-extern "C" int gie_ground_nf1_query(gie_mapper *m, const float *xy, int n, int32_t *steps)
-{
-    int rc = gie_gnf1_check_query(m, "gie_ground_nf1_query", xy, n, steps); if (rc) return rc;
-    if (n == 0) return GIE_OK;
-    float *dx = (float *)gie_scratch(m, 0, (size_t)n * 8, "gie_ground_nf1_query");
-    int32_t *dr = (int32_t *)gie_scratch(m, 1, (size_t)n * 4, "gie_ground_nf1_query");
-    if (!dx || !dr) return GIE_ERR_DEVICE;
-    be_h2d(&m->be, dx, xy, (size_t)n * 8);
-    rc = gie_ground_nf1_query_dev(m, dx, n, dr); if (rc) return rc;
-    be_d2h(&m->be, steps, dr, (size_t)n * 4);
     gie_scratch_trim(m);
     return gie_sync(m);
 }

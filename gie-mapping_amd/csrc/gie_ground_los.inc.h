@@ -38,12 +38,7 @@ __global__ __launch_bounds__(256) void k_glos_prep(const gie_ctx c, const gie_gr
     const bool none = gie_ground_nobs(g) == 0;                  /* no obstacle column: dist_sq is -1 everywhere */
     const int y = wd / g.W, x = (wd - y * g.W) * 64 + lane;
     bool tr = false;
-    if (x < c.X) {
-        const int id = y * c.X + x;
-        const int8_t ty = g.type[id];
-        const bool open = ty == GIE_VOX_FREE || ty == GIE_VOX_FNT || (ty == GIE_VOX_UNKNOWN && (flags & GIE_GROUND_LOS_UNKNOWN_TRAVERSABLE));
-        tr = open && (none || g.dist[id] >= clearance_sq);
-    }
+    if (x < c.X) tr = gie_ground_traversable(g, y * c.X + x, none, clearance_sq, flags & GIE_GROUND_LOS_UNKNOWN_TRAVERSABLE);
     const uint64_t bt = __ballot(tr);
     if (lane == 0) blk[wd] = ~bt;
 }
@@ -81,21 +76,6 @@ GIE_DEV bool gie_gwalk_step(gie_gwalk &w, int v[2])
     return true;
 }
 
-/* the cell of a point (metres): gie_ground_query's mapping; false outside the rectangle and for a point that is not finite */
-GIE_DEV bool gie_glos_cell(const gie_ctx &c, const gie_glos_dev &s, const float *xy, int v[2])
-{
-    const int S[2] = { s.X, s.Y };
-    bool in = true;
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-        const float u = floorf(xy[k] / c.voxel_width + 0.5f);   /* gie_pos2coord */
-        v[k] = 0;
-        if (!(u >= -1.0e9f && u <= 1.0e9f)) { in = false; continue; }             /* (NaN, inf, and what no int32 coordinate holds) */
-        v[k] = (int)u - s.pvt[k];
-        in &= v[k] >= 0 && v[k] < S[k];
-    }
-    return in;
-}
 /* the local cell of a path point (any int32: the difference in 64 bits); false outside the rectangle */
 GIE_DEV bool gie_glos_local(const gie_glos_dev &s, const int32_t *g, int v[2])
 {
@@ -113,7 +93,7 @@ __global__ __launch_bounds__(256) void k_ground_segments(const gie_ctx c, const 
     int a[2], b[2];
     gie_ground_hit h;
     h.reserved = 0;
-    const bool ina = gie_glos_cell(c, s, a_xy + 2 * (size_t)i, a), inb = gie_glos_cell(c, s, b_xy + 2 * (size_t)i, b);
+    const bool ina = gie_ground_cell_of(c.voxel_width, s.X, s.Y, s.pvt, a_xy + 2 * (size_t)i, a), inb = gie_ground_cell_of(c.voxel_width, s.X, s.Y, s.pvt, b_xy + 2 * (size_t)i, b);
     if (!ina || !inb) {
         h.first = -2; h.len = 0; h.hit[0] = h.hit[1] = 0; h.min_dist_sq = 0;
         out[i] = h;
@@ -219,10 +199,7 @@ static int gie_glos_check(gie_mapper *m, const char *who)
 {
     static_assert(sizeof(gie_ground_los_param) == 16 && sizeof(gie_ground_hit) == 24 && sizeof(gie_ground_shortcut_param) == 32 &&
                   sizeof(gie_ground_waypoint) == 24, "the sizes include/gie.h states");
-    if (!m) { gie_set_err(std::string(who) + ": null handle"); return GIE_ERR_INVALID; }
-    if (gie_tiled(m)) { gie_set_err(std::string(who) + ": not for a tiled mapper (its lines would stop at the tile's faces)"); return GIE_ERR_INVALID; }
-    if (!m->ground.valid) { gie_set_err(std::string(who) + ": no ground field yet (gie_ground_compute first)"); return GIE_ERR_INVALID; }
-    return GIE_OK;
+    return gie_ground_check(m, who, true, "lines");
 }
 static const char *gie_glos_bad_rule(int clearance_sq, int flags, const int32_t *reserved, int n_reserved)
 {

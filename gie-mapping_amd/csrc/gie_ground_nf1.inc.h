@@ -22,6 +22,7 @@
  *                  cooperative residency: the launch is no member of the chain of grid-barrier launches and has no timeout
  *                  path; the level count is bounded by X * Y whatever the planes hold.
  *   k_gnf1_path    one lane per start point (k_nf1_path's form in the plane).
+ *   k_gnf1_query   one lane per point: the gather of the field (the route costs to gie_ground_frontier.inc.h's goals).
  *   exports        one lane per cell (k_lin).
  * The compiler's figures and the times are in DESIGN.md 20.
  */
@@ -50,10 +51,8 @@ __global__ __launch_bounds__(256) void k_gnf1_prep(const gie_ctx c, const gie_gr
     bool tr = false, src = false;
     if (x < c.X) {
         const int id = y * c.X + x;
-        const int8_t ty = g.type[id];
-        const bool open = ty == GIE_VOX_FREE || ty == GIE_VOX_FNT || (ty == GIE_VOX_UNKNOWN && (flags & GIE_GROUND_NF1_UNKNOWN_TRAVERSABLE));
-        tr = open && (none || g.dist[id] >= clearance_sq);
-        src = tr && ty == GIE_VOX_FNT && (flags & GIE_GROUND_NF1_FROM_FRONTIERS);
+        tr = gie_ground_traversable(g, id, none, clearance_sq, flags & GIE_GROUND_NF1_UNKNOWN_TRAVERSABLE);
+        src = tr && g.type[id] == GIE_VOX_FNT && (flags & GIE_GROUND_NF1_FROM_FRONTIERS);
         s.f[id] = src ? 0 : -1;
     }
     const uint64_t bt = __ballot(tr), bs = __ballot(src);
@@ -68,9 +67,9 @@ __global__ __launch_bounds__(256) void k_gnf1_goals(const gie_ctx c, const gie_g
     const int S[2] = { c.X, c.Y }, P[2] = { pvt0, pvt1 };
     int v[2];
 #pragma unroll
-    for (int k = 0; k < 2; k++) {
-        const float u = floorf(xy[2 * (size_t)p + k] / c.voxel_width + 0.5f);      /* gie_pos2coord */
-        if (!(u >= -1.0e9f && u <= 1.0e9f)) return;             /* (NaN, inf, and what no int32 coordinate holds) */
+    for (int k = 0; k < 2; k++) {                               /* (gie_ground_cell_of, written out: through the function the kernel's register count changes) */
+        const float u = floorf(xy[2 * (size_t)p + k] / c.voxel_width + 0.5f);
+        if (!(u >= -1.0e9f && u <= 1.0e9f)) return;
         v[k] = (int)u - P[k];
         if (v[k] < 0 || v[k] >= S[k]) return;
     }
@@ -89,8 +88,7 @@ __global__ __launch_bounds__(GIE_GNF1_THREADS) void k_gnf1_bfs(const gie_ctx c, 
     __shared__ int s_cnt[GIE_GNF1_THREADS / 64], s_any[3];     /* s_any[L % 3]: some wave found a new bit in level L */
     uint64_t *NX = s_planes, *F = LDS ? s_planes + nwords : s.fr, *B = LDS ? s_planes + 2 * (size_t)nwords : s.blk;
     const int tid = threadIdx.x, W = s.W, X = c.X, Y = c.Y;
-    /* a thread's words are tid + 1024 k: word column and row of the first, and the step between two, without a division per word */
-    const int y0 = tid / W, tx0 = tid - y0 * W, dy = GIE_GNF1_THREADS / W, dtx = GIE_GNF1_THREADS - dy * W;
+    const gie_ground_words w0 = gie_ground_words_first(tid, GIE_GNF1_THREADS, W);
     int n = 0;
     for (int wd = tid; wd < nwords; wd += GIE_GNF1_THREADS) {   /* the sources counted, the planes into LDS */
         const uint64_t f = s.fr[wd];
@@ -113,24 +111,18 @@ __global__ __launch_bounds__(GIE_GNF1_THREADS) void k_gnf1_bfs(const gie_ctx c, 
     for (int level = 0; level < max_levels; level++) {
         if (tid == 0) s_any[(level + 1) % 3] = 0;               /* (last read after the barrier of level - 2, next set in level + 1) */
         int any = 0;
+        gie_ground_words w = w0;
 #pragma unroll 1
-        for (int wd = tid, y = y0, tx = tx0; wd < nwords; wd += GIE_GNF1_THREADS) {
-            const uint64_t f = F[wd];
-            uint64_t d = f | (f << 1) | (f >> 1);
-            if (tx > 0) d |= F[wd - 1] >> 63;
-            if (tx < W - 1) d |= F[wd + 1] << 63;
-            if (y > 0) d |= F[wd - W];
-            if (y < Y - 1) d |= F[wd + W];
-            const uint64_t bl = B[wd], nx = d & ~bl;            /* (blk holds the padding bits beyond X; only its owner touches a word of it) */
+        for (int wd = tid; wd < nwords; wd += GIE_GNF1_THREADS) {
+            const uint64_t d = gie_ground_dilate4(F, wd, w.tx, w.y, W, Y), bl = B[wd], nx = d & ~bl;        /* (blk holds the padding bits beyond X; only its owner touches a word of it) */
             NX[wd] = nx;
             if (nx) {
                 any = 1;
                 B[wd] = bl | nx;
-                int32_t *fr = s.f + (size_t)y * X + tx * 64;
+                int32_t *fr = s.f + (size_t)w.y * X + w.tx * 64;
                 for (uint64_t b = nx; b; b &= b - 1) fr[__builtin_ctzll(b)] = level + 1;
             }
-            y += dy; tx += dtx;
-            if (tx >= W) { tx -= W; y++; }
+            gie_ground_words_next(w, W);
         }
         if (__any(any) && (tid & 63) == 0) s_any[level % 3] = 1;
         __syncthreads();                                        /* every read of F is done, next is complete */
@@ -153,8 +145,8 @@ __global__ __launch_bounds__(256) void k_gnf1_path(const gie_ctx c, const int32_
     int v[2] = { 0, 0 };
     bool in = true;
 #pragma unroll
-    for (int k = 0; k < 2; k++) {
-        const float u = floorf(xy[2 * (size_t)p + k] / c.voxel_width + 0.5f);      /* gie_pos2coord */
+    for (int k = 0; k < 2; k++) {                               /* (gie_ground_cell_of, written out: through the function the kernel's register count changes) */
+        const float u = floorf(xy[2 * (size_t)p + k] / c.voxel_width + 0.5f);
         if (!(u >= -1.0e9f && u <= 1.0e9f)) { in = false; continue; }
         v[k] = (int)u - P[k];
         in &= v[k] >= 0 && v[k] < S[k];
@@ -178,6 +170,24 @@ __global__ __launch_bounds__(256) void k_gnf1_path(const gie_ctx c, const int32_
     }
 }
 
+/* gie_ground_nf1_query: one lane per point */
+__global__ __launch_bounds__(256) void k_gnf1_query(const gie_ctx c, const int32_t *f, const int pvt0, const int pvt1, const float *xy, const int n, int32_t *steps)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const int S[2] = { c.X, c.Y }, P[2] = { pvt0, pvt1 };
+    int v[2] = { 0, 0 };
+    bool in = true;
+#pragma unroll
+    for (int k = 0; k < 2; k++) {                               /* (gie_ground_cell_of, written out: through the function the kernel's register count changes) */
+        const float u = floorf(xy[2 * (size_t)p + k] / c.voxel_width + 0.5f);
+        if (!(u >= -1.0e9f && u <= 1.0e9f)) { in = false; continue; }
+        v[k] = (int)u - P[k];
+        in &= v[k] >= 0 && v[k] < S[k];
+    }
+    steps[p] = in ? f[v[1] * c.X + v[0]] : -1;
+}
+
 /* the one-layer TYPE_NF1 CostMap payload; `o` from the ground field's type plane as it stands (no copy is kept) */
 struct op_gnf1_costmap {
     const int32_t *f; const int8_t *type; gie_seendist *out;
@@ -194,9 +204,7 @@ struct op_gnf1_copy { const int32_t *f; int32_t *out; GIE_DEVM void operator()(c
 static int gie_gnf1_check(gie_mapper *m, const char *who, bool need_field)
 {
     static_assert(sizeof(gie_ground_nf1_param) == 32, "the size include/gie.h states");
-    if (!m) { gie_set_err(std::string(who) + ": null handle"); return GIE_ERR_INVALID; }
-    if (gie_tiled(m)) { gie_set_err(std::string(who) + ": not for a tiled mapper (its field would stop at the tile's faces)"); return GIE_ERR_INVALID; }
-    if (!m->ground.valid) { gie_set_err(std::string(who) + ": no ground field yet (gie_ground_compute first)"); return GIE_ERR_INVALID; }
+    const int rc = gie_ground_check(m, who, true); if (rc) return rc;
     if (need_field && !m->gnf1.valid) { gie_set_err(std::string(who) + ": no ground navigation function of this ground field (gie_ground_nf1_compute first)"); return GIE_ERR_INVALID; }
     return GIE_OK;
 }
@@ -233,15 +241,10 @@ extern "C" int gie_ground_nf1_compute_dev(gie_mapper *m, const float *d_goal_xy,
     const gie_ground_dev g = gie_ground_view(m, &c);
     const int W = g.W, nwords = W * c.Y;
     const bool lds = nwords <= GIE_GNF1_LDS_WORDS;              /* by the size alone */
-    {
-        static bool attr_done = false;
-        if (!attr_done) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gnf1_bfs<true>), hipFuncAttributeMaxDynamicSharedMemorySize, GIE_GNF1_LDS_BYTES);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gnf1_bfs<false>), hipFuncAttributeMaxDynamicSharedMemorySize, GIE_GNF1_LDS_BYTES);
-            if (e != hipSuccess) { gie_set_err(std::string("gie_ground_nf1_compute_dev: hipFuncSetAttribute: ") + hipGetErrorString(e)); return GIE_ERR_DEVICE; }
-            attr_done = true;
-        }
-    }
+    static bool attr_done = false;
+    const int ra = gie_ground_lds_limit(&attr_done, "gie_ground_nf1_compute_dev", reinterpret_cast<const void *>(&k_gnf1_bfs<true>),
+                                        reinterpret_cast<const void *>(&k_gnf1_bfs<false>), GIE_GNF1_LDS_BYTES);
+    if (ra) return ra;
     if (!m->gnf1.f) {
         int32_t *f = gie_dalloc<int32_t>(m, (size_t)c.X * c.Y, false);
         uint64_t *bits = f ? gie_dalloc<uint64_t>(m, 2 * (size_t)nwords, false) : nullptr;
@@ -315,6 +318,36 @@ extern "C" int gie_ground_nf1_path(gie_mapper *m, const float *start_xy, int n, 
     rc = gie_ground_nf1_path_dev(m, dx, n, max_len, (int32_t *)(dr + (size_t)n * 4), (int32_t *)dr); if (rc) return rc;
     be_d2h(&m->be, len, dr, (size_t)n * 4);
     be_d2h(&m->be, path_xy, dr + (size_t)n * 4, pbytes);
+    gie_scratch_trim(m);
+    return gie_sync(m);
+}
+static int gie_gnf1_check_query(gie_mapper *m, const char *who, const float *xy, int n, const int32_t *steps)
+{
+    const int rc = gie_gnf1_check(m, who, true); if (rc) return rc;
+    if (n < 0 || (n > 0 && (!xy || !steps))) { gie_set_err(std::string(who) + ": n < 0, or n > 0 with a null array"); return GIE_ERR_INVALID; }
+    return GIE_OK;
+}
+extern "C" int gie_ground_nf1_query_dev(gie_mapper *m, const float *d_xy, int n, int32_t *d_steps)
+{
+    const int rc = gie_gnf1_check_query(m, "gie_ground_nf1_query_dev", d_xy, n, d_steps); if (rc) return rc;
+    if (n == 0) return GIE_OK;
+    gie_ctx c;
+    (void)gie_ground_view(m, &c);
+    be_prof(&m->be, GIE_K_GROUND_NF1, 0);
+    GIE_LAUNCH(&m->be, k_gnf1_query, dim3((n + 255) / 256), dim3(256), 0, c, m->gnf1.f, m->ground.pvt[0], m->ground.pvt[1], d_xy, n, d_steps);
+    be_prof(&m->be, GIE_K_GROUND_NF1, 1);
+    return GIE_OK;
+}
+extern "C" int gie_ground_nf1_query(gie_mapper *m, const float *xy, int n, int32_t *steps)
+{
+    int rc = gie_gnf1_check_query(m, "gie_ground_nf1_query", xy, n, steps); if (rc) return rc;
+    if (n == 0) return GIE_OK;
+    float *dx = (float *)gie_scratch(m, 0, (size_t)n * 8, "gie_ground_nf1_query");
+    int32_t *dr = (int32_t *)gie_scratch(m, 1, (size_t)n * 4, "gie_ground_nf1_query");
+    if (!dx || !dr) return GIE_ERR_DEVICE;
+    be_h2d(&m->be, dx, xy, (size_t)n * 8);
+    rc = gie_ground_nf1_query_dev(m, dx, n, dr); if (rc) return rc;
+    be_d2h(&m->be, steps, dr, (size_t)n * 4);
     gie_scratch_trim(m);
     return gie_sync(m);
 }

@@ -134,15 +134,9 @@ __global__ __launch_bounds__(256) void k_gpose_goals(const gie_ctx c, const gie_
 {
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= n) return;
-    const int S[2] = { c.X, c.Y }, P[2] = { pvt0, pvt1 };
+    const int P[2] = { pvt0, pvt1 };
     int v[2];
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-        const float u = floorf(xy[2 * (size_t)p + k] / c.voxel_width + 0.5f);      /* gie_pos2coord */
-        if (!(u >= -1.0e9f && u <= 1.0e9f)) return;             /* (NaN, inf, and what no int32 coordinate holds) */
-        v[k] = (int)u - P[k];
-        if (v[k] < 0 || v[k] >= S[k]) return;
-    }
+    if (!gie_ground_cell_of(c.voxel_width, c.X, c.Y, P, xy + 2 * (size_t)p, v)) return;
     const int want = gk ? gk[p] : -1;
     if (want < -1 || want >= GIE_GROUND_POSE_HEADINGS) return;
     const int wd = v[1] * s.W + (v[0] >> 6);
@@ -206,6 +200,7 @@ __global__ __launch_bounds__(GIE_GNF1_THREADS) void k_gpose_bfs(const gie_ctx c,
         s.w[GIE_GPOSE_W_SRC] = t; s.w[GIE_GPOSE_W_FREE] = u;
         if (counts) { counts[0] = t; counts[1] = u; }
     }
+    /* (gie_ground_words, written out: with it both forms measured above the parent's range, profiles/r28_ground_helpers_times.txt) */
     const int y0 = tid / W, tx0 = tid - y0 * W, dy = GIE_GNF1_THREADS / W, dtx = GIE_GNF1_THREADS - dy * W;
     const long long max_levels = (long long)GIE_GROUND_POSE_HEADINGS * X * Y;      /* no route is longer: the loop ends here whatever the planes hold */
 #pragma unroll 1
@@ -250,16 +245,8 @@ __global__ __launch_bounds__(GIE_GNF1_THREADS) void k_gpose_bfs(const gie_ctx c,
 /* the cell of point p and the field's value there; k == -1: the lowest heading with the least value >= 0 */
 GIE_DEV int gie_gpose_lookup(const gie_ctx &c, const int32_t *f, const int pvt0, const int pvt1, const float *xy, int k, int v[2], int &kk)
 {
-    const int S[2] = { c.X, c.Y }, P[2] = { pvt0, pvt1 };
-    bool in = true;
-#pragma unroll
-    for (int a = 0; a < 2; a++) {
-        const float u = floorf(xy[a] / c.voxel_width + 0.5f);   /* gie_pos2coord */
-        v[a] = 0;
-        if (!(u >= -1.0e9f && u <= 1.0e9f)) { in = false; continue; }
-        v[a] = (int)u - P[a];
-        in &= v[a] >= 0 && v[a] < S[a];
-    }
+    const int P[2] = { pvt0, pvt1 };
+    const bool in = gie_ground_cell_of(c.voxel_width, c.X, c.Y, P, xy, v);
     kk = 0;
     if (!in || k < -1 || k >= GIE_GROUND_POSE_HEADINGS) return -1;
     const size_t plane = (size_t)c.X * c.Y, id = (size_t)v[1] * c.X + v[0];
@@ -373,14 +360,9 @@ extern "C" int gie_ground_pose_nf1_compute_dev(gie_mapper *m, const float *d_goa
     const gie_ground_dev g = gie_ground_view(m, &c);
     const int W = g.W, nwords = W * c.Y;
     const bool lds = nwords <= GIE_GPOSE_LDS_WORDS;             /* by the size alone */
-    {
-        static bool attr_done = false;
-        if (!attr_done) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gpose_bfs<true>), hipFuncAttributeMaxDynamicSharedMemorySize, GIE_GNF1_LDS_BYTES);
-            if (e != hipSuccess) { gie_set_err(std::string(who) + ": hipFuncSetAttribute: " + hipGetErrorString(e)); return GIE_ERR_DEVICE; }
-            attr_done = true;
-        }
-    }
+    static bool attr_done = false;
+    const int ra = gie_ground_lds_limit(&attr_done, who, reinterpret_cast<const void *>(&k_gpose_bfs<true>), nullptr, GIE_GNF1_LDS_BYTES);
+    if (ra) return ra;
     if (!m->gpose.f) {
         int32_t *f = gie_dalloc<int32_t>(m, (size_t)GIE_GROUND_POSE_HEADINGS * c.X * c.Y, false);
         uint64_t *bits = f ? gie_dalloc<uint64_t>(m, 4 * (size_t)GIE_GROUND_POSE_HEADINGS * nwords, false) : nullptr;

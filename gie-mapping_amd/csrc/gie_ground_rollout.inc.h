@@ -5,7 +5,7 @@
  * ground navigation function's field and writes nothing of the map, of that field or of that function; it has no plane of its own:
  * the blocked plane is ground line of sight's (glos_blk, k_glos_prep), rebuilt in front of the one query launch.
  *   k_ground_rollouts<NF1>  a wave per trajectory, four trajectories per workgroup (k_ground_shortcut's shape).  The poses go in chunks
- *                      of 64, in order; in chunk `base` lane l owns pose k = base + l: one float2 load, gie_glos_cell, the cell of
+ *                      of 64, in order; in chunk `base` lane l owns pose k = base + l: one float2 load, gie_ground_cell_of, the cell of
  *                      pose k - 1 from the lane below (a wave shuffle; lane 0 takes the previous chunk's last cell from two scalar
  *                      registers), then the walk of L2(c_{k-1}, c_k) from the cell AFTER c_{k-1} (pose 0: c_0 alone): a bit test and
  *                      a dist_sq load per cell, leaving at its first blocked cell.  f = ctz(ballot(no pose || no cell || blocked)) is
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(256) void k_ground_rollouts(const gie_ctx c, const 
         if (k < T) {
             const float2 q = pts[k];
             const float p[2] = { q.x, q.y };
-            has = gie_glos_cell(c, s, p, v);
+            has = gie_ground_cell_of(c.voxel_width, s.X, s.Y, s.pvt, p, v);
         }
         int a[2] = { __shfl_up(v[0], 1), __shfl_up(v[1], 1) };
         const uint64_t hm = __ballot(has);

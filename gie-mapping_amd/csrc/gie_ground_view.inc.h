@@ -43,7 +43,7 @@ struct gie_gview_arg {
 /* the cell of view i, and its normals into nr; false for a view that scores -1 */
 GIE_DEV bool gie_gview_load(const gie_ctx &c, const gie_glos_dev &s, const gie_gview_arg &a, const float *xy, const int32_t *normals, const size_t i, int p[2], int nr[4])
 {
-    bool ok = gie_glos_cell(c, s, xy + 2 * i, p);
+    bool ok = gie_ground_cell_of(c.voxel_width, s.X, s.Y, s.pvt, xy + 2 * i, p);
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         nr[k] = 0;
@@ -182,15 +182,10 @@ static int gie_gview_run(gie_mapper *m, const char *who, const float *d_xy, cons
     gie_ctx c;
     const gie_ground_dev g = gie_ground_view(m, &c);
     const int nwords = g.W * c.Y;
-    {
-        static bool attr_done = false;
-        if (!attr_done) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ground_gain<true>), hipFuncAttributeMaxDynamicSharedMemorySize, GIE_GVIEW_LDS_BYTES);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ground_gain<false>), hipFuncAttributeMaxDynamicSharedMemorySize, GIE_GVIEW_LDS_BYTES);
-            if (e != hipSuccess) { gie_set_err(std::string(who) + ": hipFuncSetAttribute: " + hipGetErrorString(e)); return GIE_ERR_DEVICE; }
-            attr_done = true;
-        }
-    }
+    static bool attr_done = false;
+    const int ra = gie_ground_lds_limit(&attr_done, who, reinterpret_cast<const void *>(&k_ground_gain<true>), reinterpret_cast<const void *>(&k_ground_gain<false>),
+                                        GIE_GVIEW_LDS_BYTES);
+    if (ra) return ra;
     if (!m->gview_opq) {
         m->gview_opq = gie_dalloc<uint64_t>(m, (size_t)nwords, false);
         if (!m->gview_opq) { gie_set_err(std::string(who) + ": device allocation of the opaque plane failed"); return GIE_ERR_DEVICE; }

@@ -11,11 +11,10 @@ import gie
 import ground_footprint_ref as P
 import ground_ref as R
 from gie import _capi, scenes
-from stage_common import W, box_labels, build_host_probe, lidar_frames, mapper as _mapper, stage_calls_change_nothing, update as _update
+from ground_common import INVALID, P5A, settle as _settle, ground as _ground, xy as _xy, open_cells as _open, same as _same, arc as _arc, scene
+from stage_common import W, box_labels, build_host_probe, lidar_frames, mapper as _mapper, stage_calls_change_nothing
 
 pytestmark = pytest.mark.gpu
-INVALID = 1                                                     # GIE_ERR_INVALID
-P5A = bytes([0x5a])
 NAMES = ["ogm_classify", "ray_register", "ray_free", "ray_finalize", "block_alloc", "fuse", "edt_pass_y", "edt_pass_x", "edt_pass_z", "mark",
          "frontiers", "wave_a", "wave_b", "waves", "commit", "edt_prep", "mark_commit", "ground_nf1", "ground", "ground_query", "cloud", "los",
          "los_query", "sdf", "sdf_query"]                       # gie_profile_read's entries of a mapper without frontier clusters
@@ -24,49 +23,6 @@ SMALL, LONG = (9, 1, 4), (1600, 4, 9)                           # (front_sq, bac
 FLAG_PAIRS = ((False, False), (True, True), (False, True), (True, False))      # (unknown traversable, margin)
 RULES = [(e, c) for c, e in itertools.product((0, 1, 9), (SMALL, LONG))]       # a rectangle and a clearance_sq
 COMBOS = [(e, c, u, mg) for (e, c), (u, mg) in itertools.product(RULES, FLAG_PAIRS)]      # the 24 combinations
-
-
-def _settle(m, lab, pos=(0.0, 0.0, 0.0)):
-    pos = tuple(np.float32(v) for v in pos)
-    for _ in range(2):
-        _update(m, pos, (1.0, 0.0, 0.0, 0.0), lab)
-    return m.pivot()
-
-
-def _ground(m, size, blocks=False, min_known=1):
-    """the ground field of the whole height: read_ground()'s planes"""
-    z = m.pivot()[2]
-    m.ground_compute(z, z + size[2] - 1, min_known, blocks)
-    return m.read_ground()
-
-
-def _xy(pvt, cells, shift=0.0):
-    """world points (float32 metres) of local cells (any shape (.., 2), fractions allowed): (cell + pvt + shift) * w, the product in float32"""
-    c = np.asarray(cells, np.float64) + np.array(pvt[:2])
-    return ((c.astype(np.float32) + np.float32(shift)) * np.float32(W)).astype(np.float32)
-
-
-def _scene(size, seed, n_boxes=7, unknown_slab=3, pos_k=2):
-    rng = np.random.default_rng(seed)
-    pos, q = scenes.pose(pos_k, W, delta_vox=3, yaw_deg=0.0)
-    pvt = scenes.local_pivot(pos, W, size)
-    boxes = []
-    for _ in range(n_boxes):
-        s = rng.integers(2, 7, size=3)
-        c = rng.integers(np.asarray(pvt) - 2, np.asarray(pvt) + np.asarray(size))
-        boxes.append((c, c + s))
-    return pos, box_labels(pvt, size, 0, boxes, unknown_slab)
-
-
-def _open(g):
-    t = np.asarray(g["type"])
-    return (t == R.FREE) | (t == R.FNT)
-
-
-def _same(got, want, what):
-    for key in want.dtype.names:
-        assert np.array_equal(got[key], want[key]), (what, key, got[key].tolist(), want[key].tolist())
-    assert got.tobytes() == want.tobytes(), what
 
 
 def _flags(unknown, margin):
@@ -90,15 +46,6 @@ def _both_forms(m, st, xy, hd, e, c, u, mg, want, what):
     o = dout.cpu().numpy()
     assert o[:n * 32].tobytes() == want.tobytes() and o[n * 32:].tobytes() == P5A * 32, what
     return got
-
-
-def _arc(start, heading, step, turn, T):
-    """T poses of a unicycle arc: (cells with fractions [T][2], headings int32 [T][2] = lround(32767 (cos, sin)) of the true heading)"""
-    k = np.arange(T)
-    th = heading + turn * k
-    d = np.stack([np.cos(th), np.sin(th)], 1)
-    xy = np.asarray(start, np.float64) + np.concatenate([np.zeros((1, 2)), np.cumsum(d[:-1] * step, 0)])
-    return xy, np.rint(32767.0 * d).astype(np.int32)
 
 
 def _fan(g, size, T, rng, n=13):
@@ -186,7 +133,7 @@ def _sweep_conditions(cases, pvt, shape):
 @pytest.mark.parametrize("size", [(70, 40, 4), (130, 48, 4)])
 def test_footprints_equal_the_reference(size):
     import torch
-    pos, lab = _scene(size, 300 + size[0])
+    pos, lab = scene(size, 300 + size[0], n_boxes=7, unknown_slab=3, smax=7)
     m = _mapper(size)
     try:
         pvt = _settle(m, lab, pos)
@@ -211,7 +158,7 @@ HEADS = [(1, 0), (0, 1), (-1, 0), (0, -1), (1, 1), (-1, 1), (1, -1), (-1, -1), (
 def test_pinned_poses_on_the_borders_and_word_boundaries(size):
     import torch
     X, Y = size[0], size[1]
-    pos, lab = _scene(size, 300 + size[0])
+    pos, lab = scene(size, 300 + size[0], n_boxes=7, unknown_slab=3, smax=7)
     m = _mapper(size)
     try:
         pvt = _settle(m, lab, pos)
@@ -240,7 +187,7 @@ def test_pinned_poses_on_the_borders_and_word_boundaries(size):
 # ---------------------------------------------------------------------------------------------------------- 3. against the rollouts
 def test_zero_extents_agree_with_the_rollouts_on_the_same_poses():
     size = (70, 40, 4)
-    pos, lab = _scene(size, 370)
+    pos, lab = scene(size, 370, n_boxes=7, unknown_slab=3, smax=7)
     m = _mapper(size)
     try:
         pvt = _settle(m, lab, pos)
@@ -264,7 +211,7 @@ def test_zero_extents_agree_with_the_rollouts_on_the_same_poses():
 def test_mask_equals_the_reference_and_keeps_the_record():
     import torch
     size = (70, 40, 4)
-    pos, lab = _scene(size, 370)
+    pos, lab = scene(size, 370, n_boxes=7, unknown_slab=3, smax=7)
     m = _mapper(size)
     try:
         pvt = _settle(m, lab, pos)

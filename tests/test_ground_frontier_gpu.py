@@ -22,39 +22,12 @@ import ground_nf1_ref as N
 import ground_ref as R
 import gie
 from gie import _capi, scenes
+from ground_common import INVALID, P5A, settle as _settle, plane as _plane, ground as _ground, xy as _xy, framed as _framed, serpentine as _serpentine, chain_scene as _chain_scene
 from stage_common import W, build_host_probe, lidar_frames, mapper as _mapper, stage_calls_change_nothing, update as _update
 
 pytestmark = pytest.mark.gpu
-INVALID = 1                                                     # GIE_ERR_INVALID
 CLEARANCES = (0, 1, 2, 4, 5, 9)
 DT = gie.GROUND_FRONTIER_CLUSTER_DTYPE
-P5A = bytes([0x5a])
-
-
-def _settle(m, lab, pos=(0.0, 0.0, 0.0)):
-    pos = tuple(np.float32(v) for v in pos)
-    for _ in range(2):
-        _update(m, pos, (1.0, 0.0, 0.0, 0.0), lab)
-    return m.pivot()
-
-
-def _plane(size, lab2d):
-    """a [Y][X] label plane on every layer"""
-    return np.repeat(np.asarray(lab2d, np.int8)[None], size[2], axis=0)
-
-
-def _ground(m, size, band=None, blocks=False, min_known=1):
-    """the ground field of the local layers band = (lo, hi) (default: the whole height): read_ground()'s planes"""
-    z = m.pivot()[2]
-    lo, hi = band if band is not None else (0, size[2] - 1)
-    m.ground_compute(z + lo, z + hi, min_known, blocks)
-    return m.read_ground()
-
-
-def _xy(pvt, cells, shift=0.0):
-    """world points (float32 metres) of local cells (x, y): (cell + pvt + shift) * w, the product in float32"""
-    c = np.asarray(cells, np.float64).reshape(-1, 2) + np.array(pvt[:2])
-    return ((c.astype(np.float32) + np.float32(shift)) * np.float32(W)).astype(np.float32)
 
 
 def _same(got, want):
@@ -76,13 +49,6 @@ def _check(m, g, pvt, csq=0, conn=8, min_size=1, cap=256, members=1, kept=0, dro
     assert np.array_equal(labels, want["labels"]), (csq, conn, min_size, int((labels != want["labels"]).sum()))
     _same(m.read_ground_frontier_clusters(), want)
     return want
-
-
-def _framed(X, Y, fill=1):
-    lab = np.full((Y, X), fill, np.int8)
-    lab[0] = lab[-1] = 2
-    lab[:, 0] = lab[:, -1] = 2
-    return lab
 
 
 # ---------------------------------------------------------------------------------------------------------- 1. word boundaries
@@ -155,22 +121,6 @@ def test_connectivity_across_the_word_boundary():
         _check(m, g, pvt, 0, 4, 2, 32, kept=7, dropped=3)
     finally:
         m.close()
-
-
-def _serpentine(X, Y, pitch):
-    """(label plane [Y][X], the cells (x, y) in order) of ONE one-cell-wide corridor through walls: rows `pitch` apart from y = 1,
-    each from x = 1 to X - 2, joined at alternating ends"""
-    lab = np.full((Y, X), 2, np.int8)
-    cells = []
-    rows = list(range(1, Y - 1, pitch))
-    for i, y in enumerate(rows):
-        xs = list(range(1, X - 1)) if i % 2 == 0 else list(range(X - 2, 0, -1))
-        cells += [(x, y) for x in xs]
-        if i + 1 < len(rows):
-            cells += [(xs[-1], yy) for yy in range(y + 1, rows[i + 1])]
-    c = np.array(cells)
-    lab[c[:, 1], c[:, 0]] = 1
-    return lab, c
 
 
 def test_one_serpentine_arc_through_every_word_column():
@@ -327,19 +277,6 @@ def test_a_flat_volume_agrees_with_the_3d_frontier_clusters():
 
 
 # ---------------------------------------------------------------------------------------------------------- 7. the device chain
-def _chain_scene(X=64, Y=40):
-    """free space in a frame; a closed room with a never-seen cell inside (a ring the robot cannot reach), never-seen lines and cells
-    outside it (arcs and rings it can)"""
-    lab = _framed(X, Y)
-    lab[5:14, 40:52] = 2
-    lab[6:13, 41:51] = 1
-    lab[9, 45] = 0
-    lab[20:30, 12] = 0
-    lab[30, 30:44] = 0
-    lab[8, 8] = lab[34, 55] = lab[16, 30] = 0
-    return lab
-
-
 def test_the_device_chain_with_one_sync():
     import torch
     size = (64, 40, 3)

@@ -8,13 +8,20 @@ import numpy as np
 import pytest
 
 import gie
+import ground_costmat_ref as CM
+import ground_footprint_ref as FP
+import ground_frontier_ref as FR
+import ground_los_ref as L
+import ground_nf1_ref as N
+import ground_pose_nf1_ref as PQ
 import ground_ref as R
+import ground_rollout_ref as RO
+import ground_view_ref as V
 from gie import _capi, scenes
+from ground_common import INVALID, ground as _ground, settle
 from stage_common import W, box_labels as _box_labels, build_host_probe, lidar_frames, mapper as _mapper, stage_calls_change_nothing
-from stage_common import update as _update
 
 pytestmark = pytest.mark.gpu
-INVALID = 1                                                     # GIE_ERR_INVALID
 HDR_FIELDS = ("x_size", "y_size", "z_size", "x_origin", "y_origin", "z_origin", "width", "type")
 
 
@@ -34,10 +41,8 @@ def _boxes_in(rng, n, pvt, size, smin, smax):
 
 def _settle(m, lab, pos=(0.0, 0.0, 0.0)):
     """two updates of one label plane at one pose: (types as read_local returns them, pivot)"""
-    pos = tuple(np.float32(v) for v in pos)
-    for _ in range(2):
-        _update(m, pos, (1.0, 0.0, 0.0, 0.0), lab)
-    return m.read_local(edt=False, dist_sq=False, coc=False)["type"], m.pivot()
+    pvt = settle(m, lab, pos)
+    return m.read_local(edt=False, dist_sq=False, coc=False)["type"], pvt
 
 
 def _labels(size, fill=1):
@@ -309,6 +314,152 @@ def test_query_and_dev_forms():
         assert d_pay.cpu().numpy().tobytes() == host_pay.tobytes()
         assert bytes(hdr) == bytes(host_hdr)
         assert d_q.cpu().numpy().tobytes() == host_q.tobytes()
+    finally:
+        m.close()
+
+
+# ---------------------------------------------------------------------------------------------------------- 8b. one mapping of a point to its cell
+def _cell_table(pvt, size):
+    """(points float32 [n][2], {category: indices}) around the field of `size` at `pvt`: "centres" the centres of cells at x = 0, 63, 64
+    and of one cell outside each side; "ties" the pos2coord ties half a cell outside the first and the last cell of both axes, each
+    with its two float32 neighbours (whichever way a tie rounds, one side of it is inside and one outside); "odd" NaN, +-inf, +-1e30
+    and +-3e9 in one coordinate beside a good other one"""
+    X, Y = size[0], size[1]
+    w, px, py = np.float32(W), pvt[0], pvt[1]
+    xm, ym = np.float32(px + 32) * w, np.float32(py + 4) * w   # a good x, a good y
+    centres = [(np.float32(px + x) * w, ym) for x in (0, 63, 64, -1, X)] + [(xm, np.float32(py + y) * w) for y in (-1, Y)]
+    ties = []
+    for edge in (px - 0.5, px + X - 0.5):
+        t = np.float32(edge) * w
+        ties += [(v, ym) for v in (np.nextafter(t, np.float32(-np.inf)), t, np.nextafter(t, np.float32(np.inf)))]
+    for edge in (py - 0.5, py + Y - 0.5):
+        t = np.float32(edge) * w
+        ties += [(xm, v) for v in (np.nextafter(t, np.float32(-np.inf)), t, np.nextafter(t, np.float32(np.inf)))]
+    bad = [np.nan, np.inf, -np.inf, 1e30, -1e30, 3e9, -3e9]
+    odd = [(v, ym) for v in bad] + [(xm, v) for v in bad]
+    cat, at = {}, 0
+    for name, pts in (("centres", centres), ("ties", ties), ("odd", odd)):
+        cat[name] = np.arange(at, at + len(pts))
+        at += len(pts)
+    return np.array(centres + ties + odd, np.float32), cat
+
+
+def test_every_point_taking_entry_maps_one_table_of_points_alike():
+    """include/gie.h: every ground entry maps a point to its cell the way gie_ground_query does.  One table of points — cell centres
+    either side of the word boundary, the rounding ties on the field's four edges, one cell outside each side, NaN, inf and values no
+    int32 holds — goes through every entry that takes points, host and _dev form; each answer is its own reference's, exactly, and
+    where an answer shows whether the point had a cell that is ground_nf1_ref.cells_of's verdict."""
+    import torch
+    size = (65, 9, 2)                                           # two bit words per row, 63 padding bits
+    X, Y = size[0], size[1]
+    pos = (3.0, -2.0, 0.5)
+    pvt = scenes.local_pivot(pos, W, size)
+    assert pvt[0] != 0 and pvt[1] != 0
+    T, cat = _cell_table(pvt, size)
+    cells = N.cells_of(T, pvt, W, (Y, X))
+    has = np.array([c is not None for c in cells])
+    # the table itself, before the device is touched: both verdicts in the categories that admit both; an odd point fails by its odd
+    # coordinate alone
+    for name in ("centres", "ties"):
+        assert has[cat[name]].any() and not has[cat[name]].all(), name
+    assert [cells[i] for i in cat["centres"][:3]] == [(0, 4), (63, 4), (64, 4)]
+    for k in range(0, len(cat["ties"]), 3):                    # around each tie one neighbour is inside and one outside
+        assert has[cat["ties"][k]] != has[cat["ties"][k + 2]], k
+    assert not has[cat["odd"]].any()
+    for i, j in enumerate(cat["odd"]):
+        k = int(i >= len(cat["odd"]) // 2)                      # the first half is odd in x, the second in y
+        fixed = T[j].copy()
+        fixed[k] = T[1, k]                                      # (T[1]: the centre of cell (63, 4))
+        assert np.isfinite(fixed).all() and N.cells_of(fixed[None], pvt, W, (Y, X))[0] is not None, j
+    lab = _labels(size)
+    lab[:, 0, :] = lab[:, -1, :] = lab[:, :, 0] = lab[:, :, -1] = 2      # a one-cell frame of walls
+    lab[:, 5, 30] = 0                                           # one never-seen cell
+    n = len(T)
+    inside_pt = np.float32([(pvt[0] + 32) * W, (pvt[1] + 2) * W])
+    seg_a, seg_b = np.concatenate([T, np.tile(inside_pt, (n, 1))]), np.concatenate([np.tile(inside_pt, (n, 1)), T])
+    traj = T.reshape(n, 1, 2)
+    head = np.tile(np.int32([[[1, 0]]]), (n, 1, 1))
+    m = _mapper(size)
+    try:
+        assert tuple(settle(m, lab, pos)) == tuple(pvt)
+        g = _ground(m, size)
+        assert (g["type"] == R.UNKNOWN).sum() == 1 and (g["type"] == R.OCCUPIED).sum() == 2 * X + 2 * Y - 4
+        trav = N.traversable(g)
+        on_free = np.array([c is not None and bool(trav[c[1], c[0]]) for c in cells])
+        decided = ~has | on_free                                # where a value of a field tells whether the point had a cell
+        assert on_free.any() and (has & ~on_free).any()
+        # ---- the references
+        want = {"query": R.query(g, g["coc"], pvt, W, T)}
+        want["nf"], want["ns"] = N.field(g, T, pvt, W)
+        nf1, _ = N.field(g, inside_pt[None], pvt, W)
+        want["steps"] = FR.gather(nf1, T, pvt, W)
+        want["path"], want["len"] = N.path(nf1, T, pvt, W, 8)
+        want["hits"] = L.segments(g, seg_a, seg_b, pvt, W)
+        want["cost"], want["valid"] = CM.matrix(g, T, pvt, W)
+        want["gain"] = V.gain(g, T, pvt, 0.0, 0.45, W)
+        want["roll"] = RO.rollouts(g, traj, pvt, W)
+        want["foot"] = FP.footprints(g, traj, head, pvt, W, 0, 0, 0)
+        want["pnf"], want["cs"], want["pcounts"] = PQ.field(g, T, None, pvt, W, 0, 0, 0)
+        want["psteps"] = PQ.query(want["pnf"], T, None, pvt, W)
+        # ---- the host forms
+        got = {"query": m.ground_query(T)}
+        got["ns"] = m.ground_nf1_compute(T)
+        got["nf"] = m.read_ground_nf1()
+        assert m.ground_nf1_compute(inside_pt[None]) == 1
+        got["steps"] = m.ground_nf1_query(T)
+        got["path"], got["len"] = m.ground_nf1_path(T, 8)
+        got["hits"] = m.ground_segments(seg_a, seg_b)
+        got["cost"], got["valid"] = m.ground_costmat(T)
+        got["gain"] = m.ground_view_gain(T, 0.0, 0.45)
+        got["roll"] = m.ground_rollouts(traj)
+        got["foot"] = m.ground_footprints(traj, head, 0, 0, 0)
+        got["pcounts"] = m.ground_pose_nf1_compute(T, None, 0, 0, 0)
+        got["pnf"], got["cs"] = m.read_ground_pose_nf1()
+        got["psteps"] = m.ground_pose_nf1_query(T)
+        for key in want:
+            a, b = np.asarray(got[key]), np.asarray(want[key])
+            assert a.shape == b.shape and a.tobytes() == b.astype(a.dtype).tobytes(), key
+        # ---- each entry's verdict on "this point has a cell"
+        verdict = {"query": got["query"]["inside"] == 1, "segments a": got["hits"]["first"][:n] != -2, "segments b": got["hits"]["first"][n:] != -2,
+                   "view": got["gain"]["candidates"] >= 0, "rollouts": got["roll"]["end"] != RO.LEFT, "footprints": got["foot"]["end"] != FP.NO_PLACEMENT}
+        for key, v in verdict.items():
+            assert np.array_equal(v, has), key
+        fields = {"nf1 goals": np.array([c is not None and got["nf"][c[1], c[0]] == 0 for c in cells]), "nf1 query": got["steps"] >= 0,
+                  "nf1 path": got["len"] > 0, "costmat": got["valid"], "pose query": got["psteps"] >= 0,
+                  "pose goals": np.array([c is not None and bool((got["pnf"][:, c[1], c[0]] == 0).all()) for c in cells])}
+        for key, v in fields.items():
+            assert np.array_equal(v[decided], has[decided]) and not v[~has].any(), key
+        # ---- the _dev forms on the mapper's stream, back to back: the host forms' bytes
+        dev = torch.device("cuda", 0)
+        st = torch.cuda.ExternalStream(m.stream_handle(), device=dev)
+        out = {}
+
+        def buf(key, nbytes):
+            out[key] = torch.full((nbytes,), 0x5a, dtype=torch.uint8, device=dev)
+            return out[key].data_ptr()
+        with torch.cuda.stream(st):
+            d = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in
+                 (("T", T), ("p", inside_pt[None]), ("a", seg_a), ("b", seg_b), ("head", head))}
+            m.ground_query_dev(d["T"].data_ptr(), n, buf("query", 16 * n))
+            m.ground_nf1_compute_dev(d["T"].data_ptr(), n, d_n_sources=buf("ns", 4))
+            m.read_ground_nf1_dev(buf("nf", 4 * X * Y))
+            m.ground_nf1_compute_dev(d["p"].data_ptr(), 1)
+            m.ground_nf1_query_dev(d["T"].data_ptr(), n, buf("steps", 4 * n))
+            d_path = torch.zeros((n * 8 * 2,), dtype=torch.int32, device=dev)
+            m.ground_nf1_path_dev(d["T"].data_ptr(), n, 8, d_path.data_ptr(), buf("len", 4 * n))
+            m.ground_segments_dev(d["a"].data_ptr(), d["b"].data_ptr(), 2 * n, buf("hits", 24 * 2 * n))
+            m.ground_costmat_dev(d["T"].data_ptr(), n, buf("cost", 4 * n * n), buf("valid", n))
+            m.ground_view_gain_dev(d["T"].data_ptr(), 0, n, buf("gain", 16 * n), 0.0, 0.45)
+            m.ground_rollouts_dev(d["T"].data_ptr(), n, 1, buf("roll", 48 * n))
+            m.ground_footprints_dev(d["T"].data_ptr(), d["head"].data_ptr(), n, 1, buf("foot", 32 * n), 0, 0, 0)
+            m.ground_pose_nf1_compute_dev(d["T"].data_ptr(), 0, n, buf("pcounts", 8), 0, 0, 0)
+            m.read_ground_pose_nf1_dev(buf("pnf", 4 * 8 * X * Y), buf("cs", X * Y))
+            m.ground_pose_nf1_query_dev(d["T"].data_ptr(), 0, n, buf("psteps", 4 * n))
+        m.sync()
+        out["path"] = d_path
+        for key, t in out.items():
+            host = np.asarray(got[key], np.int32) if key in ("ns", "pcounts") else np.asarray(got[key])
+            assert t.cpu().numpy().tobytes() == (host.astype(np.uint8) if key == "valid" else host).tobytes(), key
     finally:
         m.close()
 

@@ -14,46 +14,13 @@ import ground_nf1_ref as N
 import ground_ref as R
 import los_ref
 from gie import _capi, scenes
-from stage_common import W, box_labels, build_host_probe, lidar_frames, mapper as _mapper, stage_calls_change_nothing, update as _update
+from ground_common import INVALID, P5A, settle as _settle, ground as _ground, xy as _xy, scene as _scene, same as _same
+from stage_common import W, box_labels, build_host_probe, lidar_frames, mapper as _mapper, stage_calls_change_nothing
 
 pytestmark = pytest.mark.gpu
-INVALID = 1                                                     # GIE_ERR_INVALID
-P5A = bytes([0x5a])
 NAMES = ["ogm_classify", "ray_register", "ray_free", "ray_finalize", "block_alloc", "fuse", "edt_pass_y", "edt_pass_x", "edt_pass_z", "mark",
          "frontiers", "wave_a", "wave_b", "waves", "commit", "edt_prep", "mark_commit", "ground_nf1", "ground", "ground_query", "cloud", "los",
          "los_query", "sdf", "sdf_query"]                       # gie_profile_read's entries before this section existed
-
-
-def _settle(m, lab, pos=(0.0, 0.0, 0.0)):
-    pos = tuple(np.float32(v) for v in pos)
-    for _ in range(2):
-        _update(m, pos, (1.0, 0.0, 0.0, 0.0), lab)
-    return m.pivot()
-
-
-def _ground(m, size, blocks=False, min_known=1):
-    """the ground field of the whole height: read_ground()'s planes"""
-    z = m.pivot()[2]
-    m.ground_compute(z, z + size[2] - 1, min_known, blocks)
-    return m.read_ground()
-
-
-def _xy(pvt, cells, shift=0.0):
-    """world points (float32 metres) of local cells (x, y): (cell + pvt + shift) * w, the product in float32"""
-    c = np.asarray(cells, np.float64).reshape(-1, 2) + np.array(pvt[:2])
-    return ((c.astype(np.float32) + np.float32(shift)) * np.float32(W)).astype(np.float32)
-
-
-def _scene(size, seed, n_boxes=14, unknown_slab=4, pos_k=2):
-    rng = np.random.default_rng(seed)
-    pos, q = scenes.pose(pos_k, W, delta_vox=3, yaw_deg=0.0)
-    pvt = scenes.local_pivot(pos, W, size)
-    boxes = []
-    for _ in range(n_boxes):
-        s = rng.integers(2, 9, size=3)
-        c = rng.integers(np.asarray(pvt) - 2, np.asarray(pvt) + np.asarray(size))
-        boxes.append((c, c + s))
-    return pos, box_labels(pvt, size, 0, boxes, unknown_slab)
 
 
 def _prefill(n, cap):
@@ -97,12 +64,6 @@ def _segment_points(rng, size, pvt):
     return pa, pb
 
 
-def _same(got, want, what):
-    for key in want.dtype.names:
-        assert np.array_equal(got[key], want[key]), (what, key, int((got[key] != want[key]).sum() if got[key].shape == want[key].shape else -1))
-    assert got.tobytes() == want.tobytes(), what
-
-
 # ---------------------------------------------------------------------------------------------------------- 1. segments
 @pytest.mark.parametrize("size", [(64, 24, 8), (65, 24, 8), (70, 24, 8), (130, 24, 8), (130, 1, 8)])
 def test_segments_equal_the_reference(size):
@@ -115,7 +76,7 @@ def test_segments_equal_the_reference(size):
         pa, pb = _segment_points(rng, size, pvt)
         seen = set()
         for blocks in (False, True):
-            g = _ground(m, size, blocks)
+            g = _ground(m, size, blocks=blocks)
             assert (g["type"] == R.UNKNOWN).any() and (g["type"] == R.OCCUPIED).any()
             for csq in (0, 4, 9):
                 for ut in (False, True):
@@ -268,7 +229,7 @@ def test_shortcut_of_random_polylines_of_any_int32():
     n, max_len = 40, 80
     try:
         pvt = _settle(m, lab, pos)
-        g = _ground(m, size, True)
+        g = _ground(m, size, blocks=True)
         rng = np.random.default_rng(8)
         inside = np.stack([rng.integers(0, size[0], (n, max_len)), rng.integers(0, size[1], (n, max_len))], 2)
         steps = np.cumsum(rng.integers(-1, 2, (n, max_len, 2)), axis=1) + inside[:, :1]           # slow drifts, points repeat

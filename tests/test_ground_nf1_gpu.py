@@ -11,34 +11,13 @@ import pytest
 import ground_nf1_ref as N
 import ground_ref as R
 from gie import _capi, scenes
-from stage_common import ROOT, W, box_labels, build_host_probe, lidar_frames, mapper as _mapper, stage_calls_change_nothing, update as _update
+from ground_common import INVALID, POISON, settle as _settle, ground as _ground, xy as _xy, plane as _plane, serpentine as _serpentine, scene as _scene
+from stage_common import ROOT, W, box_labels, build_host_probe, lidar_frames, mapper as _mapper, stage_calls_change_nothing
 
 pytestmark = pytest.mark.gpu
-INVALID = 1                                                     # GIE_ERR_INVALID
 CLEARANCES = (0, 1, 2, 4, 5, 9)
 HDR_FIELDS = ("x_size", "y_size", "z_size", "x_origin", "y_origin", "z_origin", "width", "type")
 LDS_BUDGET = 144 * 1024                                         # bytes of the three bit planes the propagation keeps in LDS
-POISON = 0x5a5a5a5a
-
-
-def _settle(m, lab, pos=(0.0, 0.0, 0.0)):
-    pos = tuple(np.float32(v) for v in pos)
-    for _ in range(2):
-        _update(m, pos, (1.0, 0.0, 0.0, 0.0), lab)
-    return m.pivot()
-
-
-def _ground(m, size, blocks=False, min_known=1):
-    """the ground field of the whole height: read_ground()'s planes"""
-    z = m.pivot()[2]
-    m.ground_compute(z, z + size[2] - 1, min_known, blocks)
-    return m.read_ground()
-
-
-def _xy(pvt, cells, shift=0.0):
-    """world points (float32 metres) of local cells (x, y): (cell + pvt + shift) * w, the product in float32"""
-    c = np.asarray(cells, np.float64).reshape(-1, 2) + np.array(pvt[:2])
-    return ((c.astype(np.float32) + np.float32(shift)) * np.float32(W)).astype(np.float32)
 
 
 def _flags(ut, ff):
@@ -54,39 +33,6 @@ def _check(m, g, pvt, goals, csq=0, ut=False, ff=False):
     assert n == n_want, (csq, ut, ff, n, n_want)
     assert np.array_equal(nf, want), (csq, ut, ff, int((nf != want).sum()))
     return nf, n
-
-
-def _plane(size, lab2d):
-    """a [Y][X] label plane on every layer"""
-    return np.repeat(np.asarray(lab2d, np.int8)[None], size[2], axis=0)
-
-
-def _serpentine(X, Y, pitch):
-    """(label plane [Y][X], the cells (x, y) in order) of ONE one-cell-wide corridor through walls: rows `pitch` apart from y = 1,
-    each from x = 1 to X - 2, joined at alternating ends"""
-    lab = np.full((Y, X), 2, np.int8)
-    cells = []
-    rows = list(range(1, Y - 1, pitch))
-    for i, y in enumerate(rows):
-        xs = list(range(1, X - 1)) if i % 2 == 0 else list(range(X - 2, 0, -1))
-        cells += [(x, y) for x in xs]
-        if i + 1 < len(rows):
-            cells += [(xs[-1], yy) for yy in range(y + 1, rows[i + 1])]
-    c = np.array(cells)
-    lab[c[:, 1], c[:, 0]] = 1
-    return lab, c
-
-
-def _scene(size, seed, n_boxes=14, unknown_slab=4, pos_k=2):
-    rng = np.random.default_rng(seed)
-    pos, q = scenes.pose(pos_k, W, delta_vox=3, yaw_deg=0.0)
-    pvt = scenes.local_pivot(pos, W, size)
-    boxes = []
-    for _ in range(n_boxes):
-        s = rng.integers(2, 9, size=3)
-        c = rng.integers(np.asarray(pvt) - 2, np.asarray(pvt) + np.asarray(size))
-        boxes.append((c, c + s))
-    return pos, box_labels(pvt, size, 0, boxes, unknown_slab)
 
 
 # ---------------------------------------------------------------------------------------------------------- 1. word boundaries
@@ -143,7 +89,7 @@ def test_clearances_against_a_pillar_and_a_wall():
         pvt = _settle(m, lab)
         seen = set()
         for blocks in (False, True):
-            g = _ground(m, size, blocks)
+            g = _ground(m, size, blocks=blocks)
             assert (g["type"] == R.UNKNOWN).any() and (g["type"] == R.FNT).any() and (g["type"] == R.OCCUPIED).any()
             for ut in (False, True):
                 for csq in CLEARANCES:

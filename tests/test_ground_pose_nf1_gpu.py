@@ -12,11 +12,10 @@ import ground_nf1_ref as N
 import ground_pose_nf1_ref as Q
 import ground_ref as R
 from gie import _capi, scenes
+from ground_common import INVALID, P5A, settle as _settle, xy as _xy, ground
 from stage_common import W, box_labels, mapper as _mapper, stage_calls_change_nothing, update as _update
 
 pytestmark = pytest.mark.gpu
-INVALID = 1                                                     # GIE_ERR_INVALID
-P5A = bytes([0x5a])
 NAMES = ["ogm_classify", "ray_register", "ray_free", "ray_finalize", "block_alloc", "fuse", "edt_pass_y", "edt_pass_x", "edt_pass_z", "mark",
          "frontiers", "wave_a", "wave_b", "waves", "commit", "edt_prep", "mark_commit", "ground_nf1", "ground", "ground_query", "cloud", "los",
          "los_query", "sdf", "sdf_query"]                       # gie_profile_read's entries of a mapper without frontier clusters: the parent's
@@ -24,24 +23,11 @@ FEET = [(0, 0, 0), (64, 4, 9), (9, 9, 1), (Q.MAX_SQ, 4, 1)]     # (front_sq, bac
 FP = (64, 4, 9)
 
 
-def _settle(m, lab, pos=(0.0, 0.0, 0.0)):
-    pos = tuple(np.float32(v) for v in pos)
-    for _ in range(2):
-        _update(m, pos, (1.0, 0.0, 0.0, 0.0), lab)
-    return m.pivot()
-
-
 def _ground(m, size):
     """the ground field of the inner layers: the volume's top and bottom layers are frontier voxels everywhere, a band that holds them
     has no FREE column"""
-    z, skip = m.pivot()[2], 2 if size[2] >= 8 else 1
-    m.ground_compute(z + skip, z + size[2] - 1 - skip, 1, False)
-    return m.read_ground()
-
-
-def _xy(pvt, cells):
-    c = np.asarray(cells, np.float64).reshape(-1, 2) + np.array(pvt[:2])
-    return (c.astype(np.float32) * np.float32(W)).astype(np.float32)
+    skip = 2 if size[2] >= 8 else 1
+    return ground(m, size, (skip, size[2] - 1 - skip))
 
 
 def _labels(size, plane):

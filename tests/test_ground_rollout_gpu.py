@@ -12,62 +12,16 @@ import gie
 import ground_ref as R
 import ground_rollout_ref as Q
 from gie import _capi, scenes
-from stage_common import W, box_labels, build_host_probe, lidar_frames, mapper as _mapper, stage_calls_change_nothing, update as _update
+from ground_common import INVALID, P5A, settle as _settle, ground as _ground, xy as _xy, scene as _scene, open_cells as _open, same as _same, arc
+from stage_common import W, box_labels, build_host_probe, lidar_frames, mapper as _mapper, stage_calls_change_nothing
 
 pytestmark = pytest.mark.gpu
-INVALID = 1                                                     # GIE_ERR_INVALID
-P5A = bytes([0x5a])
 NAMES = ["ogm_classify", "ray_register", "ray_free", "ray_finalize", "block_alloc", "fuse", "edt_pass_y", "edt_pass_x", "edt_pass_z", "mark",
          "frontiers", "wave_a", "wave_b", "waves", "commit", "edt_prep", "mark_commit", "ground_nf1", "ground", "ground_query", "cloud", "los",
          "los_query", "sdf", "sdf_query"]                       # gie_profile_read's entries of a mapper without frontier clusters
 RD = gie.GROUND_ROLLOUT_DTYPE
 # clearance_sq x inflate_sq x the two flags: every combination, in an order that mixes them
 COMBOS = [(c, i, u, nf) for (u, nf), c, i in itertools.product(((False, False), (True, True), (False, True), (True, False)), (0, 1, 4, 9), (0, 16, 1 << 22))]
-
-
-def _settle(m, lab, pos=(0.0, 0.0, 0.0)):
-    pos = tuple(np.float32(v) for v in pos)
-    for _ in range(2):
-        _update(m, pos, (1.0, 0.0, 0.0, 0.0), lab)
-    return m.pivot()
-
-
-def _ground(m, size, blocks=False, min_known=1):
-    """the ground field of the whole height: read_ground()'s planes"""
-    z = m.pivot()[2]
-    m.ground_compute(z, z + size[2] - 1, min_known, blocks)
-    return m.read_ground()
-
-
-def _xy(pvt, cells, shift=0.0):
-    """world points (float32 metres) of local cells (any shape (.., 2), fractions allowed): (cell + pvt + shift) * w, the product in float32"""
-    c = np.asarray(cells, np.float64) + np.array(pvt[:2])
-    return ((c.astype(np.float32) + np.float32(shift)) * np.float32(W)).astype(np.float32)
-
-
-def _scene(size, seed, n_boxes=14, unknown_slab=4, pos_k=2):
-    rng = np.random.default_rng(seed)
-    pos, q = scenes.pose(pos_k, W, delta_vox=3, yaw_deg=0.0)
-    pvt = scenes.local_pivot(pos, W, size)
-    boxes = []
-    for _ in range(n_boxes):
-        s = rng.integers(2, 9, size=3)
-        c = rng.integers(np.asarray(pvt) - 2, np.asarray(pvt) + np.asarray(size))
-        boxes.append((c, c + s))
-    return pos, box_labels(pvt, size, 0, boxes, unknown_slab)
-
-
-def _open(g):
-    """bool [Y][X]: FREE or FNT columns (a FNT column is a free one with a never-seen voxel beside it: over the whole height of a
-    volume that is nearly every free column)"""
-    t = np.asarray(g["type"])
-    return (t == R.FREE) | (t == R.FNT)
-
-
-def _same(got, want, what):
-    for key in want.dtype.names:
-        assert np.array_equal(got[key], want[key]), (what, key, got[key].tolist(), want[key].tolist())
-    assert got.tobytes() == want.tobytes(), what
 
 
 def _flags(unknown, nf1):
@@ -92,14 +46,6 @@ def _both_forms(m, st, xy, c, i, u, nf, want, what):
     return got
 
 
-def _arc(start, heading, step, turn, T):
-    """T poses (cells, fractions) of a unicycle arc: steps of `step` cells, the heading turning by `turn` radians per step"""
-    k = np.arange(T)
-    th = heading + turn * k
-    d = np.stack([np.cos(th), np.sin(th)], 1) * step
-    return np.asarray(start, np.float64) + np.concatenate([np.zeros((1, 2)), np.cumsum(d[:-1], 0)])
-
-
 def _fan(g, pvt, size, T, rng, n=37):
     """n trajectories of T poses (cells, fractions) from FREE (or FNT) cells: straight lines and arcs with steps of 0.3 .. 3 cells, small circles
     in the most open places (the long clear ones), horizontal sweeps over x = 63 | 64 and 127 | 128, and poses on gie_pos2coord's ties"""
@@ -112,16 +58,16 @@ def _fan(g, pvt, size, T, rng, n=37):
     for j in range(n):
         kind = j % 6
         if kind in (0, 1):                                      # a straight line; every other one with long steps: legs that jump over cells
-            out.append(_arc(free[rng.integers(len(free))] + rng.uniform(-0.4, 0.4, 2), rng.uniform(0, 2 * np.pi), rng.uniform(0.3 if kind == 0 else 2.0, 3.0), 0.0, T))
+            out.append(arc(free[rng.integers(len(free))] + rng.uniform(-0.4, 0.4, 2), rng.uniform(0, 2 * np.pi), rng.uniform(0.3 if kind == 0 else 2.0, 3.0), 0.0, T)[0])
         elif kind == 2:                                         # an arc
-            out.append(_arc(free[rng.integers(len(free))] + rng.uniform(-0.4, 0.4, 2), rng.uniform(0, 2 * np.pi), rng.uniform(0.3, 3.0), rng.uniform(-0.2, 0.2), T))
+            out.append(arc(free[rng.integers(len(free))] + rng.uniform(-0.4, 0.4, 2), rng.uniform(0, 2 * np.pi), rng.uniform(0.3, 3.0), rng.uniform(-0.2, 0.2), T)[0])
         elif kind == 3:                                         # a small circle in an open place: the long clear ones
-            out.append(_arc(far[(j // 6) % len(far)], rng.uniform(0, 2 * np.pi), 0.3, rng.choice([-1, 1]) * rng.uniform(0.2, 0.5), T))
+            out.append(arc(far[(j // 6) % len(far)], rng.uniform(0, 2 * np.pi), 0.3, rng.choice([-1, 1]) * rng.uniform(0.2, 0.5), T)[0])
         elif kind == 4:                                         # along x towards a word boundary of the bit plane and over it
             x0 = [max(64 - T // 2, 0), max(128 - T // 2, 0), 60, 0][(j // 6) % 4]
-            out.append(_arc((min(x0, X - 1), int(rng.integers(0, Y))), 0.0, 1.0, 0.0, T))
+            out.append(arc((min(x0, X - 1), int(rng.integers(0, Y))), 0.0, 1.0, 0.0, T)[0])
         else:                                                   # every pose on a tie of the rounding: (cell + 0.5), both axes
-            out.append(np.floor(_arc(free[rng.integers(len(free))], rng.uniform(0, 2 * np.pi), rng.uniform(0.5, 1.5), 0.0, T)) + 0.5)
+            out.append(np.floor(arc(free[rng.integers(len(free))], rng.uniform(0, 2 * np.pi), rng.uniform(0.5, 1.5), 0.0, T)[0]) + 0.5)
     return np.stack(out)
 
 
@@ -272,7 +218,7 @@ def test_4096_poses():
         nf = m.read_ground_nf1()
         rng = np.random.default_rng(4096)
         fan = _fan(g, pvt, size, 4096, rng, n=6)
-        xy = _xy(pvt, np.stack([fan[3], _arc(fan[0][0], 0.3, 0.02, 0.0005, 4096)]))   # a small circle, and a slow drift across the field
+        xy = _xy(pvt, np.stack([fan[3], arc(fan[0][0], 0.3, 0.02, 0.0005, 4096)[0]]))   # a small circle, and a slow drift across the field
         st = torch.cuda.ExternalStream(m.stream_handle(), device=torch.device("cuda", 0))
         want = Q.rollouts(g, xy, pvt, W, 0, 1 << 22, Q.NF1, nf)
         got = _both_forms(m, st, xy, 0, 1 << 22, False, True, want, "T = 4096")
@@ -370,7 +316,7 @@ def test_chained_behind_the_ground_field_and_its_nf1_with_one_sync():
         dev = torch.device("cuda", 0)
         rng = np.random.default_rng(1)
         goal = _xy(pvt, [(40, 20), (10, 30)])
-        fan = np.stack([_arc((35, 20) + rng.uniform(-8, 8, 2), rng.uniform(0, 6.28), rng.uniform(0.3, 2.0), rng.uniform(-0.1, 0.1), 40) for _ in range(33)])
+        fan = np.stack([arc((35, 20) + rng.uniform(-8, 8, 2), rng.uniform(0, 6.28), rng.uniform(0.3, 2.0), rng.uniform(-0.1, 0.1), 40)[0] for _ in range(33)])
         xy = _xy(pvt, fan)
         n, T = xy.shape[0], xy.shape[1]
         with torch.cuda.stream(torch.cuda.ExternalStream(m.stream_handle(), device=dev)):
@@ -530,7 +476,7 @@ def test_section_calls_change_nothing_of_the_map_update():
             a.ground_nf1_compute(_xy(field["pvt"], [(24, 20)]), 0, True)
         if phase in ("fuse", "edt", "merge"):
             r = np.random.default_rng(k)
-            xy = _xy(field["pvt"], np.stack([_arc(r.uniform(0, 40, 2), r.uniform(0, 6.28), r.uniform(0.3, 2.0), 0.05, 70) for _ in range(30)]))
+            xy = _xy(field["pvt"], np.stack([arc(r.uniform(0, 40, 2), r.uniform(0, 6.28), r.uniform(0.3, 2.0), 0.05, 70)[0] for _ in range(30)]))
             a.ground_rollouts(xy, k % 3, 16, k % 2 == 0, True)
 
     stage_calls_change_nothing(size, (frame(k) for k in range(5)), _mapper, calls, n_probe=2000)

@@ -13,47 +13,14 @@ import ground_ref as R
 import ground_view_ref as V
 import los_ref
 from gie import _capi, scenes
-from stage_common import W, box_labels, build_host_probe, lidar_frames, mapper as _mapper, stage_calls_change_nothing, update as _update
+from ground_common import INVALID, P5A, settle as _settle, ground as _ground, xy as _xy, scene as _scene, same as _same
+from stage_common import W, box_labels, build_host_probe, lidar_frames, mapper as _mapper, stage_calls_change_nothing
 
 pytestmark = pytest.mark.gpu
-INVALID = 1                                                     # GIE_ERR_INVALID
-P5A = bytes([0x5a])
 NAMES = ["ogm_classify", "ray_register", "ray_free", "ray_finalize", "block_alloc", "fuse", "edt_pass_y", "edt_pass_x", "edt_pass_z", "mark",
          "frontiers", "wave_a", "wave_b", "waves", "commit", "edt_prep", "mark_commit", "ground_nf1", "ground", "ground_query", "cloud", "los",
          "los_query", "sdf", "sdf_query"]                       # gie_profile_read's entries of a mapper without frontier clusters
 SD = gie.VIEW_SCORE_DTYPE
-
-
-def _settle(m, lab, pos=(0.0, 0.0, 0.0)):
-    pos = tuple(np.float32(v) for v in pos)
-    for _ in range(2):
-        _update(m, pos, (1.0, 0.0, 0.0, 0.0), lab)
-    return m.pivot()
-
-
-def _ground(m, size, blocks=False, min_known=1):
-    """the ground field of the whole height: read_ground()'s planes"""
-    z = m.pivot()[2]
-    m.ground_compute(z, z + size[2] - 1, min_known, blocks)
-    return m.read_ground()
-
-
-def _xy(pvt, cells, shift=0.0):
-    """world points (float32 metres) of local cells (x, y): (cell + pvt + shift) * w, the product in float32"""
-    c = np.asarray(cells, np.float64).reshape(-1, 2) + np.array(pvt[:2])
-    return ((c.astype(np.float32) + np.float32(shift)) * np.float32(W)).astype(np.float32)
-
-
-def _scene(size, seed, n_boxes=14, unknown_slab=4, pos_k=2):
-    rng = np.random.default_rng(seed)
-    pos, q = scenes.pose(pos_k, W, delta_vox=3, yaw_deg=0.0)
-    pvt = scenes.local_pivot(pos, W, size)
-    boxes = []
-    for _ in range(n_boxes):
-        s = rng.integers(2, 9, size=3)
-        c = rng.integers(np.asarray(pvt) - 2, np.asarray(pvt) + np.asarray(size))
-        boxes.append((c, c + s))
-    return pos, box_labels(pvt, size, 0, boxes, unknown_slab)
 
 
 def _view_points(size, pvt, g):
@@ -73,12 +40,6 @@ def _view_points(size, pvt, g):
     odd2 = _xy(pvt, [(cx(5), 0)])
     odd2[:, 1] = 1e30
     return np.concatenate([xy, ties, odd, odd2])
-
-
-def _same(got, want, what):
-    for key in want.dtype.names:
-        assert np.array_equal(got[key], want[key]), (what, key, got[key].tolist(), want[key].tolist())
-    assert got.tobytes() == want.tobytes(), what
 
 
 def _normals(base, n):
