@@ -1560,6 +1560,15 @@ extern "C" int gie_debug_tile_state(gie_mapper *m, uint8_t *tknown, uint8_t *tsk
     scalars[GIE_DBG_TS_STATE2] = cnt[GIE_CNT_STATE2];
     return be_sync(&m->be) != 0 ? GIE_ERR_DEVICE : GIE_OK;
 }
+/* test hook (not in gie.h): the per-plane obstacle flags the last gie_fuse left (c.zocc, Z bytes: EDT pass Y skips the planes whose
+ * flag is 0), copied out as they are — no launch, nothing written */
+extern "C" int gie_debug_plane_flags(gie_mapper *m, uint8_t *flags)
+{
+    if (!m || !flags) { gie_set_err("gie_debug_plane_flags: bad arguments"); return GIE_ERR_INVALID; }
+    if (be_sync(&m->be) != 0) return GIE_ERR_DEVICE;
+    be_d2h(&m->be, flags, m->c.zocc, (size_t)m->c.Z);
+    return be_sync(&m->be) != 0 ? GIE_ERR_DEVICE : GIE_OK;
+}
 /* test hook (not in gie.h): the frame counter as if `ct` map updates had run — the next gie_set_pose counts ct + 1.  Nothing else
  * changes: the stamp planes keep what earlier updates wrote, so a test can stand right before the stamp wrap of gie_set_pose
  * (ct + 1 a multiple of 2^18) without 262 144 updates.  Between two map updates only, never inside an open merge.  What remembers

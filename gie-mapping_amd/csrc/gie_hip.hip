@@ -525,7 +525,9 @@ static void be_edt_prep(be_state *b, const gie_ctx &c)
  * returns at once */
 static void be_edt(be_state *b, const gie_ctx &c, int full)
 {
-    dim3 gy((c.X + GIE_EDTY_COLS - 1) / GIE_EDTY_COLS, c.Z);
+    /* a linear grid: the kernels derive (strip, z) from the workgroup index so that both 64-byte strips of a 128-byte type line
+     * run on one XCD (gie_edty_strip, gie_ops.h) */
+    dim3 gy(16 * gie_edty_groups((c.X + GIE_EDTY_COLS - 1) / GIE_EDTY_COLS, c.Z));
     be_prof(b, GIE_K_EDT_Y, 0);
     /* one 32-voxel mask word per thread: with only the planes that hold obstacles at work, the
      * pass is bound by how many loads are in flight, not by bytes */
@@ -533,7 +535,7 @@ static void be_edt(be_state *b, const gie_ctx &c, int full)
     if ((c.X & 3) == 0) {
         /* 16 lanes x 4 columns per workgroup (more, smaller workgroups than 32 lanes) */
         const int yb = c.Y > 512 ? 32 : 16, nq = (c.Y + yb - 1) / yb;
-        dim3 g4((c.X / 4 + GIE_EDTY4_LANES - 1) / GIE_EDTY4_LANES, c.Z), b4(GIE_EDTY4_LANES, nq);
+        dim3 g4(16 * gie_edty_groups((c.X / 4 + GIE_EDTY4_LANES - 1) / GIE_EDTY4_LANES, c.Z)), b4(GIE_EDTY4_LANES, nq);
         if (yb == 16) GIE_LAUNCH(b, k_edt_y4<16>, g4, b4, 0, c);
         else GIE_LAUNCH(b, k_edt_y4<32>, g4, b4, 0, c);
     }

@@ -447,10 +447,11 @@ __global__ __launch_bounds__(GIE_EDTY_COLS * TPC) void k_edt_y(const gie_ctx c)
     constexpr int QW = YW / TPC;                         /* mask words per thread (TPC threads share a column) */
     __shared__ uint32_t s_bits[YW][GIE_EDTY_COLS];
     const int col = threadIdx.x, q = threadIdx.y;
-    const int x = blockIdx.x * GIE_EDTY_COLS + col;
-    const int z = blockIdx.y;
-    if (!c.zocc[z]) return;                              /* plane without obstacle: passes X/Z never read its cy1 */
     const int X = c.X, Y = c.Y;
+    int strip, z;                                        /* the two 64-byte strips of a type line on one XCD (gie_edty_strip) */
+    if (!gie_edty_strip(blockIdx.x, (X + GIE_EDTY_COLS - 1) / GIE_EDTY_COLS, c.Z, &strip, &z)) return;
+    const int x = strip * GIE_EDTY_COLS + col;
+    if (!c.zocc[z]) return;                              /* plane without obstacle: passes X/Z never read its cy1 */
     const bool in = x < X;
     const int8_t *t = c.glb_type + (size_t)z * X * Y + (in ? x : 0);
 #pragma unroll
@@ -504,17 +505,31 @@ __global__ __launch_bounds__(GIE_EDTY_COLS * TPC) void k_edt_y(const gie_ctx c)
  * wave moves 128-byte row segments per instruction instead of 64 single bytes (the byte form is
  * bound by the number of memory instructions, not by bytes).  Thread (l, q) owns the YB
  * positions y = q·YB .. of its four columns; what lies below / above its own mask word comes
- * from the other threads' words in LDS (one 16-byte read per word covers the four columns). */
+ * from the other threads' words in LDS.
+ * The kernel is bound by its vector ALU work, not by bytes (halving its HBM reads left its time
+ * where it was), so the arithmetic is kept short:
+ *   - the masks are built byte-parallel: one zero-byte test per dword finds the OCCUPIED bytes of
+ *     the four columns, eight rows are gathered per accumulator word (bit 8 cc + k);
+ *   - s_nz[column] has bit w set when word w of the column holds an obstacle, so the last word
+ *     below and the first word above a thread's own are two bit scans and two LDS reads per
+ *     column instead of a walk over all the other words;
+ *   - "nothing below" is -65536 and "nothing above" is 65535: the nearer of the two (ties: the
+ *     larger y) is one comparison without special cases, and 0xffff comes out where the column
+ *     is empty. */
 #define GIE_EDTY4_LANES 16      /* lanes along x of a workgroup (more, smaller workgroups than 32) */
 template <int YB>
 __global__ __launch_bounds__(32 * GIE_EDTY4_LANES) void k_edt_y4(const gie_ctx c)
 {
     __shared__ __attribute__((aligned(16))) uint32_t s_m[32][GIE_EDTY4_LANES * 4];
-    const int l = threadIdx.x, q = threadIdx.y, nq = blockDim.y;
-    const int x = (blockIdx.x * GIE_EDTY4_LANES + l) * 4;
-    const int z = blockIdx.y;
-    if (!c.zocc[z]) return;                              /* plane without obstacle: passes X/Z never read its cy1 */
+    __shared__ __attribute__((aligned(16))) uint32_t s_nz[GIE_EDTY4_LANES * 4];
+    const int l = threadIdx.x, q = threadIdx.y;
     const int X = c.X, Y = c.Y;
+    int strip, z;                                        /* the two 64-byte strips of a type line on one XCD (gie_edty_strip) */
+    if (!gie_edty_strip(blockIdx.x, (X / 4 + GIE_EDTY4_LANES - 1) / GIE_EDTY4_LANES, c.Z, &strip, &z)) return;
+    const int x = (strip * GIE_EDTY4_LANES + l) * 4;
+    if (!c.zocc[z]) return;                              /* plane without obstacle: passes X/Z never read its cy1 */
+    if (q == 0) *reinterpret_cast<uint4 *>(&s_nz[4 * l]) = make_uint4(0u, 0u, 0u, 0u);
+    __syncthreads();
     const bool in = x < X;
     const size_t base = (size_t)z * X * Y + (in ? x : 0);
     uint32_t m[4] = {0u, 0u, 0u, 0u};
@@ -527,48 +542,51 @@ __global__ __launch_bounds__(32 * GIE_EDTY4_LANES) void k_edt_y4(const gie_ctx c
             v[k] = *reinterpret_cast<const uint32_t *>(t + (size_t)min(y, Y - 1) * X);
         }
         const uint32_t ymask = (q * YB + YB <= Y) ? 0xffffffffu : ((q * YB < Y) ? (0xffffffffu >> (32 - (Y - q * YB))) : 0u);
+        uint32_t acc[YB / 8];                             /* bit 8 cc + k: column cc is OCCUPIED in row 8 j + k */
+#pragma unroll
+        for (int j = 0; j < YB / 8; j++) acc[j] = 0u;
 #pragma unroll
         for (int k = 0; k < YB; k++) {
-#pragma unroll
-            for (int cc = 0; cc < 4; cc++) m[cc] |= (uint32_t)(((v[k] >> (8 * cc)) & 0xffu) == (uint32_t)GIE_VOX_OCCUPIED) << k;
+            const uint32_t t2 = v[k] ^ (0x01010101u * (uint32_t)GIE_VOX_OCCUPIED);          /* a zero byte where the type is OCCUPIED */
+            const uint32_t zb = ~(((t2 & 0x7f7f7f7fu) + 0x7f7f7f7fu) | t2) & 0x80808080u;    /* bit 7 of those bytes */
+            acc[k >> 3] |= (zb >> 7) << (k & 7);
         }
 #pragma unroll
-        for (int cc = 0; cc < 4; cc++) m[cc] &= ymask;
+        for (int cc = 0; cc < 4; cc++) {
+#pragma unroll
+            for (int j = 0; j < YB / 8; j++) m[cc] |= ((acc[j] >> (8 * cc)) & 0xffu) << (8 * j);
+            m[cc] &= ymask;
+            if (m[cc]) atomicOr(&s_nz[4 * l + cc], 1u << q);
+        }
     }
     *reinterpret_cast<uint4 *>(&s_m[q][4 * l]) = make_uint4(m[0], m[1], m[2], m[3]);
     __syncthreads();
     if (!in) return;
-    int pl[4] = {-1, -1, -1, -1}, nf[4] = {-1, -1, -1, -1};
-    for (int w = 0; w < q; w++) {                         /* last obstacle below this thread's positions */
-        const uint4 o = *reinterpret_cast<const uint4 *>(&s_m[w][4 * l]);
-        const uint32_t ow[4] = {o.x, o.y, o.z, o.w};
+    const uint4 nzv = *reinterpret_cast<const uint4 *>(&s_nz[4 * l]);
+    const uint32_t nz[4] = {nzv.x, nzv.y, nzv.z, nzv.w};
+    const uint32_t mlow = (1u << q) - 1u, mhigh = ~((2u << q) - 1u);                       /* the words below / above this thread's */
+    int pl[4], nf[4];
 #pragma unroll
-        for (int cc = 0; cc < 4; cc++) if (ow[cc]) pl[cc] = w * YB + 31 - __clz(ow[cc]);
-    }
-    for (int w = nq - 1; w > q; w--) {                    /* first obstacle above them */
-        const uint4 o = *reinterpret_cast<const uint4 *>(&s_m[w][4 * l]);
-        const uint32_t ow[4] = {o.x, o.y, o.z, o.w};
-#pragma unroll
-        for (int cc = 0; cc < 4; cc++) if (ow[cc]) nf[cc] = w * YB + __ffs(ow[cc]) - 1;
+    for (int cc = 0; cc < 4; cc++) {
+        const uint32_t b = nz[cc] & mlow, a = nz[cc] & mhigh;
+        const int wb = b ? 31 - __clz(b) : 0, wa = a ? __ffs(a) - 1 : 0;
+        const uint32_t ob = s_m[wb][4 * l + cc], oa = s_m[wa][4 * l + cc];
+        pl[cc] = b ? wb * YB + 31 - __clz(ob) : -65536;  /* last obstacle below this thread's positions */
+        nf[cc] = a ? wa * YB + __ffs(oa) - 1 : 65535;     /* first obstacle above them */
     }
     uint16_t *out = c.cy1 + base;
 #pragma unroll
     for (int k = 0; k < YB; k++) {
         const int y = q * YB + k;
-        if (y >= Y) break;
         uint32_t r4[4];
 #pragma unroll
         for (int cc = 0; cc < 4; cc++) {
-            const uint32_t bw = m[cc];
-            const uint32_t lo = bw & (0xffffffffu >> (31 - k));
-            const int below = lo ? q * YB + 31 - __clz(lo) : pl[cc];
-            const uint32_t hi = bw >> k;
+            const uint32_t hi = m[cc] >> k;
+            pl[cc] = (hi & 1u) ? y : pl[cc];              /* (running: the last obstacle at or below y) */
             const int above = hi ? y + __ffs(hi) - 1 : nf[cc];
-            int r;
-            if (above >= 0 && (below < 0 || above - y <= y - below)) r = above; else r = below;
-            r4[cc] = r < 0 ? 0xffffu : (uint32_t)r;
+            r4[cc] = (uint32_t)((above - y <= y - pl[cc]) ? above : pl[cc]);
         }
-        *reinterpret_cast<uint2 *>(out + (size_t)y * X) = make_uint2(r4[0] | (r4[1] << 16), r4[2] | (r4[3] << 16));
+        if (y < Y) *reinterpret_cast<uint2 *>(out + (size_t)y * X) = make_uint2(r4[0] | (r4[1] << 16), r4[2] | (r4[3] << 16));
     }
 }
 

@@ -1632,4 +1632,20 @@ GIE_DEV void gie_query_voxel(const gie_ctx &c, const int32_t *xyz, int i, gie_vo
     }
 }
 
+/* EDT pass Y, which (strip, z) a workgroup takes.  A workgroup reads a 64-byte strip of every type row of its plane, so two
+ * strips share each 128-byte line; workgroups are dealt round-robin over the eight XCDs, whose L2s each fetch a line of their
+ * own.  With the launch's linear workgroup index l = 16 g + 8 h + r (r < 8, h < 2) the two strips 2 p + h of a line of plane z
+ * — pair number 8 g + r = z * ceil(nstrip / 2) + p — get indices that are equal modulo 8 and eight apart: one XCD, close in
+ * time, and the line is fetched once.  (Placement is a matter of speed only: any mapping that takes every (strip, z) once is
+ * right.)  Returns 0 for the indices that pad the launch (the missing half of an odd strip count, the last group's tail). */
+GIE_HD int gie_edty_groups(int nstrip, int Z) { return (((nstrip + 1) >> 1) * Z + 7) >> 3; }      /* the launch has 16 workgroups per group */
+GIE_HD int gie_edty_strip(int l, int nstrip, int Z, int *strip, int *z)
+{
+    const int np = (nstrip + 1) >> 1;
+    const int pair = ((l >> 4) << 3) | (l & 7);
+    *z = pair / np;
+    *strip = 2 * (pair - *z * np) + ((l >> 3) & 1);
+    return *z < Z && *strip < nstrip;
+}
+
 #endif /* GIE_OPS_H */
