@@ -109,6 +109,12 @@ struct gie_gpose_cache {
     int valid = 0;                        /* a compute has been enqueued on the current ground field */
     int reverse = 0;                      /* that compute had GIE_GROUND_POSE_NF1_REVERSE */
 };
+/* the ground signed distance field (gie_ground_sdf.inc.h): allocated at the section's first call through gie_dalloc; it belongs to
+ * one ground field and is recomputed at the first call after a gie_ground_compute* */
+struct gie_gsdf_cache {
+    int32_t *ids = nullptr;               /* inside_dist_sq, X * Y, and behind it the count of interior obstacle columns */
+    int valid = 0;                        /* the inside pass has been enqueued on the current ground field */
+};
 /* the ground frontier clusters (gie_ground_frontier.inc.h): allocated at their first compute through gie_dalloc, kept until the next
  * compute; they refer to the ground field's pivot and are invalidated by the next gie_ground_compute* */
 struct gie_gfr_cache {
@@ -172,6 +178,7 @@ struct gie_mapper {
     gie_ground_cache ground;              /* the ground costmap (HIP backend: gie_ground.inc.h) */
     gie_gnf1_cache gnf1;                  /* the ground navigation function (HIP backend: gie_ground_nf1.inc.h) */
     gie_gpose_cache gpose;                /* the ground pose navigation function (HIP backend: gie_ground_pose_nf1.inc.h) */
+    gie_gsdf_cache gsdf;                  /* the ground signed distance field (HIP backend: gie_ground_sdf.inc.h) */
     uint64_t *glos_blk = nullptr;         /* ground line of sight (HIP backend: gie_ground_los.inc.h): the blocked bit plane, allocated at the first call and rebuilt by every call */
     gie_gfr_cache gfr;                    /* the ground frontier clusters (HIP backend: gie_ground_frontier.inc.h) */
     gie_gcm_cache gcm;                    /* the ground cost matrix's scratch (HIP backend: gie_ground_costmat.inc.h) */

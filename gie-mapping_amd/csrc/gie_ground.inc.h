@@ -392,6 +392,7 @@ extern "C" int gie_ground_compute_dev(gie_mapper *m, const gie_ground_param *p, 
     m->gnf1.valid = 0;                                          /* (gie_ground_nf1.inc.h: its field was of the planes just overwritten) */
     m->gfr.valid = 0;                                           /* (gie_ground_frontier.inc.h: so were its clusters) */
     m->gpose.valid = 0;                                         /* (gie_ground_pose_nf1.inc.h: and its field) */
+    m->gsdf.valid = 0;                                          /* (gie_ground_sdf.inc.h: and its inside distances) */
     return GIE_OK;
 }
 extern "C" int gie_ground_compute(gie_mapper *m, const gie_ground_param *p, int32_t counts[4])

@@ -605,3 +605,4 @@ static void be_waves(be_state *b, const gie_ctx &c, int with_ab, int record_seed
 #include "gie_ground_rollout.inc.h"
 #include "gie_ground_footprint.inc.h"
 #include "gie_ground_pose_nf1.inc.h"
+#include "gie_ground_sdf.inc.h"

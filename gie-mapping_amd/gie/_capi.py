@@ -189,6 +189,17 @@ class GroundPoseNf1Param(C.Structure):
     _fields_ = [("front_sq", C.c_int32), ("back_sq", C.c_int32), ("side_sq", C.c_int32), ("clearance_sq", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class GroundSdfRolloutParam(C.Structure):
+    """gie_ground_sdf_rollout_param (include/gie.h): 32 bytes; margin in metres."""
+    _fields_ = [("margin", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+class GroundSdfRollout(C.Structure):
+    """gie_ground_sdf_rollout (include/gie.h): 32 bytes, one per trajectory."""
+    _fields_ = [("points", C.c_int32), ("argmin", C.c_int32), ("min_dist", C.c_float), ("grad", C.c_float * 2), ("first_below", C.c_int32),
+                ("n_below", C.c_int32), ("first_in", C.c_int32)]
+
+
 class GroundFrontierParam(C.Structure):
     """gie_ground_frontier_param (include/gie.h): 32 bytes; clearance_sq in squared cells."""
     _fields_ = [("clearance_sq", C.c_int32), ("min_size", C.c_int32), ("connectivity", C.c_int32), ("max_clusters", C.c_int32),
@@ -202,6 +213,7 @@ class GroundFrontierCluster(C.Structure):
 
 
 assert C.sizeof(GroundFrontierParam) == 32 and C.sizeof(GroundFrontierCluster) == 64 and GroundFrontierCluster.sum.offset == 40
+assert C.sizeof(GroundSdfRolloutParam) == 32 and C.sizeof(GroundSdfRollout) == 32 and GroundSdfRollout.first_below.offset == 20
 assert C.sizeof(GroundPoseNf1Param) == 32 and GroundPoseNf1Param.flags.offset == 16
 assert C.sizeof(GroundFootprintParam) == 32 and C.sizeof(GroundFootprint) == 32 and GroundFootprintParam.flags.offset == 16 and GroundFootprint.hit_cells.offset == 16
 assert C.sizeof(GroundRolloutParam) == 32 and C.sizeof(GroundRollout) == 48 and GroundRollout.cost.offset == 24 and GroundRollout.nf1_end.offset == 32
@@ -422,6 +434,13 @@ DEVICE_ONLY = {
     "ground_pose_nf1_query_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "ground_pose_nf1_path": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ground_pose_nf1_path_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    # ground signed distance: inside distances, bilinear queries, path clearance (include/gie.h): device library only
+    "read_ground_sdf": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
+    "read_ground_sdf_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
+    "ground_query_sdf": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ground_query_sdf_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ground_sdf_rollouts": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.POINTER(GroundSdfRolloutParam), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ground_sdf_rollouts_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.POINTER(GroundSdfRolloutParam), C.c_void_p, C.c_void_p, C.c_void_p]),
     # goal-to-goal cost matrix of the local volume (include/gie.h): device library only
     "costmat_compute": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(Nf1Param), C.c_void_p, C.c_void_p]),
     "costmat_compute_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(Nf1Param), C.c_void_p, C.c_void_p]),

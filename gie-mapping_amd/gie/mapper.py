@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import CLOUD_DIST, CLOUD_TYPE, GROUND_POSE_HEADINGS, GROUND_POSE_MAX_SQ, GROUND_POSE_NF1_FROM_FRONTIERS, GROUND_POSE_NF1_REVERSE, GROUND_POSE_NF1_UNKNOWN_TRAVERSABLE, GROUND_FOOTPRINT_MARGIN, GROUND_FOOTPRINT_MAX_SQ, GROUND_FOOTPRINT_UNKNOWN_TRAVERSABLE, GROUND_LOS_UNKNOWN_TRAVERSABLE, GROUND_NF1_FROM_FRONTIERS, GROUND_NF1_UNKNOWN_TRAVERSABLE, GROUND_ROLLOUT_MAX_POSES, GROUND_ROLLOUT_NF1, GROUND_ROLLOUT_UNKNOWN_TRAVERSABLE, GROUND_UNKNOWN_BLOCKS, GROUND_VIEW_UNION, GROUND_VIEW_UNKNOWN_OPAQUE, LOS_UNKNOWN_OPAQUE, NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE, VOX_FNT, VOX_FREE, VOX_OCCUPIED, VOX_UNKNOWN
-from ._capi import CamParam, CloudParam, Config, CostMapHdr, FrameStats, FrontierParam, GroundFootprintParam, GroundFrontierParam, GroundLosParam, GroundNf1Param, GroundParam, GroundPoseNf1Param, GroundRolloutParam, GroundShortcutParam, GroundViewParam, LosParam, MultiScanParam, Nf1Param, ScanParam, ShortcutParam, ViewParam, Voxel
+from ._capi import CamParam, CloudParam, Config, CostMapHdr, FrameStats, FrontierParam, GroundFootprintParam, GroundFrontierParam, GroundLosParam, GroundNf1Param, GroundParam, GroundPoseNf1Param, GroundRolloutParam, GroundSdfRolloutParam, GroundShortcutParam, GroundViewParam, LosParam, MultiScanParam, Nf1Param, ScanParam, ShortcutParam, ViewParam, Voxel
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG, "csrc", "libgie_hip.so")
@@ -42,6 +42,9 @@ GROUND_WAYPOINT_DTYPE = np.dtype([("xy", "<i4", (2,)), ("index", "<i4"), ("min_d
 # gie_ground_rollout (48 bytes)
 GROUND_ROLLOUT_DTYPE = np.dtype([("end", "<i4"), ("poses", "<i4"), ("hit", "<i4", (2,)), ("cells", "<i4"), ("min_dist_sq", "<i4"), ("cost", "<i8"),
                                  ("nf1_end", "<i4"), ("nf1_min", "<i4"), ("nf1_min_at", "<i4"), ("reserved", "<i4")])
+# gie_ground_sdf_rollout (32 bytes)
+GROUND_SDF_ROLLOUT_DTYPE = np.dtype([("points", "<i4"), ("argmin", "<i4"), ("min_dist", "<f4"), ("grad", "<f4", (2,)), ("first_below", "<i4"), ("n_below", "<i4"),
+                                     ("first_in", "<i4")])
 # gie_ground_footprint (32 bytes)
 GROUND_FOOTPRINT_DTYPE = np.dtype([("end", "<i4"), ("poses", "<i4"), ("hit", "<i4", (2,)), ("hit_cells", "<i4"), ("min_dist_sq", "<i4"), ("min_at", "<i4"), ("reserved", "<i4")])
 # gie_ground_frontier_cluster: 64 bytes, the offsets of the C struct
@@ -1112,6 +1115,62 @@ class Mapper(MapperBase):
         stream."""
         p = self.ground_rollout_param(clearance_sq, inflate_sq, unknown_traversable, nf1)
         self._chk(self._f["ground_rollouts_dev"](self._h, C.c_void_p(d_xy or None), int(n), int(T), C.byref(p), C.c_void_p(d_out or None)))
+
+    # --- ground signed distance: inside distances, bilinear queries, path clearance (include/gie.h) ---
+    def read_ground_sdf(self, sdf=True, inside_dist_sq=True):
+        """{"sdf": float32 (cell units), "inside_dist_sq": int32}, shaped [Y][X] like read_ground (synchronises)."""
+        shape = (self.size[1], self.size[0])
+        s = np.empty(shape, np.float32) if sdf else None
+        d = np.empty(shape, np.int32) if inside_dist_sq else None
+        self._chk(self._f["read_ground_sdf"](self._h, _ptr(s), _ptr(d)))
+        return {k: v for k, v in (("sdf", s), ("inside_dist_sq", d)) if v is not None}
+
+    def read_ground_sdf_dev(self, d_sdf, d_inside_dist_sq):
+        """The same planes into device buffers (raw device addresses, 0 = not wanted), asynchronous on the mapper's stream."""
+        self._chk(self._f["read_ground_sdf_dev"](self._h, C.c_void_p(d_sdf or None), C.c_void_p(d_inside_dist_sq or None)))
+
+    def ground_query_sdf(self, xy, dist=True, grad=True, flags=True):
+        """n points (metres, world frame) -> (dist [n] float32 metres, grad [n, 2] float32, flags [n] uint8), None for an output that
+        is not wanted (synchronises)."""
+        xy = np.ascontiguousarray(xy, dtype=np.float32).reshape(-1, 2)
+        n = xy.shape[0]
+        d = np.empty(n, np.float32) if dist else None
+        g = np.empty((n, 2), np.float32) if grad else None
+        f = np.empty(n, np.uint8) if flags else None
+        self._chk(self._f["ground_query_sdf"](self._h, _ptr(xy) if n else None, n, _ptr(d), _ptr(g), _ptr(f)))
+        return d, g, f
+
+    def ground_query_sdf_dev(self, d_xy, n, d_dist, d_grad, d_flags):
+        """n queries with points (n x 2 float32) and results in DEVICE buffers (raw addresses, 0 = not wanted), on the mapper's stream."""
+        self._chk(self._f["ground_query_sdf_dev"](self._h, C.c_void_p(d_xy or None), int(n), C.c_void_p(d_dist or None), C.c_void_p(d_grad or None),
+                                                  C.c_void_p(d_flags or None)))
+
+    def ground_sdf_rollout_param(self, margin=0.0):
+        """gie_ground_sdf_rollout_param: margin in METRES, compared with the queries' dist."""
+        p = GroundSdfRolloutParam()
+        p.margin = float(margin)
+        return p
+
+    def ground_sdf_rollouts(self, xy, margin=0.0, dist=False, grad=False):
+        """n trajectories of T points (an (n, T, 2) float32 array, metres, world frame; a NaN tail ends a shorter one) over the current
+        ground field -> (GROUND_SDF_ROLLOUT_DTYPE [n], dist [n, T] float32 or None, grad [n, T, 2] float32 or None) (synchronises)."""
+        xy = np.ascontiguousarray(np.asarray(xy, dtype=np.float32))
+        if xy.ndim != 3 or xy.shape[2] != 2:
+            raise ValueError("ground_sdf_rollouts: an (n, T, 2) array")
+        n, T = xy.shape[0], xy.shape[1]
+        out = np.zeros(n, GROUND_SDF_ROLLOUT_DTYPE)
+        d = np.empty((n, T), np.float32) if dist else None
+        g = np.empty((n, T, 2), np.float32) if grad else None
+        p = self.ground_sdf_rollout_param(margin)
+        self._chk(self._f["ground_sdf_rollouts"](self._h, _ptr(xy) if n and T else None, n, T, C.byref(p), _ptr(out) if n else None, _ptr(d), _ptr(g)))
+        return out, d, g
+
+    def ground_sdf_rollouts_dev(self, d_xy, n, T, d_out, d_dist=0, d_grad=0, margin=0.0):
+        """n trajectories with points (n x T x 2 float32), records (n x 32 bytes) and the optional per-point outputs (0 = not wanted) in
+        DEVICE buffers (raw addresses), on the mapper's stream."""
+        p = self.ground_sdf_rollout_param(margin)
+        self._chk(self._f["ground_sdf_rollouts_dev"](self._h, C.c_void_p(d_xy or None), int(n), int(T), C.byref(p), C.c_void_p(d_out or None),
+                                                     C.c_void_p(d_dist or None), C.c_void_p(d_grad or None)))
 
     # --- ground footprints: oriented-rectangle pose checks on the ground costmap (include/gie.h) ---
     def ground_footprint_param(self, front_sq, back_sq, side_sq, clearance_sq=0, unknown_traversable=False, margin=False):

@@ -614,6 +614,19 @@ public:
     }
     int32_t ground_counts[4] = { 0, 0, 0, 0 };   /* columns of the last ground_costmap(): UNKNOWN, FREE, OCCUPIED, FNT */
 
+    /* What an optimising planner takes from that CostMap (include/gie.h "ground signed distance"): at n points xy (metres, world
+     * frame, two floats each) the bilinear signed distance (metres; negative inside an obstacle, NaN outside the field) and its
+     * gradient (m/m, two per point), on the ground field ground_costmap() left.  Returns false, and leaves both arguments alone,
+     * while the band is not set. */
+    bool ground_distance(const float *xy, int n, std::vector<float> &dist, std::vector<float> &grad)
+    {
+        if (param.ground_max_height < param.ground_min_height) return false;
+        dist.resize((size_t)std::max(n, 0));
+        grad.resize((size_t)std::max(n, 0) * 2);
+        if (n > 0) chk(gie_ground_query_sdf(m_, xy, n, dist.data(), grad.data(), nullptr));
+        return true;
+    }
+
     /* gie_ground_nf1_param.clearance_sq of ground_robot_radius: cells = ceil(radius / voxel_width), squared */
     int ground_clearance_sq() const { const int cells = (int)ceilf(param.ground_robot_radius / cfg_.voxel_width); return cells * cells; }
     /* A ground robot's plan on the map as it stands (include/gie.h "ground navigation function"): the ground field of the band as

@@ -1279,6 +1279,86 @@ int gie_ground_pose_nf1_query_dev(gie_mapper *h, const float *d_xy, const int32_
 int gie_ground_pose_nf1_path(gie_mapper *h, const float *start_xy, const int32_t *start_k, int n, int max_len, int32_t *path_xyk, int32_t *len);
 int gie_ground_pose_nf1_path_dev(gie_mapper *h, const float *d_start_xy, const int32_t *d_start_k, int n, int max_len, int32_t *d_path_xyk, int32_t *d_len);
 
+/* ---- ground signed distance: the ground costmap continued into the obstacles, a distance and a gradient at continuous points and
+ * the clearance of whole trajectories — what the optimising planners (TEB, CHOMP, MPC, elastic bands) take where the search planner
+ * takes "ground navigation function" and the sampling one "ground rollouts".  gie_ground_query returns the integer dist_sq of the
+ * one cell a point falls into: a step function without a slope, and 0 on every obstacle column, so a pose inside an obstacle (a
+ * wall moved onto the robot by a map update; any unknown region with GIE_GROUND_UNKNOWN_BLOCKS) is not pushed out.  This is
+ * "signed distance field" in the plane, on the ground field; that section's own field is of no use to a ground robot (the floor is
+ * one voxel away everywhere).  No counterpart in the reference's code.
+ *
+ * Everything refers to the ground field that is valid where the call is enqueued (the rule of "ground line of sight"): its pivot,
+ * its rectangle X x Y, its obstacle columns — OCCUPIED, and UNKNOWN too when the field was computed with GIE_GROUND_UNKNOWN_BLOCKS.
+ *  inside_dist_sq(x, y)  0 on a column that is not an obstacle column; on an obstacle column the exact squared Euclidean distance,
+ *                     in cells and as an integer, to the nearest non-obstacle column OF THE RECTANGLE; -1 when the rectangle holds
+ *                     no non-obstacle column.
+ *  gsdf(x, y)         cell units, like gie_seendist.d:
+ *                       inside_dist_sq <= 1:  the `d` gie_read_costmap_ground writes for the cell, bit for bit:
+ *                                             sqrtf((float)dist_sq), or (float)max_loc_dist_sq on a field without an obstacle column;
+ *                       inside_dist_sq >  1:  1.0f - sqrtf((float)inside_dist_sq);
+ *                       inside_dist_sq == -1: -(float)max_loc_dist_sq.
+ *                     "signed distance field"'s convention: the surface layer of an obstacle stays at 0, deeper columns go
+ *                     negative.  The field differs from the ground costmap ONLY on obstacle columns all four of whose edge
+ *                     neighbours inside the rectangle are obstacle columns.
+ * Query at a point p (metres, world frame), "signed distance field"'s with the z axis removed, on the FIELD's pivot.  The order of
+ * the float32 operations is part of the contract (the library is compiled without contraction into fused multiply-adds):
+ *  u_k = p_k / w - (float)pvt_k    continuous local coordinate (cell centres at integers);
+ *  axis with size_k >= 2:          inside iff 0 <= u_k <= size_k - 1; i0 = min((int)floorf(u_k), size_k - 2), t_k = u_k - (float)i0;
+ *  axis with size_k == 1:          inside iff -0.5 <= u_k < 0.5; i0 = i1 = 0, t_k = 0; its gradient component is exactly 0;
+ *  corners                         v0 = gsdf(i0x, i0y), v1 = gsdf(i1x, i0y), v2 = gsdf(i0x, i1y), v3 = gsdf(i1x, i1y);
+ *  weights                         sx = 1 - tx, sy = 1 - ty;  c0 = v0 * sx + v1 * tx, c1 = v2 * sx + v3 * tx;
+ *  dist    (c0 * sy + c1 * ty) * w: metres;
+ *  grad    grad_x = (v1 - v0) * sy + (v3 - v2) * ty, grad_y = c1 - c0 (n x 2, x y per point): m/m;
+ *  flags   bit 0 inside the rectangle, bit 1 all corners known (type != UNKNOWN), bit 2 some corner an obstacle column;
+ *  outside the rectangle, NaN, +-inf: dist = NaN, grad = 0, 0, flags = 0.
+ * Rollouts: n trajectories of T points, laid out as "ground rollouts" lays out its poses (point k of trajectory i at
+ *  xy[2 * (i * T + k)]), 1 <= T <= GIE_GROUND_ROLLOUT_MAX_POSES; a NaN tail passes shorter trajectories.  One record per trajectory,
+ *  every field a pure function of the per-point query results: minima, first indices and counts, no sum of floats — no result
+ *  depends on a schedule.  The optional per-point outputs dist (n * T) and grad (2 * n * T) hold exactly what gie_ground_query_sdf
+ *  writes for every point, in the prefix or behind it.
+ * Cache: inside_dist_sq belongs to ONE ground field: it is computed on the device at the first call of this section after a
+ *  gie_ground_compute* and kept until the next one; a map update changes nothing, as it changes nothing of the ground field.  The
+ *  device counts the interior obstacle columns (those whose four edge neighbours are obstacle columns, outside the rectangle
+ *  counting as one) from the bit rows; with none the exact transform returns at once and 0 / 1 is read off the bit rows.  No call
+ *  waits on the host for that.
+ * Memory: 4 bytes per cell and one int32, allocated at the first call of the section, freed by gie_destroy.  A mapper that never
+ *  calls the section allocates and launches nothing.  The section writes nothing of the map, of the ground field or of any other
+ *  stage's field.
+ * Arguments: sdf / inside_dist_sq are X * Y values each (x fastest), either may be NULL, not both; dist (n), grad (2n) and flags (n)
+ *  may each be NULL, not all three; the rollouts' dist and grad may each be NULL; n == 0 is valid and launches nothing.
+ * GIE_ERR_INVALID, nothing written: a NULL handle; a tiled mapper; no ground field yet; all outputs NULL; n < 0; n > 0 with a NULL
+ *  xy; for the rollouts a NULL param, n > 0 with a NULL record buffer, a margin that is negative or not finite, non-zero flags or
+ *  reserved, T outside 1 .. GIE_GROUND_ROLLOUT_MAX_POSES and, in the host form, n * T * 8 bytes beyond size_t.
+ * The host forms stage through the two scratch slots of the host forms and synchronise.  The _dev forms take DEVICE buffers and are
+ *  enqueued on the mapper's stream (gie_get_stream) with no host wait, no read-back and no grid barrier.
+ * Cost: the inside pass is a memset of the count and two launches (the count; one wave per x for the transform, as the ground
+ *  field's own); a read, a query and a rollout call are one launch each behind it: a lane per cell or point, a wave per trajectory
+ *  with a lane per point in chunks of 64.
+ * gie_profile_read: the section adds no name: the inside pass and gie_read_ground_sdf* are counted under "ground", the queries and
+ *  the rollouts under "ground_query" (a call that runs the inside pass first adds one entry to each). */
+typedef struct gie_ground_sdf_rollout_param {   /* 32 bytes */
+    float   margin;         /* metres, finite, >= 0: a point is BELOW with dist < margin */
+    int32_t flags;          /* must be 0 */
+    int32_t reserved[6];    /* must be 0 */
+} gie_ground_sdf_rollout_param;
+typedef struct gie_ground_sdf_rollout {         /* 32 bytes */
+    int32_t points;         /* m: the leading points whose query has flag bit 0; the first point without it ends the prefix */
+    int32_t argmin;         /* the FIRST k < m with the least dist; -1 when m == 0 */
+    float   min_dist;       /* that dist, metres; NaN when m == 0 */
+    float   grad[2];        /* the query's gradient at argmin; 0, 0 when m == 0 */
+    int32_t first_below;    /* the first k < m with dist < margin; -1 */
+    int32_t n_below;        /* how many k < m have dist < margin */
+    int32_t first_in;       /* the first k < m with dist <= 0 (on or inside an obstacle); -1 */
+} gie_ground_sdf_rollout;
+int gie_read_ground_sdf(gie_mapper *h, float *sdf, int32_t *inside_dist_sq);
+int gie_read_ground_sdf_dev(gie_mapper *h, float *d_sdf, int32_t *d_inside_dist_sq);
+int gie_ground_query_sdf(gie_mapper *h, const float *xy, int n, float *dist, float *grad, uint8_t *flags);
+int gie_ground_query_sdf_dev(gie_mapper *h, const float *d_xy, int n, float *d_dist, float *d_grad, uint8_t *d_flags);
+int gie_ground_sdf_rollouts(gie_mapper *h, const float *xy, int n, int T, const gie_ground_sdf_rollout_param *p, gie_ground_sdf_rollout *out,
+                            float *dist, float *grad);
+int gie_ground_sdf_rollouts_dev(gie_mapper *h, const float *d_xy, int n, int T, const gie_ground_sdf_rollout_param *p, gie_ground_sdf_rollout *d_out,
+                                float *d_dist, float *d_grad);
+
 /* ---- goal-to-goal cost matrix: the path lengths among up to 64 points (the robot and the goals of the frontier clusters, say), the
  * input of every tour-based explorer — in which order to visit the clusters.  n fields of gie_nf1_compute would give the same
  * numbers with n persistent launches and n whole fields; here ONE level-synchronous pass advances all searches, a 64-bit mask per
