@@ -38,6 +38,12 @@ struct be_state {
     int pool_used;
     int cur_id;                         /* bracket the launches currently belong to (-1: none) */
     double acc_ms[32]; int acc_n[32];
+    /* the batch EDT's hint (GIE_EDT_HINT_*, gie_types.h): pinned, host-mapped words the streaming kernel of pass Z stores and be_edt
+     * reads with a plain load before the next update's launches */
+    volatile uint32_t *edt_hint;        /* the host's address (null: no such memory — no guess, every launch as before) */
+    uint32_t *edt_hint_dev;             /* the device's */
+    int edt_guess;                      /* what the last update was launched for: GIE_EDT_HINT_* */
+    int edt_force;                      /* test hook: the next update's guess (GIE_EDT_HINT_*), -1: the word's */
 };
 
 struct be_arena { char *base; size_t size, top; int k; std::vector<long long> skew; };
@@ -84,6 +90,14 @@ static int be_init(be_state *b, int device, int wave_workgroups)
     for (int i = 0; i < GIE_NEV; i++) { GIE_HIP_OK(hipEventCreate(&b->ev[i])); b->ev_set[i] = 0; }
     b->scan_tmp = nullptr; b->scan_bytes = 0; b->arena = nullptr; b->side_on = 0; b->side_busy = 0;
     for (int i = 0; i < 2; i++) GIE_HIP_OK(hipEventCreateWithFlags(&b->copy_ev[i], hipEventDisableTiming));
+    {   /* (coherent host memory: the word is visible to the host once the kernel that stored it has ended) */
+        void *h = nullptr, *d = nullptr;
+        b->edt_hint = nullptr; b->edt_hint_dev = nullptr;
+        if (hipHostMalloc(&h, 64, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&d, h, 0) == hipSuccess) {
+            memset(h, 0, 64); b->edt_hint = (volatile uint32_t *)h; b->edt_hint_dev = (uint32_t *)d;
+        } else { if (h) (void)hipHostFree(h); (void)hipGetLastError(); }
+        b->edt_guess = GIE_EDT_HINT_NONE; b->edt_force = -1;
+    }
     b->prof_on = 0; b->cur_id = -1; b->pool = new std::vector<hipEvent_t>(); b->pending = new std::vector<int>(); b->pool_used = 0;
     for (int i = 0; i < 32; i++) { b->acc_ms[i] = 0; b->acc_n[i] = 0; }
     {   /* a second mapper on this device: whatever the first one has in flight was launched unchained — let it finish once */
@@ -100,7 +114,9 @@ static void be_fini(be_state *b)
     delete b->pool; delete b->pending;
     for (int i = 0; i < GIE_NEV; i++) (void)hipEventDestroy(b->ev[i]);
     for (int i = 0; i < 2; i++) (void)hipEventDestroy(b->copy_ev[i]);
+    (void)hipStreamSynchronize(b->stream);              /* (a streaming kernel still in flight stores the hint word) */
     (void)hipStreamDestroy(b->stream);
+    if (b->edt_hint) { (void)hipHostFree((void *)b->edt_hint); b->edt_hint = nullptr; b->edt_hint_dev = nullptr; }
     if (b->side_on) { (void)hipStreamSynchronize(b->side); (void)hipEventDestroy(b->side_ready); (void)hipEventDestroy(b->side_done); (void)hipStreamDestroy(b->side); }
     if (b->arena) { be_arena *a = (be_arena *)b->arena; if (a->base) (void)hipFree(a->base); delete a; b->arena = nullptr; }
 }
@@ -379,14 +395,14 @@ static int be_zs_mode(const gie_ctx &c)
 }
 /* pass Z: the streaming form (if it takes the volume), pass X on the rows of the slabs it gave up (fused form: pass X did not
  * run), the column kernel (the rest, or the repair of those slabs) */
-static int be_edt_z_stream(be_state *b, const gie_ctx &c, int full);
+static int be_edt_z_stream(be_state *b, const gie_ctx &c, int full, int zs, int guess = GIE_EDT_HINT_NONE, int note = 0);
 static void be_edt_z_rest(be_state *b, const gie_ctx &c, int full, int zs)
 {
     if (zs == 2) gie_launch_edt_dim(b, c, c.X, false, full, 0, true);
     gie_launch_edt_dim(b, c, c.Z, true, full);
 }
 /* pass Z again over the whole volume (pass Y is complete, pass X where the streaming form does not take the volume) */
-static void be_edt_z(be_state *b, const gie_ctx &c, int full) { be_edt_z_rest(b, c, full, be_edt_z_stream(b, c, full) ? be_zs_mode(c) : 0); }
+static void be_edt_z(be_state *b, const gie_ctx &c, int full) { const int zs = be_zs_mode(c); be_edt_z_rest(b, c, full, be_edt_z_stream(b, c, full, zs) ? zs : 0); }
 /* EDT_OCC::batchEDTUpdate, local_edt.cu:7-28 */
 /* adaptive sweep (k_voxa): the kernel walks the list or sweeps the volume, whichever the list's
  * length calls for; staged = the functor's load1/load2/finish form; always_list = never sweep */
@@ -465,11 +481,12 @@ static void be_edt_z_direct(be_state *b, const gie_ctx &c)
 }
 /* the streaming form of pass Z (k_edt_z_stream): a wave per (64 columns, y, z segment) */
 #define GIE_ZSTREAM_WAVES 8
-/* returns 1 when launched: the launch also carries the list form of the pass (k_edt_z_direct's body) when `full` is 0 */
-static int be_edt_z_stream(be_state *b, const gie_ctx &c, int full)
+/* returns 1 when launched: the launch also carries the list form of the pass (k_edt_z_direct's body) when `full` is 0.
+ * zs: be_zs_mode, or 1 in its place (be_edt); guess: what the update was launched for (GIE_EDT_HINT_*); note: the kernel stores the hint */
+static int be_edt_z_stream(be_state *b, const gie_ctx &c, int full, int zs, int guess, int note)
 {
-    const int zs = be_zs_mode(c);
     if (!zs) return 0;
+    uint32_t *const hint = note ? b->edt_hint_dev : nullptr;
     const int nxr = (c.X + 63) / 64;
     /* z segments so that the launch has about eight waves per SIMD (GIE_ZSTREAM_WAVES) to overlap its rows' round trips (a segment re-reads 16 planes) */
     const long long want = (long long)b->cu_total * 4 * GIE_ZSTREAM_WAVES;
@@ -483,8 +500,8 @@ static int be_edt_z_stream(be_state *b, const gie_ctx &c, int full)
     const long long cap = (long long)b->cu_total * 8 * 4;
     if (grid > cap) grid = cap;
     if (!full && grid < (long long)b->cu_total * 16) grid = (long long)b->cu_total * 16;      /* (the list form's grid: be_edt_z_direct) */
-    if (zs == 2) GIE_LAUNCH(b, k_edt_z_stream<true>, dim3((unsigned)grid), dim3(256), 0, c, full, nseg, seg_len, zs);
-    else GIE_LAUNCH(b, k_edt_z_stream<false>, dim3((unsigned)grid), dim3(256), 0, c, full, nseg, seg_len, zs);
+    if (zs == 2) GIE_LAUNCH(b, k_edt_z_stream<true>, dim3((unsigned)grid), dim3(256), 0, c, full, nseg, seg_len, zs, guess, hint);
+    else GIE_LAUNCH(b, k_edt_z_stream<false>, dim3((unsigned)grid), dim3(256), 0, c, full, nseg, seg_len, zs, guess, hint);
     return 1;
 }
 /* tskip for this update; with c.catchup_fast the tiles whose deferred records have to be stored are listed and stored (pupvt: the
@@ -520,6 +537,28 @@ static void be_edt_prep(be_state *b, const gie_ctx &c)
     const int ncol = c.tfd[0] * c.tfd[1];
     GIE_LAUNCH(b, k_edt_prep, dim3((ncol + GIE_PREP_WAVES - 1) / GIE_PREP_WAVES), dim3(64 * GIE_PREP_WAVES), 0, c, ncol);
 }
+/* The guess for the update about to be launched: a plain load of the hint word — no copy, no event, no wait.  The word is the last
+ * update's only if the host has waited for that update since; otherwise it is an older one's or 0, and the guess is that much
+ * worse.  GIE_EDT_HINT=0 (test build): no guess, the launches of before. */
+static int be_edt_hint_take(be_state *b)
+{
+    static const int on = GIE_SWITCH("GIE_EDT_HINT", 1);
+    if (!b->edt_hint) return GIE_EDT_HINT_NONE;
+    const int out = (int)(b->edt_hint[0] & 3u);
+    int guess = (on && (out == GIE_EDT_HINT_LEFT || out == GIE_EDT_HINT_TOOK)) ? out : GIE_EDT_HINT_NONE;
+    if (b->edt_force >= 0) { guess = b->edt_force; b->edt_force = -1; }
+    b->edt_guess = guess;
+    return guess;
+}
+#if defined(GIE_TEST_HOOKS)
+/* gie_debug_edt_hint: the next update's guess (GIE_EDT_HINT_*; anything else: the word's again); info[4], if asked for: the word, the
+ * two counts of wrong guesses, what the last update was launched for — current once the caller has waited for the stream */
+static void be_edt_hint_debug(be_state *b, int force, int32_t *info)
+{
+    b->edt_force = (force >= GIE_EDT_HINT_NONE && force <= GIE_EDT_HINT_TOOK) ? force : -1;
+    if (info) { for (int i = 0; i < 3; i++) info[i] = b->edt_hint ? (int32_t)b->edt_hint[i] : 0; info[3] = b->edt_guess; }
+}
+#endif
 /* full = 1: whole volume (column kernel); 0: only where Mark reads — the direct kernel over tl_known
  * and the column kernel are both launched and the one the known-tile count does not call for
  * returns at once */
@@ -543,12 +582,24 @@ static void be_edt(be_state *b, const gie_ctx &c, int full)
     else if (c.Y <= 512) GIE_LAUNCH(b, (k_edt_y<16, 16>), gy, dim3(GIE_EDTY_COLS, 16), 0, c);
     else GIE_LAUNCH(b, (k_edt_y<32, 16>), gy, dim3(GIE_EDTY_COLS, 16), 0, c);
     be_prof(b, GIE_K_EDT_Y, 1);
-    const int zs = be_zs_mode(c);
-    be_prof(b, GIE_K_EDT_X, 0); gie_launch_edt_dim(b, c, c.X, false, full, zs == 2 ? zs : 0); be_prof(b, GIE_K_EDT_X, 1);
+    /* Where the fused streaming form may take the volume (be_zs_mode 2) the device decides whether it does (gie_zs_takes), and a
+     * launch made for the other outcome costs its full time on the stream: pass X's 64 K workgroups that leave at once, or an
+     * empty k_edt_x_redo.  The outcome barely moves from one update to the next, so the launches are made for the last one's:
+     *   TOOK: no pass X.  Should the form not take this volume after all, its kernel says so (GIE_CNT_XMISS) and the launches
+     *         behind it do all of pass X and pass Z;
+     *   LEFT: be_zs_mode 1 — pass X in full, the streaming form from pass X's planes (which still takes the volume if this
+     *         update's planes call for it), no k_edt_x_redo;
+     *   NONE: both, as before.
+     * Exact whatever the guess: a wrong one costs time on that update only. */
+    int zs = be_zs_mode(c);
+    const int guess = zs == 2 ? be_edt_hint_take(b) : GIE_EDT_HINT_NONE;
+    if (guess == GIE_EDT_HINT_LEFT) zs = 1;
+    /* (no launch, no bracket: the profile lists a stage by the brackets it has counted) */
+    if (guess != GIE_EDT_HINT_TOOK) { be_prof(b, GIE_K_EDT_X, 0); gie_launch_edt_dim(b, c, c.X, false, full, zs == 2 ? zs : 0); be_prof(b, GIE_K_EDT_X, 1); }
     be_prof(b, GIE_K_EDT_Z, 0);
     /* dense fields: the streaming form does the whole pass and flags what it could not finish for the column kernel; few known
      * tiles: the list form — in the same launch */
-    const int zl = be_edt_z_stream(b, c, full);
+    const int zl = be_edt_z_stream(b, c, full, zs, guess, 1);
     if (!zl && !full) be_edt_z_direct(b, c);
     be_edt_z_rest(b, c, full, zl ? zs : 0);
     be_prof(b, GIE_K_EDT_Z, 1);
@@ -589,6 +640,21 @@ static void be_waves(be_state *b, const gie_ctx &c, int with_ab, int record_seed
 }
 
 #include "gie_api.inc.h"
+#if defined(GIE_TEST_HOOKS)
+/* test hook (not in gie.h; this backend's alone — the sequential one under tests/emu has no launches to guess for): the guess the
+ * NEXT gie_batch_edt launches its passes for — 0 none (pass X and k_edt_x_redo both), 1 "the streaming form did not take the last
+ * volume", 2 "the fused form took it" (GIE_EDT_HINT_*, be_edt); anything else: the device's word again, as the updates after the
+ * next one do anyway.  A race makes the real hint harmless and untestable; this makes every guess meet every kind of update.
+ * info (null, or 4 words): the hint word of the last update that has ended (bits 0-1 its outcome, the rest its planes with
+ * obstacles), the updates launched for 1 / for 2 that had the other outcome, the last guess. */
+extern "C" int gie_debug_edt_hint(gie_mapper *m, int force, int32_t *info)
+{
+    if (!m) { gie_set_err("gie_debug_edt_hint: null handle"); return GIE_ERR_INVALID; }
+    if (be_sync(&m->be) != 0) return GIE_ERR_DEVICE;
+    be_edt_hint_debug(&m->be, force, info);
+    return GIE_OK;
+}
+#endif
 #include "gie_sdf.inc.h"
 #include "gie_nf1.inc.h"
 #include "gie_costmat.inc.h"

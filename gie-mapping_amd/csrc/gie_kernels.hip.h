@@ -1007,7 +1007,8 @@ __device__ __forceinline__ void gie_edt_x_row(const gie_ctx &c, const int y, con
 }
 /* zs: pass Z's fused streaming form may take the volume (be_zs_mode) — when it does (it reads pass Y's planes itself) this pass
  * has nothing to do, and every workgroup leaves after the test (0.017 ms for the headline's 64 K workgroups: workgroups of 16 waves
- * were measured no cheaper, and a grid-stride walk over the rows needs 123 VGPRs at CP = 8 against 44, so the grid stays this one) */
+ * were measured no cheaper, and a grid-stride walk over the rows needs 123 VGPRs at CP = 8 against 44, so the grid stays this one —
+ * and the host does not launch it where the form took the last update's volume: be_edt) */
 template <int CP>
 __global__ __launch_bounds__(64 * GIE_EDTX_WAVES) void k_edt_x(const gie_ctx c, const int zs, const int full)
 {
@@ -1019,11 +1020,13 @@ __global__ __launch_bounds__(64 * GIE_EDTX_WAVES) void k_edt_x(const gie_ctx c, 
 }
 /* After the fused streaming form: pass X on the rows (y, every plane with obstacles) of the y values whose slabs it gave up
  * (c.zredo) — the column kernel behind it reads them.  A grid-stride walk over (y, 8 planes with obstacles): nothing to do on
- * most updates. */
+ * most updates.  GIE_CNT_XMISS (pass X was not launched on the host's hint and the form did not take the volume): every row — the
+ * same rows of the same planes k_edt_x does, through the same gie_edt_x_row. */
 template <int CP>
 __global__ __launch_bounds__(64 * GIE_EDTX_WAVES) void k_edt_x_redo(const gie_ctx c)
 {
-    if (c.cnt[GIE_CNT_ZFAIL] == 0) return;
+    const int all = c.cnt[GIE_CNT_XMISS];
+    if (!all && c.cnt[GIE_CNT_ZFAIL] == 0) return;
     const int K = *c.zcount, Y = c.Y, lane = threadIdx.x & 63;
     const int nw = (int)gridDim.x * GIE_EDTX_WAVES, w0 = (int)blockIdx.x * GIE_EDTX_WAVES + (int)(threadIdx.x >> 6);
     const int ntx = (c.X + 15) >> 4, nkc = (K + 7) >> 3;
@@ -1031,8 +1034,8 @@ __global__ __launch_bounds__(64 * GIE_EDTX_WAVES) void k_edt_x_redo(const gie_ct
     for (int u = w0; u < Y * nkc; u += nw) {
         const int uu = __builtin_amdgcn_readfirstlane(u);   /* (wave-uniform said outright: the row's addresses stay scalar) */
         const int y = uu / nkc, k0 = (uu % nkc) * 8;
-        bool f = false;
-        for (int i = lane; i < ntx; i += 64) f |= c.zredo[(size_t)y * ntx + i] != 0u;
+        bool f = all != 0;
+        if (!all) for (int i = lane; i < ntx; i += 64) f |= c.zredo[(size_t)y * ntx + i] != 0u;
         if (!__any(f)) continue;                            /* wave-uniform */
 #pragma unroll 1
         for (int k = k0; k < min(k0 + 8, K); k++) {
@@ -1056,7 +1059,10 @@ template <int CP, int TX, int WAVES>
 __global__ __launch_bounds__(64 * WAVES, (CP <= 8 ? 4 : 2)) void k_edt_z(const gie_ctx c, const int ntiles_x, const int ntiles, const int full)
 {
     static_assert(TX == 16 && WAVES == 8, "a workgroup tile spans two 8-voxel tile columns, one column per wave and half");
-    if (full == 0 && gie_z_use_lists(c, c.cnt[GIE_CNT_TL_KNOWN])) return;   /* few known tiles: k_edt_z_direct (launched next to this one) does the pass */
+    /* few known tiles: k_edt_z_direct (launched next to this one) does the pass — unless pass X had not run when it was its turn
+     * (GIE_CNT_XMISS: the streaming kernel left the list form alone, k_edt_x_redo has done the rows since, and this kernel takes the
+     * tiles with a reader) */
+    if (full == 0 && gie_z_use_lists(c, c.cnt[GIE_CNT_TL_KNOWN]) && !c.cnt[GIE_CNT_XMISS]) return;
     const int repair = c.cnt[GIE_CNT_ZSTREAM];            /* the streaming form (k_edt_z_stream, launched before this one) has done the volume: only the tiles it flagged */
     if (repair && c.cnt[GIE_CNT_ZFAIL] == 0) return;      /* ... and it finished every column (a walk over the flags of 16 K tiles was 40 us of nothing) */
     constexpr int LP = 64 * CP;
@@ -1482,14 +1488,30 @@ __device__ __forceinline__ bool gie_zs_wide_trip_fused(const __amdgpu_buffer_rsr
         __builtin_amdgcn_raw_buffer_store_b32(bc[t], rs_out, (zc + t < z1) ? voff : GIE_BUF_OOB, (unsigned)min(zc + t, Z - 1) * pstride, 0);
     return true;
 }
+/* guess: what be_edt launched this update for (GIE_EDT_HINT_*: TOOK — pass X was not launched; LEFT — zs is 1 where be_zs_mode is 2).
+ * hint: where to note for the host whether the form takes this volume, and a wrong guess (gie_types.h; null: a launch that is not
+ * a map update's first) */
 template <bool FUSED>
-__global__ __launch_bounds__(256, FUSED ? GIE_ZS_FUSED_WGS : 6) void k_edt_z_stream(const gie_ctx c, const int full, const int nseg, const int seg_len, const int zs)
+__global__ __launch_bounds__(256, FUSED ? GIE_ZS_FUSED_WGS : 6) void k_edt_z_stream(const gie_ctx c, const int full, const int nseg, const int seg_len, const int zs,
+                                                                                    const int guess, uint32_t *hint)
 {
     __shared__ uint8_t s_occ[1024 + 2 * (32 + 2 * GIE_ZS_R)];        /* plane holds obstacles, for planes -W .. Z + W (0 outside the volume) */
     const int Z = c.Z, X = c.X, Y = c.Y;
+    const int takes = gie_zs_takes(c, zs, full);          /* (the same answer in every workgroup) */
+    if (hint && blockIdx.x == 0 && threadIdx.x == 0) {
+        hint[0] = GIE_EDT_HINT_WORD(*c.zcount, takes);
+        if (guess != GIE_EDT_HINT_NONE && guess != (takes ? GIE_EDT_HINT_TOOK : GIE_EDT_HINT_LEFT)) hint[guess] += 1u;      /* (one stream: the kernels that do this run one after the other) */
+    }
+    if (FUSED && guess == GIE_EDT_HINT_TOOK && !takes) {
+        /* the hint was wrong: there are no pass-X planes to read, neither for the list form nor for the column kernel.  The launches
+         * behind this one do the whole volume — k_edt_x_redo every row, the column kernel every tile — and the state they leave is
+         * the one an update leaves whose pass X ran first: GIE_CNT_ZSTREAM stays 0, so nobody goes by zredo or tbmax */
+        if (blockIdx.x == 0 && threadIdx.x == 0) c.cnt[GIE_CNT_XMISS] = 1;
+        return;
+    }
     if (full == 0 && gie_z_use_lists(c, c.cnt[GIE_CNT_TL_KNOWN])) { gie_edt_z_direct_body(c); return; }   /* few known tiles: the list form, in this launch (one launch less
                                                                                                          * per update than with a kernel of its own: 4.5 us each on the sparse workloads) */
-    if (!gie_zs_takes(c, zs, full)) return;               /* planes with obstacles are few: the column kernel's envelope forms (same answer in every workgroup) */
+    if (!takes) return;                                   /* planes with obstacles are few: the column kernel's envelope forms */
     __shared__ __attribute__((aligned(16))) uint32_t s_row[FUSED ? 4 : 1][FUSED ? GIE_ZS_ROWS : 1][GIE_ZS_XW];    /* fused: the wave's rows of pass Y's planes */
     if (blockIdx.x == 0 && threadIdx.x == 0) c.cnt[GIE_CNT_ZSTREAM] = 1;
     for (int i = threadIdx.x; i < Z + 2 * GIE_ZS_W; i += 256) { const int z = i - GIE_ZS_W; s_occ[i] = (z >= 0 && z < Z) ? c.zocc[z] : (uint8_t)0; }

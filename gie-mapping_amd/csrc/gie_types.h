@@ -202,7 +202,8 @@ enum {
     GIE_CNT_A = 0, GIE_CNT_B, GIE_CNT_C,        /* seed counts from obtainFrontiers */
     GIE_CNT_TL_SWEPT,                           /* entries in tl_swept */
     GIE_CNT_ZWIDE,                              /* pass Z, streaming form: trips redone with the wide window (a statistic: GIE_DEBUG_COUNTS) */
-    GIE_CNT_FREE5,                              /* (unused since the waves run in block / tile rounds) */
+    GIE_CNT_XMISS,                              /* batch EDT: pass X was not launched (the host's hint: the fused streaming form took the last volume) and the
+                                                 * form did not take this one — k_edt_x_redo does every row, the column kernel every tile (be_edt) */
     GIE_CNT_LV0, GIE_CNT_LV1, GIE_CNT_LV2,      /* wave C: entries expanded in a level (rotating) */
     GIE_CNT_ERR,                                /* sticky error flags */
     GIE_CNT_NEWBLK,                             /* blocks allocated this frame */
@@ -228,6 +229,15 @@ enum {
     GIE_CNT_LAZY_EXACT = 44,                    /* the last fused sweep took its lazy tiles' bounds from pass Z (exact), not from samples (gie_tile_oldskip's hysteresis); kept across updates */
     GIE_CNT_NUM = 48
 };
+/* The batch EDT's hint: words of pinned host memory per mapper that pass Z's streaming kernel stores for the host to read — without
+ * waiting — before it launches the next update's passes (be_edt): did the streaming form take the volume (gie_zs_takes)?
+ * A stale or missing word is a worse guess, never an error: the device decides again on every update.
+ *     word 0: bits 0-1 the outcome (0: no update yet), bits 2-31 planes with obstacles
+ *     words 1, 2: updates launched for LEFT / for TOOK that had the other outcome (since gie_create) */
+#define GIE_EDT_HINT_NONE 0
+#define GIE_EDT_HINT_LEFT 1                     /* the form did not take the volume: pass X in full, the streaming form from pass X's planes, no k_edt_x_redo */
+#define GIE_EDT_HINT_TOOK 2                     /* the fused form took it: pass X is not launched */
+#define GIE_EDT_HINT_WORD(planes, took) (((uint32_t)(planes) << 2) | ((took) ? 2u : 1u))
 /* ids of the per-kernel profile (be_prof brackets; gie_kernel_names, gie_profile_read) */
 enum { GIE_K_CLASSIFY = 0, GIE_K_RAY_REGISTER, GIE_K_RAY_FREE, GIE_K_RAY_FINAL, GIE_K_ALLOC, GIE_K_FUSE, GIE_K_EDT_Y, GIE_K_EDT_X,
        GIE_K_EDT_Z, GIE_K_MARK, GIE_K_FRONTIER, GIE_K_WAVE_A, GIE_K_WAVE_B, GIE_K_WAVE_C, GIE_K_COMMIT, GIE_K_EDT_ZFACES, GIE_K_MARKC,
