@@ -248,11 +248,19 @@ static int be_prof_event(be_state *b)
 /* GIE_TRACE_LAUNCHES=1: every kernel launch is announced on stderr (process id, kernel) and waited for — the last line a
  * process prints before a device fault names the kernel */
 static int be_trace_on() { static const int on = GIE_SWITCH("GIE_TRACE_LAUNCHES", 0); return on; }
-#define GIE_LAUNCH(b, kern, grid, block, lds, ...) do { \
-        if (be_trace_on()) { fprintf(stderr, "[%d] launch %s\n", (int)getpid(), #kern); fflush(stderr); } \
+#define GIE_LAUNCH(b, kern, grid, block, lds, ...) GIE_LAUNCH_AS(b, #kern, kern, grid, block, lds, __VA_ARGS__)
+/* ... under the name given: the templated launchers name the instantiation (k_edt_x<8>), not the parameter (k_edt_x<CP>) */
+#define GIE_LAUNCH_AS(b, name, kern, grid, block, lds, ...) do { \
+        if (be_trace_on()) { fprintf(stderr, "[%d] launch %s\n", (int)getpid(), name); fflush(stderr); } \
         GIE_LAUNCH_(b, kern, grid, block, lds, __VA_ARGS__); \
-        if (be_trace_on()) { hipError_t e_ = hipStreamSynchronize((b)->stream); if (e_ != hipSuccess) { fprintf(stderr, "[%d] %s: %s\n", (int)getpid(), #kern, hipGetErrorString(e_)); fflush(stderr); } } \
+        if (be_trace_on()) { hipError_t e_ = hipStreamSynchronize((b)->stream); if (e_ != hipSuccess) { fprintf(stderr, "[%d] %s: %s\n", (int)getpid(), name, hipGetErrorString(e_)); fflush(stderr); } } \
     } while (0)
+/* the name of an instantiation, written only when the trace is on (a constant 0 in the product library) */
+struct be_kname {
+    char s[40];
+    be_kname(const char *kern, int a) { s[0] = 0; if (be_trace_on()) snprintf(s, sizeof(s), "%s<%d>", kern, a); }
+    be_kname(const char *kern, int a, int b, int c) { s[0] = 0; if (be_trace_on()) snprintf(s, sizeof(s), "%s<%d, %d, %d>", kern, a, b, c); }
+};
 #define GIE_LAUNCH_(b, kern, grid, block, lds, ...) do { \
         if ((b)->prof_on && (b)->cur_id >= 0) { \
             const int e0_ = be_prof_event(b), e1_ = be_prof_event(b); \
@@ -363,16 +371,16 @@ template <int CP, int TX, int WAVES> static void gie_launch_edt_z(be_state *b, c
     int wgs = (int)((160 * 1024) / (lds + 256));            /* workgroups that fit one CU's LDS */
     if (wgs < 1) wgs = 1; if (wgs > 4) wgs = 4;
     int grid = wgs * b->cu_total; if (grid > (ntiles + 1) / 2) grid = (ntiles + 1) / 2;     /* tiles are taken in pairs */
-    GIE_LAUNCH(b, (k_edt_z<CP, TX, WAVES>), dim3(grid), dim3(64 * WAVES), lds, c, ntx, ntiles, full);
+    GIE_LAUNCH_AS(b, be_kname("k_edt_z", CP, TX, WAVES).s, (k_edt_z<CP, TX, WAVES>), dim3(grid), dim3(64 * WAVES), lds, c, ntx, ntiles, full);
 }
 /* pass X (zpass false): `zs_fused` = the fused streaming form of pass Z may take the volume (be_zs_mode), when it does the launch
  * returns at once; redo: only the rows of the slabs that form gave up (k_edt_x_redo) */
 template <int CP> static void gie_launch_edt_xz(be_state *b, const gie_ctx &c, bool zpass, int full, int zs_fused = 0, bool redo = false)
 {
     if (redo) {
-        GIE_LAUNCH(b, k_edt_x_redo<CP>, dim3(b->cu_total * 8), dim3(64 * GIE_EDTX_WAVES), 0, c);
+        GIE_LAUNCH_AS(b, be_kname("k_edt_x_redo", CP).s, k_edt_x_redo<CP>, dim3(b->cu_total * 8), dim3(64 * GIE_EDTX_WAVES), 0, c);
     } else if (!zpass) {
-        GIE_LAUNCH(b, k_edt_x<CP>, dim3((c.Y + GIE_EDTX_WAVES - 1) / GIE_EDTX_WAVES, c.Z), dim3(64 * GIE_EDTX_WAVES), 0, c, zs_fused, full);
+        GIE_LAUNCH_AS(b, be_kname("k_edt_x", CP).s, k_edt_x<CP>, dim3((c.Y + GIE_EDTX_WAVES - 1) / GIE_EDTX_WAVES, c.Z), dim3(64 * GIE_EDTX_WAVES), 0, c, zs_fused, full);
     } else {
         gie_launch_edt_z<CP, 16, 8>(b, c, full);      /* 2 workgroups per CU overlap load / envelope / store phases */
     }

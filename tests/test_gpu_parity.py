@@ -150,7 +150,9 @@ def test_long_drive_on_a_fixed_pool(oracle_lib):
     ((64, 64, 64), 0.001, 1), ((100, 70, 33), 0.01, 2), ((130, 20, 257), 0.0005, 3), ((16, 300, 16), 0.02, 4),
     ((512, 8, 8), 0.003, 5), ((8, 8, 512), 0.003, 6), ((8, 512, 8), 0.003, 7), ((65, 129, 1), 0.01, 8),
     ((1, 1, 1), 1.0, 9), ((40, 40, 40), 1.0, 10),
-    # the 1024-long axis templates (pass Y with 32 mask words, envelope passes with CP = 16)
+    # the 1024-long axis templates: envelope passes with CP = 16; pass Y along 1024 rows, which at X = 16 (a multiple of 4) is
+    # k_edt_y4<32> — the 32-mask-word kernel k_edt_y<32,16> takes Y > 512 only where X % 4 != 0 (test_edt_forms_gpu.py: y_7x513,
+    # y_67x1024, y_3x1024)
     ((1024, 16, 12), 0.002, 11), ((16, 1024, 12), 0.002, 12), ((12, 16, 1024), 0.002, 13),
     # pass Z picks its argmin form by the number of planes with obstacles: banded (<= 160) or divide & conquer
     ((8, 8, 1000), 0.001, 14), ((24, 24, 400), 0.02, 15), ((20, 20, 200), 0.05, 16), ((16, 16, 130), 0.003, 17),
