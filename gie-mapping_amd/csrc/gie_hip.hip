@@ -16,6 +16,7 @@
 #include <hip/hip_ext.h>
 #include <rocprim/rocprim.hpp>
 #include "gie_kernels.hip.h"
+#include "gie_edt_plan.h"
 
 #define GIE_NEV 8
 
@@ -357,61 +358,25 @@ static void be_exclusive_scan(be_state *b, const int32_t *flag, int32_t *rank, i
     GIE_HIP_OK(rocprim::exclusive_scan(b->scan_tmp, bytes, flag, rank, 0, (size_t)n, rocprim::plus<int32_t>(), b->stream));
 }
 
-template <int CP, int TX, int WAVES> static void gie_launch_edt_z(be_state *b, const gie_ctx &c, int full)
+/* The batch EDT's launchers: what they launch, and whether, is gie_edt_plan_for's (gie_edt_plan.h).  A CP value of the plan to its instantiation: */
+#define BE_EDT_CP(cp, fn, ...) do { switch (cp) { case 1: fn<1>(__VA_ARGS__); break; case 2: fn<2>(__VA_ARGS__); break; case 4: fn<4>(__VA_ARGS__); break; \
+                                                  case 8: fn<8>(__VA_ARGS__); break; default: fn<16>(__VA_ARGS__); break; } } while (0)
+/* pass X; p.x_zs: the fused streaming form of pass Z may take the volume — when it does the launch returns at once */
+template <int CP> static void be_edt_x(be_state *b, const gie_ctx &c, const gie_edt_plan &p, int full)
+{ GIE_LAUNCH_AS(b, be_kname("k_edt_x", CP).s, k_edt_x<CP>, dim3(p.x_grid[0], p.x_grid[1]), dim3(64 * GIE_EDTX_WAVES), 0, c, p.x_zs, full); }
+/* ... only the rows of the slabs that form gave up */
+template <int CP> static void be_edt_x_redo(be_state *b, const gie_ctx &c, const gie_edt_plan &p)
+{ GIE_LAUNCH_AS(b, be_kname("k_edt_x_redo", CP).s, k_edt_x_redo<CP>, dim3(p.redo_grid), dim3(64 * GIE_EDTX_WAVES), 0, c); }
+/* the column kernel of pass Z */
+template <int CP> static void be_edt_column(be_state *b, const gie_ctx &c, const gie_edt_plan &p, int full)
 {
-    constexpr int LP = 64 * CP;
-    const size_t tile = ((size_t)c.Z * (TX + 1) + 3) & ~(size_t)3;
-    const size_t lds = tile * 4 + (size_t)WAVES * LP * 8 + (size_t)LP * 2 + 16;      /* column tile + per-wave sites + plane list */
     static bool attr_done = false;
     if (!attr_done) {
-        GIE_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_edt_z<CP, TX, WAVES>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        GIE_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_edt_z<CP, GIE_EDTZ_TX, GIE_EDTZ_WAVES>), hipFuncAttributeMaxDynamicSharedMemorySize, GIE_LDS_BYTES));
         attr_done = true;
     }
-    const int ntx = (c.X + TX - 1) / TX, ntiles = ntx * c.Y;
-    int wgs = (int)((160 * 1024) / (lds + 256));            /* workgroups that fit one CU's LDS */
-    if (wgs < 1) wgs = 1; if (wgs > 4) wgs = 4;
-    int grid = wgs * b->cu_total; if (grid > (ntiles + 1) / 2) grid = (ntiles + 1) / 2;     /* tiles are taken in pairs */
-    GIE_LAUNCH_AS(b, be_kname("k_edt_z", CP, TX, WAVES).s, (k_edt_z<CP, TX, WAVES>), dim3(grid), dim3(64 * WAVES), lds, c, ntx, ntiles, full);
+    GIE_LAUNCH_AS(b, be_kname("k_edt_z", CP, GIE_EDTZ_TX, GIE_EDTZ_WAVES).s, (k_edt_z<CP, GIE_EDTZ_TX, GIE_EDTZ_WAVES>), dim3(p.col_grid), dim3(64 * GIE_EDTZ_WAVES), (size_t)p.col_lds, c, p.col_ntx, p.col_ntiles, full);
 }
-/* pass X (zpass false): `zs_fused` = the fused streaming form of pass Z may take the volume (be_zs_mode), when it does the launch
- * returns at once; redo: only the rows of the slabs that form gave up (k_edt_x_redo) */
-template <int CP> static void gie_launch_edt_xz(be_state *b, const gie_ctx &c, bool zpass, int full, int zs_fused = 0, bool redo = false)
-{
-    if (redo) {
-        GIE_LAUNCH_AS(b, be_kname("k_edt_x_redo", CP).s, k_edt_x_redo<CP>, dim3(b->cu_total * 8), dim3(64 * GIE_EDTX_WAVES), 0, c);
-    } else if (!zpass) {
-        GIE_LAUNCH_AS(b, be_kname("k_edt_x", CP).s, k_edt_x<CP>, dim3((c.Y + GIE_EDTX_WAVES - 1) / GIE_EDTX_WAVES, c.Z), dim3(64 * GIE_EDTX_WAVES), 0, c, zs_fused, full);
-    } else {
-        gie_launch_edt_z<CP, 16, 8>(b, c, full);      /* 2 workgroups per CU overlap load / envelope / store phases */
-    }
-}
-static void gie_launch_edt_dim(be_state *b, const gie_ctx &c, int L, bool zpass, int full, int zs_fused = 0, bool redo = false)
-{
-    if (L <= 64) gie_launch_edt_xz<1>(b, c, zpass, full, zs_fused, redo);
-    else if (L <= 128) gie_launch_edt_xz<2>(b, c, zpass, full, zs_fused, redo);
-    else if (L <= 256) gie_launch_edt_xz<4>(b, c, zpass, full, zs_fused, redo);
-    else if (L <= 512) gie_launch_edt_xz<8>(b, c, zpass, full, zs_fused, redo);
-    else gie_launch_edt_xz<16>(b, c, zpass, full, zs_fused, redo);
-}
-/* the host half of "pass Z's streaming form takes the volume" (gie_zs_takes): 0 = never, 1 = it reads pass X's planes, 2 = the
- * fused form, which reads pass Y's (X even; pass X is skipped when it takes the volume; GIE_ZS_FUSED=0 keeps the first for A/B runs) */
-static int be_zs_mode(const gie_ctx &c)
-{
-    if (c.Z < 64 || c.Z > 1024) return 0;          /* (short columns: the column kernel) */
-    static const int fused = GIE_SWITCH("GIE_ZS_FUSED", 1);
-    return (fused && (c.X & 1) == 0) ? 2 : 1;     /* (the fused form loads its rows two columns to a dword) */
-}
-/* pass Z: the streaming form (if it takes the volume), pass X on the rows of the slabs it gave up (fused form: pass X did not
- * run), the column kernel (the rest, or the repair of those slabs) */
-static int be_edt_z_stream(be_state *b, const gie_ctx &c, int full, int zs, int guess = GIE_EDT_HINT_NONE, int note = 0);
-static void be_edt_z_rest(be_state *b, const gie_ctx &c, int full, int zs)
-{
-    if (zs == 2) gie_launch_edt_dim(b, c, c.X, false, full, 0, true);
-    gie_launch_edt_dim(b, c, c.Z, true, full);
-}
-/* pass Z again over the whole volume (pass Y is complete, pass X where the streaming form does not take the volume) */
-static void be_edt_z(be_state *b, const gie_ctx &c, int full) { const int zs = be_zs_mode(c); be_edt_z_rest(b, c, full, be_edt_z_stream(b, c, full, zs) ? zs : 0); }
-/* EDT_OCC::batchEDTUpdate, local_edt.cu:7-28 */
 /* adaptive sweep (k_voxa): the kernel walks the list or sweeps the volume, whichever the list's
  * length calls for; staged = the functor's load1/load2/finish form; always_list = never sweep */
 /* mode: 0 = the kernel walks its list or sweeps the volume (decided on the device), 1 = always the list,
@@ -483,35 +448,6 @@ static void be_frontier_tiles(be_state *b, const gie_ctx &c, const int32_t *know
     }
     GIE_LAUNCH(b, k_frontier_tiles, dim3(b->cu_total * mult), dim3(64 * GIE_FR_WAVES), 0, c, list, count_idx);
 }
-static void be_edt_z_direct(be_state *b, const gie_ctx &c)
-{
-    GIE_LAUNCH(b, k_edt_z_direct, dim3(b->cu_total * 16), dim3(256), 0, c);
-}
-/* the streaming form of pass Z (k_edt_z_stream): a wave per (64 columns, y, z segment) */
-#define GIE_ZSTREAM_WAVES 8
-/* returns 1 when launched: the launch also carries the list form of the pass (k_edt_z_direct's body) when `full` is 0.
- * zs: be_zs_mode, or 1 in its place (be_edt); guess: what the update was launched for (GIE_EDT_HINT_*); note: the kernel stores the hint */
-static int be_edt_z_stream(be_state *b, const gie_ctx &c, int full, int zs, int guess, int note)
-{
-    if (!zs) return 0;
-    uint32_t *const hint = note ? b->edt_hint_dev : nullptr;
-    const int nxr = (c.X + 63) / 64;
-    /* z segments so that the launch has about eight waves per SIMD (GIE_ZSTREAM_WAVES) to overlap its rows' round trips (a segment re-reads 16 planes) */
-    const long long want = (long long)b->cu_total * 4 * GIE_ZSTREAM_WAVES;
-    int nseg = (int)((want + (long long)nxr * c.Y - 1) / ((long long)nxr * c.Y));
-    const int maxseg = c.Z / 64 > 0 ? c.Z / 64 : 1;
-    if (nseg > maxseg) nseg = maxseg; if (nseg < 1) nseg = 1;
-    int seg_len = ((c.Z + nseg - 1) / nseg + 31) & ~31;
-    nseg = (c.Z + seg_len - 1) / seg_len;
-    const long long waves = (long long)nxr * nseg * c.Y;
-    long long grid = (waves + 3) / 4;
-    const long long cap = (long long)b->cu_total * 8 * 4;
-    if (grid > cap) grid = cap;
-    if (!full && grid < (long long)b->cu_total * 16) grid = (long long)b->cu_total * 16;      /* (the list form's grid: be_edt_z_direct) */
-    if (zs == 2) GIE_LAUNCH(b, k_edt_z_stream<true>, dim3((unsigned)grid), dim3(256), 0, c, full, nseg, seg_len, zs, guess, hint);
-    else GIE_LAUNCH(b, k_edt_z_stream<false>, dim3((unsigned)grid), dim3(256), 0, c, full, nseg, seg_len, zs, guess, hint);
-    return 1;
-}
 /* tskip for this update; with c.catchup_fast the tiles whose deferred records have to be stored are listed and stored (pupvt: the
  * wave-range pivot of the update that left them) */
 static void be_tile_oldskip(be_state *b, const gie_ctx &c, const int pupvt[3])
@@ -567,51 +503,41 @@ static void be_edt_hint_debug(be_state *b, int force, int32_t *info)
     if (info) { for (int i = 0; i < 3; i++) info[i] = b->edt_hint ? (int32_t)b->edt_hint[i] : 0; info[3] = b->edt_guess; }
 }
 #endif
-/* full = 1: whole volume (column kernel); 0: only where Mark reads — the direct kernel over tl_known
- * and the column kernel are both launched and the one the known-tile count does not call for
- * returns at once */
+static int be_zs_fused_switch() { static const int on = GIE_SWITCH("GIE_ZS_FUSED", 1); return on; }
+/* the launches the plan lists, in their order: pass Y, pass X, then pass Z — the streaming form (dense fields: it does the whole pass and flags what it could not
+ * finish for the column kernel; few known tiles: the list form, in the same launch), the list form on its own, k_edt_x_redo, the column kernel (the rest, or the repair).
+ * (no launch, no bracket: the profile lists a stage by the brackets it has counted; a completion is not part of the profile) */
+static void be_edt_run(be_state *b, const gie_ctx &c, int full, int guess, int completion)
+{
+    const gie_edt_plan p = gie_edt_plan_for(c.X, c.Y, c.Z, b->cu_total, full, guess, completion, be_zs_fused_switch());
+    const dim3 gy(p.y_grid), by(p.y_block[0], p.y_block[1]);
+    if (p.y_kernel != GIE_EDT_Y_NONE) be_prof(b, GIE_K_EDT_Y, 0);
+    switch (p.y_kernel) {
+    case GIE_EDT_Y4_16: GIE_LAUNCH(b, k_edt_y4<16>, gy, by, 0, c); break;
+    case GIE_EDT_Y4_32: GIE_LAUNCH(b, k_edt_y4<32>, gy, by, 0, c); break;
+    case GIE_EDT_Y_8_8: GIE_LAUNCH(b, (k_edt_y<8, 8>), gy, by, 0, c); break;
+    case GIE_EDT_Y_16_16: GIE_LAUNCH(b, (k_edt_y<16, 16>), gy, by, 0, c); break;
+    case GIE_EDT_Y_32_16: GIE_LAUNCH(b, (k_edt_y<32, 16>), gy, by, 0, c); break;
+    }
+    if (p.y_kernel != GIE_EDT_Y_NONE) be_prof(b, GIE_K_EDT_Y, 1);
+    if (p.x) { be_prof(b, GIE_K_EDT_X, 0); BE_EDT_CP(p.cp_x, be_edt_x, b, c, p, full); be_prof(b, GIE_K_EDT_X, 1); }
+    if (!completion) be_prof(b, GIE_K_EDT_Z, 0);
+    uint32_t *const hint = p.stream_note ? b->edt_hint_dev : nullptr;
+    if (p.stream && p.stream_fused) GIE_LAUNCH(b, k_edt_z_stream<true>, dim3(p.stream_grid), dim3(256), 0, c, full, p.nseg, p.seg_len, p.zs, p.guess, hint);
+    else if (p.stream) GIE_LAUNCH(b, k_edt_z_stream<false>, dim3(p.stream_grid), dim3(256), 0, c, full, p.nseg, p.seg_len, p.zs, p.guess, hint);
+    if (p.direct) GIE_LAUNCH(b, k_edt_z_direct, dim3(p.direct_grid), dim3(256), 0, c);
+    if (p.redo) BE_EDT_CP(p.cp_x, be_edt_x_redo, b, c, p);
+    BE_EDT_CP(p.cp_z, be_edt_column, b, c, p, full);
+    if (!completion) be_prof(b, GIE_K_EDT_Z, 1);
+}
+/* EDT_OCC::batchEDTUpdate, local_edt.cu:7-28.  full = 1: whole volume; 0: only where Mark reads.  The guess is taken where it counts */
 static void be_edt(be_state *b, const gie_ctx &c, int full)
 {
-    /* a linear grid: the kernels derive (strip, z) from the workgroup index so that both 64-byte strips of a 128-byte type line
-     * run on one XCD (gie_edty_strip, gie_ops.h) */
-    dim3 gy(16 * gie_edty_groups((c.X + GIE_EDTY_COLS - 1) / GIE_EDTY_COLS, c.Z));
-    be_prof(b, GIE_K_EDT_Y, 0);
-    /* one 32-voxel mask word per thread: with only the planes that hold obstacles at work, the
-     * pass is bound by how many loads are in flight, not by bytes */
-    /* X % 4 == 0: four columns per lane, dword loads / 8-byte stores (k_edt_y4) */
-    if ((c.X & 3) == 0) {
-        /* 16 lanes x 4 columns per workgroup (more, smaller workgroups than 32 lanes) */
-        const int yb = c.Y > 512 ? 32 : 16, nq = (c.Y + yb - 1) / yb;
-        dim3 g4(16 * gie_edty_groups((c.X / 4 + GIE_EDTY4_LANES - 1) / GIE_EDTY4_LANES, c.Z)), b4(GIE_EDTY4_LANES, nq);
-        if (yb == 16) GIE_LAUNCH(b, k_edt_y4<16>, g4, b4, 0, c);
-        else GIE_LAUNCH(b, k_edt_y4<32>, g4, b4, 0, c);
-    }
-    else if (c.Y <= 256) GIE_LAUNCH(b, (k_edt_y<8, 8>), gy, dim3(GIE_EDTY_COLS, 8), 0, c);
-    else if (c.Y <= 512) GIE_LAUNCH(b, (k_edt_y<16, 16>), gy, dim3(GIE_EDTY_COLS, 16), 0, c);
-    else GIE_LAUNCH(b, (k_edt_y<32, 16>), gy, dim3(GIE_EDTY_COLS, 16), 0, c);
-    be_prof(b, GIE_K_EDT_Y, 1);
-    /* Where the fused streaming form may take the volume (be_zs_mode 2) the device decides whether it does (gie_zs_takes), and a
-     * launch made for the other outcome costs its full time on the stream: pass X's 64 K workgroups that leave at once, or an
-     * empty k_edt_x_redo.  The outcome barely moves from one update to the next, so the launches are made for the last one's:
-     *   TOOK: no pass X.  Should the form not take this volume after all, its kernel says so (GIE_CNT_XMISS) and the launches
-     *         behind it do all of pass X and pass Z;
-     *   LEFT: be_zs_mode 1 — pass X in full, the streaming form from pass X's planes (which still takes the volume if this
-     *         update's planes call for it), no k_edt_x_redo;
-     *   NONE: both, as before.
-     * Exact whatever the guess: a wrong one costs time on that update only. */
-    int zs = be_zs_mode(c);
-    const int guess = zs == 2 ? be_edt_hint_take(b) : GIE_EDT_HINT_NONE;
-    if (guess == GIE_EDT_HINT_LEFT) zs = 1;
-    /* (no launch, no bracket: the profile lists a stage by the brackets it has counted) */
-    if (guess != GIE_EDT_HINT_TOOK) { be_prof(b, GIE_K_EDT_X, 0); gie_launch_edt_dim(b, c, c.X, false, full, zs == 2 ? zs : 0); be_prof(b, GIE_K_EDT_X, 1); }
-    be_prof(b, GIE_K_EDT_Z, 0);
-    /* dense fields: the streaming form does the whole pass and flags what it could not finish for the column kernel; few known
-     * tiles: the list form — in the same launch */
-    const int zl = be_edt_z_stream(b, c, full, zs, guess, 1);
-    if (!zl && !full) be_edt_z_direct(b, c);
-    be_edt_z_rest(b, c, full, zl ? zs : 0);
-    be_prof(b, GIE_K_EDT_Z, 1);
+    const int guess = gie_edt_zs_host(c.X, c.Z, be_zs_fused_switch()) == 2 ? be_edt_hint_take(b) : GIE_EDT_HINT_NONE;
+    be_edt_run(b, c, full, guess, 0);
 }
+/* pass Z again over the whole volume (pass Y is complete, pass X where the streaming form does not take the volume) */
+static void be_edt_z(be_state *b, const gie_ctx &c, int full) { be_edt_run(b, c, full, GIE_EDT_HINT_NONE, 1); }
 /* waves A, B and C in one launch; workgroups are co-resident by construction (512 threads and ≈ 151 KB of LDS each:
  * at most one per compute unit).  The frame clear has zeroed the barrier word and the per-level
  * arrays; a second launch inside the same map update (gie_refine) clears them itself. */

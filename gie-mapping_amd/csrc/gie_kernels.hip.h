@@ -438,9 +438,6 @@ __global__ __launch_bounds__(256) void k_block_init_list(const gie_ctx c, const 
  * reads a quarter of the types and publishes its mask words through LDS, then every thread
  * holds the whole mask in registers and writes the answers of its own quarter — 4x the waves
  * in flight of a thread-per-column scan, same HBM traffic (1 B read + 2 B written per voxel). */
-#ifndef GIE_EDTY_COLS
-#define GIE_EDTY_COLS 64
-#endif
 template <int YW, int TPC>
 __global__ __launch_bounds__(GIE_EDTY_COLS * TPC) void k_edt_y(const gie_ctx c)
 {
@@ -516,7 +513,6 @@ __global__ __launch_bounds__(GIE_EDTY_COLS * TPC) void k_edt_y(const gie_ctx c)
  *   - "nothing below" is -65536 and "nothing above" is 65535: the nearer of the two (ties: the
  *     larger y) is one comparison without special cases, and 0xffff comes out where the column
  *     is empty. */
-#define GIE_EDTY4_LANES 16      /* lanes along x of a workgroup (more, smaller workgroups than 32) */
 template <int YB>
 __global__ __launch_bounds__(32 * GIE_EDTY4_LANES) void k_edt_y4(const gie_ctx c)
 {
@@ -893,10 +889,7 @@ __device__ __forceinline__ int gie_row_compact_push(uint2 *ce, int base, const b
 /* one wave per (y,z) row; rows are contiguous in memory so loads/stores are coalesced; every
  * lane ends up with the CP consecutive results of its chunk in registers and stores them as
  * 16-byte vectors (the wave covers one contiguous run) */
-#ifndef GIE_EDTX_WAVES
-#define GIE_EDTX_WAVES 4
-#endif
-/* pass Z's streaming form takes the volume (k_edt_z_stream below): `zs` = the host half (be_zs_mode: Z in [64, 1024], the switch),
+/* pass Z's streaming form takes the volume (k_edt_z_stream below): `zs` = the host half (gie_edt_zs_host, gie_edt_plan.h: Z in [64, 1024], the switch),
  * the rest is this update's, on the device — the list form is not called for and the planes with obstacles are many (k_edt_prep
  * has counted both before pass X runs) */
 GIE_HD int gie_zs_takes(const gie_ctx &c, const int zs, const int full)
@@ -1005,7 +998,7 @@ __device__ __forceinline__ void gie_edt_x_row(const gie_ctx &c, const int y, con
         for (int m = 0; m < CP; m++) if (u0 + m < X) out[u0 + m] = o[m];
     }
 }
-/* zs: pass Z's fused streaming form may take the volume (be_zs_mode) — when it does (it reads pass Y's planes itself) this pass
+/* zs: pass Z's fused streaming form may take the volume (gie_edt_zs_host) — when it does (it reads pass Y's planes itself) this pass
  * has nothing to do, and every workgroup leaves after the test (0.017 ms for the headline's 64 K workgroups: workgroups of 16 waves
  * were measured no cheaper, and a grid-stride walk over the rows needs 123 VGPRs at CP = 8 against 44, so the grid stays this one —
  * and the host does not launch it where the form took the last update's volume: be_edt) */
@@ -1353,7 +1346,7 @@ __device__ __forceinline__ uint32_t gie_zs_fused_key(const gie_lds_u32 *row, con
     return m < GIE_ZS_LIMIT ? ((m ^ (31u << 13)) | ((uint32_t)j << 18)) : (GIE_ZS_NONE | ((uint32_t)j << 18));
 }
 /* NP planes from zfirst on (clamped to the volume; pm bit j: plane zfirst + j holds obstacles) -> window places JB .. JB + NP - 1.
- * Lane l < 40 loads the columns x0 - 8 + 2l and the one after as one dword (X even: be_zs_mode) */
+ * Lane l < 40 loads the columns x0 - 8 + 2l and the one after as one dword (X even: gie_edt_zs_host) */
 template <int NP, int JB, int AUX>
 __device__ __forceinline__ void gie_zs_fused_keys(uint32_t (&wk)[GIE_ZS_W], uint32_t (*srow)[GIE_ZS_XW], const __amdgpu_buffer_rsrc_t rs, const unsigned vo,
                                                   const unsigned ps2, const int zfirst, const int Z, const unsigned long long pm, const bool ok0, const bool ok1, const int y8, const int lane)
@@ -1488,7 +1481,7 @@ __device__ __forceinline__ bool gie_zs_wide_trip_fused(const __amdgpu_buffer_rsr
         __builtin_amdgcn_raw_buffer_store_b32(bc[t], rs_out, (zc + t < z1) ? voff : GIE_BUF_OOB, (unsigned)min(zc + t, Z - 1) * pstride, 0);
     return true;
 }
-/* guess: what be_edt launched this update for (GIE_EDT_HINT_*: TOOK — pass X was not launched; LEFT — zs is 1 where be_zs_mode is 2).
+/* guess: what be_edt launched this update for (GIE_EDT_HINT_*: TOOK — pass X was not launched; LEFT — zs is 1 where gie_edt_zs_host is 2).
  * hint: where to note for the host whether the form takes this volume, and a wrong guess (gie_types.h; null: a launch that is not
  * a map update's first) */
 template <bool FUSED>

@@ -1638,7 +1638,6 @@ GIE_DEV void gie_query_voxel(const gie_ctx &c, const int32_t *xyz, int i, gie_vo
  * — pair number 8 g + r = z * ceil(nstrip / 2) + p — get indices that are equal modulo 8 and eight apart: one XCD, close in
  * time, and the line is fetched once.  (Placement is a matter of speed only: any mapping that takes every (strip, z) once is
  * right.)  Returns 0 for the indices that pad the launch (the missing half of an odd strip count, the last group's tail). */
-GIE_HD int gie_edty_groups(int nstrip, int Z) { return (((nstrip + 1) >> 1) * Z + 7) >> 3; }      /* the launch has 16 workgroups per group */
 GIE_HD int gie_edty_strip(int l, int nstrip, int Z, int *strip, int *z)
 {
     const int np = (nstrip + 1) >> 1;

@@ -238,6 +238,18 @@ enum {
 #define GIE_EDT_HINT_LEFT 1                     /* the form did not take the volume: pass X in full, the streaming form from pass X's planes, no k_edt_x_redo */
 #define GIE_EDT_HINT_TOOK 2                     /* the fused form took it: pass X is not launched */
 #define GIE_EDT_HINT_WORD(planes, took) (((uint32_t)(planes) << 2) | ((took) ? 2u : 1u))
+#ifndef GIE_EDTY_COLS              /* (the batch EDT's launch constants: its kernels, gie_kernels.hip.h, and its launch plan, gie_edt_plan.h) */
+#define GIE_EDTY_COLS 64
+#endif
+#define GIE_EDTY4_LANES 16      /* lanes along x of a workgroup (more, smaller workgroups than 32) */
+#ifndef GIE_EDTX_WAVES
+#define GIE_EDTX_WAVES 4
+#endif
+#define GIE_ZSTREAM_WAVES 8     /* the streaming form of pass Z (k_edt_z_stream): waves per SIMD its launch aims at */
+#define GIE_EDTZ_TX 16          /* the column kernel's instantiation k_edt_z<CP, 16, 8>: columns of a tile, waves */
+#define GIE_EDTZ_WAVES 8
+#define GIE_LDS_BYTES (160 * 1024)      /* LDS of a compute unit */
+GIE_HD int gie_edty_groups(int nstrip, int Z) { return (((nstrip + 1) >> 1) * Z + 7) >> 3; }      /* pass Y's launch has 16 workgroups per group (gie_edty_strip, gie_ops.h) */
 /* ids of the per-kernel profile (be_prof brackets; gie_kernel_names, gie_profile_read) */
 enum { GIE_K_CLASSIFY = 0, GIE_K_RAY_REGISTER, GIE_K_RAY_FREE, GIE_K_RAY_FINAL, GIE_K_ALLOC, GIE_K_FUSE, GIE_K_EDT_Y, GIE_K_EDT_X,
        GIE_K_EDT_Z, GIE_K_MARK, GIE_K_FRONTIER, GIE_K_WAVE_A, GIE_K_WAVE_B, GIE_K_WAVE_C, GIE_K_COMMIT, GIE_K_EDT_ZFACES, GIE_K_MARKC,

@@ -2,7 +2,7 @@
 
 Plain Python and numpy, no GPU.  Written from the dispatch code, constant by constant:
 
-  be_edt, be_zs_mode, gie_launch_edt_dim, be_edt_z_stream, be_edt_z_rest      gie_hip.hip            what the host launches
+  gie_edt_plan_for (executed by be_edt / be_edt_z, gie_hip.hip)                gie_edt_plan.h         what the host launches
   gie_zs_takes, gie_edt_x_row, gie_row_window, k_edt_z, k_edt_z_stream        gie_kernels.hip.h      what the device picks
   gie_z_use_lists                                                              gie_types.h
   gie_batch_edt (full = 0 where the volume is at most 64 tiles high)           gie_api.inc.h
@@ -33,23 +33,24 @@ WIN_CLEAR_HI = (WIN_MAX + 3) ** 2
 ZS_R, ZS_C, ZS_R2 = 8, 16, 24       # GIE_ZS_R, GIE_ZS_C, GIE_ZS_R2: narrow window, planes per trip, wide window
 ZS_LIMIT = (ZS_R + 1) ** 2          # the narrow trip is exact below 81 ...
 ZS_LIMIT2 = (ZS_R2 + 1) ** 2        # ... the wide trip below 625
-ZS_WAVES = 8                        # GIE_ZSTREAM_WAVES, gie_hip.hip
+ZS_WAVES = 8                        # GIE_ZSTREAM_WAVES, gie_types.h
 Z_LIST_DIV = 8                      # GIE_Z_LIST_DIV, gie_types.h
 Z_SHORT_TILES = 8                   # GIE_Z_SHORT_LISTS: volumes at most this many tiles high always take the list form
 PARTIAL_MAX_TILES = 64              # gie_batch_edt: full = 0 up to this many z tiles
 CPS = (1, 2, 4, 8, 16)
+NONE, LEFT, TOOK = 0, 1, 2          # GIE_EDT_HINT_*, gie_types.h: what an update is launched for
 CU_TOTAL = 256                      # compute units of the device the suite runs on; stream_segments checks that it does not matter
 
 Y_KERNELS = ("k_edt_y4<16>", "k_edt_y4<32>", "k_edt_y<8,8>", "k_edt_y<16,16>", "k_edt_y<32,16>")
 
 
 def cp_of(L):
-    """gie_launch_edt_dim: the CP instantiation of a line of L voxels"""
+    """gie_edt_cp: the CP instantiation of a line of L voxels"""
     return 1 if L <= 64 else 2 if L <= 128 else 4 if L <= 256 else 8 if L <= 512 else 16
 
 
 def pass_y_kernel(X, Y):
-    """be_edt: (kernel name, rows of a thread's share)"""
+    """gie_edt_plan_for, pass Y: (kernel name, rows of a thread's share)"""
     if X % 4 == 0:
         return ("k_edt_y4<32>", 32) if Y > 512 else ("k_edt_y4<16>", 16)
     if Y <= 256:
@@ -59,11 +60,11 @@ def pass_y_kernel(X, Y):
     return "k_edt_y<32,16>", 64              # QW = 2
 
 
-def zs_mode(X, Z):
-    """be_zs_mode: 0 = no streaming form, 1 = from pass X's planes (odd X), 2 = fused (even X)"""
+def zs_mode(X, Z, fused_switch=True):
+    """gie_edt_zs_host: 0 = no streaming form, 1 = from pass X's planes (odd X, or GIE_ZS_FUSED=0), 2 = fused (even X)"""
     if Z < 64 or Z > 1024:
         return 0
-    return 2 if X % 2 == 0 else 1
+    return 2 if fused_switch and X % 2 == 0 else 1
 
 
 def tiles(size):
@@ -92,18 +93,25 @@ def zs_takes(size, planes_with_obstacles, known_tiles, full, force=None):
     return bool(zs_mode(X, Z)) and not (not full and z_use_lists(size, known_tiles, force)) and planes_with_obstacles > BAND_MAXK
 
 
-def host_forms(size, planes_with_obstacles, known_tiles, full, completion=False):
+def host_forms(size, planes_with_obstacles, known_tiles, full, completion=False, guess=NONE, fused_switch=True):
     """The kernel names of the batch EDT that gie_batch_edt (or, completion=True, the pass Z gie_read_batch_edt runs again with
     full = 1: be_edt_z) must announce, blanks removed.  The guess of a fresh mapper is NONE (be_edt_hint_take: the hint word is
     0), so pass X and k_edt_x_redo are both launched wherever the fused form may take the volume, and neither the planes with
     obstacles nor the known tiles change a launch: those two decide on the device (z_worker) which of the launched kernels
-    does the pass.  They are arguments so that a call states the whole situation."""
+    does the pass.  They are arguments so that a call states the whole situation.
+    guess: what the update is launched for ("the hint"); it counts only for an update of a volume the fused form may
+    take.  TOOK: no pass X.  LEFT: the streaming form that reads pass X's planes, no k_edt_x_redo."""
     X, Y, Z = size
-    zs = zs_mode(X, Z)
+    zs = zs_mode(X, Z, fused_switch)
+    if completion or zs != 2:
+        guess = NONE
+    if guess == LEFT:
+        zs = 1
     out = set()
     if not completion:
         out.add(pass_y_kernel(X, Y)[0])
-        out.add("k_edt_x<%d>" % cp_of(X))                     # (guess NONE: always)
+        if guess != TOOK:
+            out.add("k_edt_x<%d>" % cp_of(X))
     if zs:
         out.add("k_edt_z_stream<true>" if zs == 2 else "k_edt_z_stream<false>")
         if zs == 2:
@@ -244,7 +252,7 @@ def column_forms_z(occ, full=True, need=None):
 
 
 def stream_segments(size, cu_total=CU_TOTAL):
-    """be_edt_z_stream: (number of z segments, their length).  The volumes of the table are small enough for the cap of one
+    """gie_edt_plan_for, the streaming kernel: (number of z segments, their length).  The volumes of the table are small enough for the cap of one
     segment per 64 planes to bind on any device of 16 compute units or more, which is asserted."""
     X, Y, Z = size
     nxr = (X + 63) // 64

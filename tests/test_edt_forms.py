@@ -48,24 +48,42 @@ def test_the_impossible_combinations_are_impossible_by_the_rules():
     assert set(form[0]) == {"banded"} and set(form[1]) == {"skipped"}
 
 
-@pytest.mark.parametrize("size,full,completion,want", [
+# (size, full, completion, guess, kernels); test_edt_plan_host.py holds the product's plan against every row too
+HAND_ROWS = [
     # (the shapes the issue names: X = 16 takes k_edt_y4 since that kernel exists; Y > 512 at X % 4 != 0 takes k_edt_y<32,16>)
-    ((16, 1024, 12), 0, False, {"k_edt_y4<32>", "k_edt_x<1>", "k_edt_z_direct", "k_edt_z<1,16,8>"}),
-    ((3, 1024, 2), 0, False, {"k_edt_y<32,16>", "k_edt_x<1>", "k_edt_z_direct", "k_edt_z<1,16,8>"}),
-    ((2, 300, 2), 0, False, {"k_edt_y<16,16>", "k_edt_x<1>", "k_edt_z_direct", "k_edt_z<1,16,8>"}),
-    ((5, 256, 3), 0, True, {"k_edt_z<1,16,8>"}),
-    ((130, 16, 176), 0, False, {"k_edt_y<8,8>", "k_edt_x<4>", "k_edt_z_stream<true>", "k_edt_x_redo<4>", "k_edt_z<4,16,8>"}),
-    ((130, 16, 176), 1, True, {"k_edt_z_stream<true>", "k_edt_x_redo<4>", "k_edt_z<4,16,8>"}),
-    ((129, 16, 176), 0, False, {"k_edt_y<8,8>", "k_edt_x<4>", "k_edt_z_stream<false>", "k_edt_z<4,16,8>"}),
-    ((129, 16, 176), 1, True, {"k_edt_z_stream<false>", "k_edt_z<4,16,8>"}),
-    ((12, 12, 1024), 1, False, {"k_edt_y4<16>", "k_edt_x<1>", "k_edt_z_stream<true>", "k_edt_x_redo<1>", "k_edt_z<16,16,8>"}),
-    ((1024, 6, 11), 0, False, {"k_edt_y4<16>", "k_edt_x<16>", "k_edt_z_direct", "k_edt_z<1,16,8>"}),
-    ((514, 56, 2), 0, False, {"k_edt_y<8,8>", "k_edt_x<16>", "k_edt_z_direct", "k_edt_z<1,16,8>"}),
-])
-def test_host_forms_by_hand(size, full, completion, want):
-    """the launch rules, read off be_edt / be_edt_z by hand for a few shapes"""
-    assert F.host_forms(size, 1, 1, full, completion) == want
-    assert F.host_forms(size, 500, 10 ** 6, full, completion) == want     # (a fresh mapper's guess is NONE: the counts change no launch)
+    ((16, 1024, 12), 0, False, F.NONE, {"k_edt_y4<32>", "k_edt_x<1>", "k_edt_z_direct", "k_edt_z<1,16,8>"}),
+    ((3, 1024, 2), 0, False, F.NONE, {"k_edt_y<32,16>", "k_edt_x<1>", "k_edt_z_direct", "k_edt_z<1,16,8>"}),
+    ((2, 300, 2), 0, False, F.NONE, {"k_edt_y<16,16>", "k_edt_x<1>", "k_edt_z_direct", "k_edt_z<1,16,8>"}),
+    ((5, 256, 3), 0, True, F.NONE, {"k_edt_z<1,16,8>"}),
+    ((130, 16, 176), 0, False, F.NONE, {"k_edt_y<8,8>", "k_edt_x<4>", "k_edt_z_stream<true>", "k_edt_x_redo<4>", "k_edt_z<4,16,8>"}),
+    ((130, 16, 176), 1, True, F.NONE, {"k_edt_z_stream<true>", "k_edt_x_redo<4>", "k_edt_z<4,16,8>"}),
+    ((129, 16, 176), 0, False, F.NONE, {"k_edt_y<8,8>", "k_edt_x<4>", "k_edt_z_stream<false>", "k_edt_z<4,16,8>"}),
+    ((129, 16, 176), 1, True, F.NONE, {"k_edt_z_stream<false>", "k_edt_z<4,16,8>"}),
+    ((12, 12, 1024), 1, False, F.NONE, {"k_edt_y4<16>", "k_edt_x<1>", "k_edt_z_stream<true>", "k_edt_x_redo<1>", "k_edt_z<16,16,8>"}),
+    ((1024, 6, 11), 0, False, F.NONE, {"k_edt_y4<16>", "k_edt_x<16>", "k_edt_z_direct", "k_edt_z<1,16,8>"}),
+    ((514, 56, 2), 0, False, F.NONE, {"k_edt_y<8,8>", "k_edt_x<16>", "k_edt_z_direct", "k_edt_z<1,16,8>"}),
+    # the guesses, read off the table of DESIGN.md 31 ("the hint"): "took" launches no pass X; "left" the streaming form that reads
+    # pass X's planes and no k_edt_x_redo; neither counts where the fused form cannot take the volume (odd X, Z < 64) or for a completion
+    ((130, 16, 176), 0, False, F.TOOK, {"k_edt_y<8,8>", "k_edt_z_stream<true>", "k_edt_x_redo<4>", "k_edt_z<4,16,8>"}),
+    ((130, 16, 176), 0, False, F.LEFT, {"k_edt_y<8,8>", "k_edt_x<4>", "k_edt_z_stream<false>", "k_edt_z<4,16,8>"}),
+    ((129, 16, 176), 0, False, F.TOOK, {"k_edt_y<8,8>", "k_edt_x<4>", "k_edt_z_stream<false>", "k_edt_z<4,16,8>"}),
+    ((129, 16, 176), 0, False, F.LEFT, {"k_edt_y<8,8>", "k_edt_x<4>", "k_edt_z_stream<false>", "k_edt_z<4,16,8>"}),
+    ((130, 16, 176), 1, True, F.TOOK, {"k_edt_z_stream<true>", "k_edt_x_redo<4>", "k_edt_z<4,16,8>"}),
+    ((130, 16, 176), 1, True, F.LEFT, {"k_edt_z_stream<true>", "k_edt_x_redo<4>", "k_edt_z<4,16,8>"}),
+    ((16, 1024, 12), 0, False, F.TOOK, {"k_edt_y4<32>", "k_edt_x<1>", "k_edt_z_direct", "k_edt_z<1,16,8>"}),
+    ((12, 12, 1024), 1, False, F.TOOK, {"k_edt_y4<16>", "k_edt_z_stream<true>", "k_edt_x_redo<1>", "k_edt_z<16,16,8>"}),
+]
+# (the rows without a guess keep the ids they had before the guess was a column)
+HAND_IDS = ["size%d-%d-%s-" % (i, r[1], r[2]) + ("" if r[3] == F.NONE else "guess%d-" % r[3]) + "want%d" % i for i, r in enumerate(HAND_ROWS)]
+
+
+@pytest.mark.parametrize("size,full,completion,guess,want", HAND_ROWS, ids=HAND_IDS)
+def test_host_forms_by_hand(size, full, completion, guess, want):
+    """the launch rules, read off gie_edt_plan_for (what be_edt / be_edt_z execute) by hand for a few shapes"""
+    assert F.host_forms(size, 1, 1, full, completion, guess) == want
+    assert F.host_forms(size, 500, 10 ** 6, full, completion, guess) == want     # (the counts change no launch)
+    if guess == F.NONE:
+        assert F.host_forms(size, 1, 1, full, completion) == want                # (a fresh mapper's guess is NONE)
 
 
 def test_the_device_rules_at_their_borders():

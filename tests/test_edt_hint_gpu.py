@@ -1,4 +1,5 @@
-"""The batch EDT launches its passes for a guess (be_edt): "pass Z's fused streaming form took the last volume" — pass X is not
+"""The batch EDT launches its passes for a guess (be_edt takes it, gie_edt_plan_for in gie_edt_plan.h states what it changes —
+tests/test_edt_plan_host.py holds that statement against edt_forms.host_forms for every guess without a GPU): "pass Z's fused streaming form took the last volume" — pass X is not
 launched, and where the form does not take this volume after all k_edt_x_redo does every row and the column kernel every tile
 (GIE_CNT_XMISS) —, "it did not" — pass X in full, the streaming form from pass X's planes, no k_edt_x_redo —, or none (both
 launches, as before).  The guess comes from a word the device stores and the host reads without waiting, so a test cannot make it

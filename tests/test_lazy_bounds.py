@@ -7,7 +7,7 @@ bound, (b) lazy tiles bounded above their true batch distances, (c) tbmax exact 
 * even X, the fused form: the hash world with the bench's out-and-back drive, a pocket without obstacles on the way (wide trips,
   slabs given up), unobserved slabs, a jump off the block grid before the turn, an update in the reference's order of kernels
   (stream_enable) and two ray-cast scans between label updates;
-* odd X, the unfused streaming form (be_zs_mode goes by X's parity): slow steps of 0-1 voxels and jumps of 6-9 in both directions;
+* odd X, the unfused streaming form (the launch plan, gie_edt_plan_for, goes by X's parity): slow steps of 0-1 voxels and jumps of 6-9 in both directions;
 * the bound's edge values: a constructed field whose tiles' largest batch distance^2 are exactly 64, 80, 81 and 82, with a pocket
   that makes slabs give up before their last trip (tiles of true 82 left with the give-up's "81 or more").
 Each drive shows from the hook's counters and arrays that the paths it is about ran."""
