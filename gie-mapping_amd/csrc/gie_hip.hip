@@ -596,6 +596,7 @@ extern "C" int gie_debug_edt_hint(gie_mapper *m, int force, int32_t *info)
 #include "gie_los.inc.h"
 #include "gie_path.inc.h"
 #include "gie_cloud.inc.h"
+#include "gie_blocks.inc.h"
 #include "gie_ground.inc.h"
 #include "gie_ground_nf1.inc.h"
 #include "gie_ground_los.inc.h"

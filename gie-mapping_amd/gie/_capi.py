@@ -122,6 +122,18 @@ class CloudPoint(C.Structure):
     _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("intensity", C.c_float)]
 
 
+class BlocksParam(C.Structure):
+    """gie_blocks_param (include/gie.h): 48 bytes."""
+    _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("flags", C.c_int32), ("min_fnt", C.c_int32), ("max_records", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
+class BlockSummary(C.Structure):
+    """gie_block_summary (include/gie.h): 32 bytes."""
+    _fields_ = [("key", C.c_int32 * 3), ("n_free", C.c_uint16), ("n_occupied", C.c_uint16), ("n_fnt", C.c_uint16), ("fnt_voxel", C.c_uint16),
+                ("free_voxel", C.c_uint16), ("flags", C.c_uint16), ("min_dist_sq", C.c_int32), ("reserved", C.c_int32)]
+
+
 class GroundParam(C.Structure):
     """gie_ground_param (include/gie.h): 32 bytes."""
     _fields_ = [("z_lo", C.c_int32), ("z_hi", C.c_int32), ("min_known", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
@@ -221,6 +233,7 @@ assert C.sizeof(GroundViewParam) == 32 and GroundViewParam.n_planes.offset == 8 
 assert C.sizeof(GroundLosParam) == 16 and C.sizeof(GroundHit) == 24 and C.sizeof(GroundShortcutParam) == 32 and C.sizeof(GroundWaypoint) == 24
 assert C.sizeof(GroundParam) == 32 and C.sizeof(GroundCell) == 16 and C.sizeof(GroundNf1Param) == 32
 assert C.sizeof(CloudParam) == 32 and C.sizeof(CloudPoint) == 16
+assert C.sizeof(BlocksParam) == 48 and C.sizeof(BlockSummary) == 32 and BlockSummary.min_dist_sq.offset == 24
 assert C.sizeof(ShortcutParam) == 16 and C.sizeof(Waypoint) == 24 and C.sizeof(ShortcutInfo) == 16
 assert C.sizeof(LosHit) == 24 and C.sizeof(View) == 64 and C.sizeof(ViewScore) == 16 and C.sizeof(LosParam) == 16 and C.sizeof(ViewParam) == 16
 
@@ -229,6 +242,7 @@ NF1_FROM_FRONTIERS = 2
 LOS_UNKNOWN_OPAQUE = 1
 CLOUD_TYPE = 0
 CLOUD_DIST = 1
+BLOCKS_DIST = 1
 GROUND_UNKNOWN_BLOCKS = 1
 GROUND_NF1_UNKNOWN_TRAVERSABLE = 1
 GROUND_NF1_FROM_FRONTIERS = 2
@@ -377,6 +391,9 @@ DEVICE_ONLY = {
     "cloud_local_dev": (C.c_int, [_H, C.POINTER(CloudParam), C.c_void_p, C.c_void_p]),
     "cloud_global": (C.c_int, [_H, C.POINTER(CloudParam), C.c_void_p, C.c_void_p]),
     "cloud_global_dev": (C.c_int, [_H, C.POINTER(CloudParam), C.c_void_p, C.c_void_p]),
+    # global block summaries: counts, frontier blocks and a coarse grid out of the block pool (include/gie.h): device library only
+    "blocks_summary": (C.c_int, [_H, C.POINTER(BlocksParam), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "blocks_summary_dev": (C.c_int, [_H, C.POINTER(BlocksParam), C.c_void_p, C.c_void_p, C.c_void_p]),
     # ground costmap of a height band of the local volume (include/gie.h): device library only
     "ground_compute": (C.c_int, [_H, C.POINTER(GroundParam), C.c_void_p]),
     "ground_compute_dev": (C.c_int, [_H, C.POINTER(GroundParam), C.c_void_p]),

@@ -13,8 +13,8 @@ import sys
 import numpy as np
 
 from . import _capi
-from ._capi import CLOUD_DIST, CLOUD_TYPE, GROUND_POSE_HEADINGS, GROUND_POSE_MAX_SQ, GROUND_POSE_NF1_FROM_FRONTIERS, GROUND_POSE_NF1_REVERSE, GROUND_POSE_NF1_UNKNOWN_TRAVERSABLE, GROUND_FOOTPRINT_MARGIN, GROUND_FOOTPRINT_MAX_SQ, GROUND_FOOTPRINT_UNKNOWN_TRAVERSABLE, GROUND_LOS_UNKNOWN_TRAVERSABLE, GROUND_NF1_FROM_FRONTIERS, GROUND_NF1_UNKNOWN_TRAVERSABLE, GROUND_ROLLOUT_MAX_POSES, GROUND_ROLLOUT_NF1, GROUND_ROLLOUT_UNKNOWN_TRAVERSABLE, GROUND_UNKNOWN_BLOCKS, GROUND_VIEW_UNION, GROUND_VIEW_UNKNOWN_OPAQUE, LOS_UNKNOWN_OPAQUE, NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE, VOX_FNT, VOX_FREE, VOX_OCCUPIED, VOX_UNKNOWN
-from ._capi import CamParam, CloudParam, Config, CostMapHdr, FrameStats, FrontierParam, GroundFootprintParam, GroundFrontierParam, GroundLosParam, GroundNf1Param, GroundParam, GroundPoseNf1Param, GroundRolloutParam, GroundSdfRolloutParam, GroundShortcutParam, GroundViewParam, LosParam, MultiScanParam, Nf1Param, ScanParam, ShortcutParam, ViewParam, Voxel
+from ._capi import BLOCKS_DIST, CLOUD_DIST, CLOUD_TYPE, GROUND_POSE_HEADINGS, GROUND_POSE_MAX_SQ, GROUND_POSE_NF1_FROM_FRONTIERS, GROUND_POSE_NF1_REVERSE, GROUND_POSE_NF1_UNKNOWN_TRAVERSABLE, GROUND_FOOTPRINT_MARGIN, GROUND_FOOTPRINT_MAX_SQ, GROUND_FOOTPRINT_UNKNOWN_TRAVERSABLE, GROUND_LOS_UNKNOWN_TRAVERSABLE, GROUND_NF1_FROM_FRONTIERS, GROUND_NF1_UNKNOWN_TRAVERSABLE, GROUND_ROLLOUT_MAX_POSES, GROUND_ROLLOUT_NF1, GROUND_ROLLOUT_UNKNOWN_TRAVERSABLE, GROUND_UNKNOWN_BLOCKS, GROUND_VIEW_UNION, GROUND_VIEW_UNKNOWN_OPAQUE, LOS_UNKNOWN_OPAQUE, NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE, VOX_FNT, VOX_FREE, VOX_OCCUPIED, VOX_UNKNOWN
+from ._capi import BlocksParam, CamParam, CloudParam, Config, CostMapHdr, FrameStats, FrontierParam, GroundFootprintParam, GroundFrontierParam, GroundLosParam, GroundNf1Param, GroundParam, GroundPoseNf1Param, GroundRolloutParam, GroundSdfRolloutParam, GroundShortcutParam, GroundViewParam, LosParam, MultiScanParam, Nf1Param, ScanParam, ShortcutParam, ViewParam, Voxel
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG, "csrc", "libgie_hip.so")
@@ -35,6 +35,9 @@ SHORTCUT_INFO_DTYPE = np.dtype([("count", "<i4"), ("forced", "<i4"), ("length", 
 # gie_cloud_point (16 bytes)
 CLOUD_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("intensity", "<f4")])
 CLOUD_NO_BAND = (-2 ** 31, 2 ** 31 - 1)
+# gie_block_summary (32 bytes)
+BLOCK_SUMMARY_DTYPE = np.dtype([("key", "<i4", (3,)), ("n_free", "<u2"), ("n_occupied", "<u2"), ("n_fnt", "<u2"), ("fnt_voxel", "<u2"), ("free_voxel", "<u2"),
+                                ("flags", "<u2"), ("min_dist_sq", "<i4"), ("reserved", "<i4")])
 # gie_ground_cell (16 bytes)
 GROUND_CELL_DTYPE = np.dtype([("dist_sq", "<i4"), ("coc", "<i4", (2,)), ("type", "i1"), ("inside", "u1"), ("pad", "u1", (2,))])
 GROUND_HIT_DTYPE = np.dtype([("first", "<i4"), ("len", "<i4"), ("hit", "<i4", (2,)), ("min_dist_sq", "<i4"), ("reserved", "<i4")])
@@ -786,6 +789,57 @@ class Mapper(MapperBase):
     def cloud_global_dev(self, d_out, d_count, type_mask, intensity=CLOUD_TYPE, z_lo=None, z_hi=None, max_points=0):
         p = self.cloud_param(type_mask, intensity, z_lo, z_hi, max_points)
         self._chk(self._f["cloud_global_dev"](self._h, C.byref(p), C.c_void_p(d_out or None), C.c_void_p(d_count or None)))
+
+    # --- global block summaries (include/gie.h) -------------------------------------------------
+    def blocks_param(self, lo=None, hi=None, dist=False, min_fnt=0, max_records=0):
+        """gie_blocks_param: lo / hi = BLOCK coordinates (global voxel >> 3), both inclusive; None, or None on an axis: open there."""
+        p = BlocksParam()
+        for k in range(3):
+            p.lo[k] = CLOUD_NO_BAND[0] if lo is None or lo[k] is None else int(lo[k])
+            p.hi[k] = CLOUD_NO_BAND[1] if hi is None or hi[k] is None else int(hi[k])
+        p.flags, p.min_fnt, p.max_records = BLOCKS_DIST if dist else 0, int(min_fnt), int(max_records)
+        return p
+
+    def blocks_summary(self, lo=None, hi=None, dist=False, min_fnt=0, max_records=None, grid=False, dev=False):
+        """One record per qualifying block of the global map with n_fnt >= min_fnt -> (records, count) or, with grid=True (a finite
+        box lo..hi), (records, count, grid): records = the written ones (BLOCK_SUMMARY_DTYPE, unspecified order), count = all of
+        them, also beyond max_records (None: count first, then fetch all), grid = uint32 [nz][ny][nx] over the box.  dev=True takes
+        the same through gie_blocks_summary_dev and torch buffers on the mapper's stream.  Synchronises."""
+        n = C.c_int32(0)
+        if max_records is None:
+            p = self.blocks_param(lo, hi, dist, min_fnt, 0)
+            self._chk(self._f["blocks_summary"](self._h, C.byref(p), None, C.byref(n), None))
+            max_records = n.value
+        max_records = int(max_records)
+        p = self.blocks_param(lo, hi, dist, min_fnt, max_records)
+        shape = tuple(int(p.hi[k]) - int(p.lo[k]) + 1 for k in (2, 1, 0)) if grid else None
+        if grid and not all(0 < s <= 1024 for s in shape):
+            raise ValueError("blocks_summary: a grid needs a finite box of at most 1024 blocks a side")
+        out = np.zeros(max(max_records, 0), BLOCK_SUMMARY_DTYPE)
+        g = np.zeros(shape, np.uint32) if grid else None
+        if dev:
+            import torch
+            d = torch.device("cuda", int(self.cfg.device_id))
+            with torch.cuda.stream(torch.cuda.ExternalStream(self.stream_handle(), device=d)):
+                dout = torch.zeros(max(out.nbytes, 16), dtype=torch.uint8, device=d)
+                dcnt = torch.zeros(1, dtype=torch.int32, device=d)
+                dg = torch.zeros(g.size, dtype=torch.int32, device=d) if grid else None
+                self.blocks_summary_dev(dout.data_ptr() if max_records > 0 else 0, dcnt.data_ptr(), dg.data_ptr() if grid else 0, lo, hi, dist, min_fnt, max_records)
+            self.sync()
+            n.value = int(dcnt.cpu()[0])
+            out = dout.cpu().numpy()[:out.nbytes].view(BLOCK_SUMMARY_DTYPE).copy()
+            if grid:
+                g = dg.cpu().numpy().view(np.uint32).reshape(shape)
+        else:
+            self._chk(self._f["blocks_summary"](self._h, C.byref(p), _ptr(out) if out.size else None, C.byref(n), _ptr(g)))
+        res = (out[:min(n.value, max_records)], n.value)
+        return res + (g,) if grid else res
+
+    def blocks_summary_dev(self, d_out, d_count, d_grid, lo=None, hi=None, dist=False, min_fnt=0, max_records=0):
+        """Records (max_records x 32 bytes, 16-byte aligned), the count (one int32) and the grid (one uint32 per cell of the box) in
+        DEVICE buffers (raw addresses; 0 = not wanted), on the mapper's stream without a host wait."""
+        p = self.blocks_param(lo, hi, dist, min_fnt, max_records)
+        self._chk(self._f["blocks_summary_dev"](self._h, C.byref(p), C.c_void_p(d_out or None), C.c_void_p(d_count or None), C.c_void_p(d_grid or None)))
 
     # --- ground costmap of a height band (include/gie.h) ---------------------------------------
     def ground_param(self, z_lo, z_hi, min_known=1, unknown_blocks=False):

@@ -66,6 +66,7 @@ struct Parameters {
     float ground_robot_radius = 0.f;     /* "ground/robot_radius" (metres): ground_plan() keeps ceil(radius / voxel_width) cells away from every obstacle column */
     float ground_footprint[3] = { -1.f, -1.f, -1.f };   /* "ground/footprint": front, back, half width (metres) of the robot's rectangle around its reference
                                                           * point, three numbers ("0.7 0.3 0.3" or "[0.7, 0.3, 0.3]"); unset (the default) while one is negative */
+    int explore_min_fnt = 1;             /* "explore/min_fnt": global_frontier_blocks() takes the blocks with at least this many FNT voxels (1..512) */
     bool profile_loc_rms = false, profile_glb_rms = false;
     std::string log_name = "GIE_log.csv";
     std::string data_case = "ugv_corridor";
@@ -125,6 +126,7 @@ struct Parameters {
         else if (k == "ground/min_height") ground_min_height = fl(); else if (k == "ground/max_height") ground_max_height = fl();
         else if (k == "ground/min_known") ground_min_known = in();
         else if (k == "ground/robot_radius") ground_robot_radius = fl();
+        else if (k == "explore/min_fnt") explore_min_fnt = in();
         else if (k == "ground/footprint") {
             std::string t = v;
             for (char &ch : t) if (ch == '[' || ch == ']' || ch == ',') ch = ' ';
@@ -390,6 +392,9 @@ struct Pose { float pos[3]; float quat_wxyz[4]; };
 /* what VOLMAPNODE::visualize publishes (volumetric_mapper.h:181-357): x, y, z in metres; intensity = the type (2) in the two OGM
  * clouds (the reference's global one is PointXYZ: ignore it there), the distance in metres in the two EDT clouds */
 struct DisplayClouds { std::vector<gie_cloud_point> loc_ogm, loc_edt, glb_ogm, glb_edt; };
+/* global_frontier_blocks(): a block of the global map that still holds frontier — the world position of its first FNT voxel, how many
+ * FNT voxels it has, the least squared distance (voxels) from its free space to an obstacle (GIE_EMPTY_VALUE: none known) */
+struct FrontierBlockGoal { float pos[3]; int32_t key[3]; int32_t n_fnt, min_dist_sq; };
 
 class VolumetricMapper {
 public:
@@ -967,6 +972,46 @@ public:
         return true;
     }
 #endif
+
+    /* Far exploration goals (include/gie.h "global block summaries"): the blocks of everything mapped so far — not of the local
+     * volume only — that hold at least min_fnt FNT voxels (below 1: explore/min_fnt), from ONE gie_blocks_summary call with
+     * GIE_BLOCKS_DIST (and one that counts).  Sorted by the squared block distance from the robot's block (its position of the last
+     * publishMap), ties by key (z, y, x); at most max_goals of them.  A goal's position is coord2pos of the block's fnt_voxel, the
+     * convention of the frontier clusters' goals.  Returns the number of such blocks (which may exceed max_goals). */
+    int global_frontier_blocks(int min_fnt, int max_goals, std::vector<FrontierBlockGoal> &goals)
+    {
+        gie_blocks_param p = {};
+        for (int i = 0; i < 3; i++) { p.lo[i] = std::numeric_limits<int32_t>::min(); p.hi[i] = std::numeric_limits<int32_t>::max(); }
+        p.flags = GIE_BLOCKS_DIST;
+        p.min_fnt = std::max(min_fnt < 1 ? param.explore_min_fnt : min_fnt, 1);
+        int32_t n = 0;
+        chk(gie_blocks_summary(m_, &p, nullptr, &n, nullptr));
+        std::vector<gie_block_summary> rec((size_t)n);
+        p.max_records = n;
+        if (n > 0) chk(gie_blocks_summary(m_, &p, rec.data(), &n, nullptr));
+        rec.resize((size_t)std::min<int32_t>(n, p.max_records));
+        const float w = cfg_.voxel_width;
+        int64_t rb[3];
+        for (int i = 0; i < 3; i++) rb[i] = (int64_t)((int32_t)std::floor(robot_pos_[i] / w + 0.5f) >> 3);      /* gie_pos2coord, in fp32; its block */
+        auto d2 = [&](const gie_block_summary &r) { int64_t s = 0; for (int i = 0; i < 3; i++) { const int64_t d = (int64_t)r.key[i] - rb[i]; s += d * d; } return s; };
+        std::sort(rec.begin(), rec.end(), [&](const gie_block_summary &a, const gie_block_summary &b) {
+            const int64_t da = d2(a), db = d2(b);
+            if (da != db) return da < db;
+            if (a.key[2] != b.key[2]) return a.key[2] < b.key[2];
+            if (a.key[1] != b.key[1]) return a.key[1] < b.key[1];
+            return a.key[0] < b.key[0];
+        });
+        goals.clear();
+        for (size_t i = 0; i < rec.size() && (int)i < max_goals; i++) {
+            const gie_block_summary &r = rec[i];
+            const int v[3] = { r.fnt_voxel >> 6, (r.fnt_voxel >> 3) & 7, r.fnt_voxel & 7 };
+            FrontierBlockGoal g;
+            for (int k = 0; k < 3; k++) { g.key[k] = r.key[k]; g.pos[k] = (float)(r.key[k] * 8 + v[k]) * w; }
+            g.n_fnt = r.n_fnt; g.min_dist_sq = r.min_dist_sq;
+            goals.push_back(g);
+        }
+        return n;
+    }
 
     /* VOLMAPNODE::visualize without the publishers: the clouds the display flags ask for (the others come back empty), of the map as
      * it stands.  sensor_pos is the reference's argument: its z is replaced by vis_height before the slice's z is taken

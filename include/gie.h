@@ -623,6 +623,69 @@ int gie_cloud_local_dev(gie_mapper *h, const gie_cloud_param *p, gie_cloud_point
 int gie_cloud_global(gie_mapper *h, const gie_cloud_param *p, gie_cloud_point *out, int32_t *count);
 int gie_cloud_global_dev(gie_mapper *h, const gie_cloud_param *p, gie_cloud_point *d_out, int32_t *d_count);
 
+/* ---- global block summaries: one record per 8 x 8 x 8 block of everything mapped so far, for an exploration planner.  Every planner
+ * section above answers questions about the local volume, which moves with the robot; a frontier the robot drove past stays in the
+ * global map (g_type keeps GIE_VOX_FNT once the voxel has left the volume) and only gie_query_global (which must know where to
+ * look), the display clouds (16 bytes per VOXEL) or the changed-block stream and a CPU mirror can see it.  This is gie_cloud_global's
+ * definition at block resolution: a pure reduction over the block pool.  No counterpart in the reference's code.
+ *
+ * A block has the coordinate k = (global voxel >> 3) on every axis (arithmetic shift: voxel -1 lies in block -1).
+ *  which voxels   every voxel g of every LIVE block of the pool, as in gie_cloud_global: the block's slot below the number handed
+ *                 out and its key not erased (gie_config.retain_radius_blocks); an empty pool has none.  With r = the record
+ *                 gie_query_global returns for g at the point of the mapper's stream where the call is enqueued (the records a
+ *                 fused update has left to the pair plane included; the call stores nothing):
+ *                   n_free, n_occupied, n_fnt   the number of the block's voxels with r.vox_type FREE, OCCUPIED, FNT (0..512 each;
+ *                                               UNKNOWN = 512 - their sum);
+ *                   fnt_voxel                   the least in-block index (g_x & 7) * 64 + (g_y & 7) * 8 + (g_z & 7) — the order of
+ *                                               gie_stream_changed's blocks — of an FNT voxel, 0xffff when there is none;
+ *                   free_voxel                  the same over the FREE and FNT voxels;
+ *                   min_dist_sq                 with GIE_BLOCKS_DIST the least r.dist_sq over the block's FREE and FNT voxels with
+ *                                               0 <= r.dist_sq < 900000 (the display clouds' validity test); GIE_EMPTY_VALUE when
+ *                                               there is none or the flag is off;
+ *                   flags                       the call's flags; reserved 0.
+ *  which blocks   a block QUALIFIES iff it holds at least one known voxel (n_free + n_occupied + n_fnt > 0: whether a block without
+ *                 one has been allocated is not observable) and lo_k <= k <= hi_k on every axis (INT32_MIN / INT32_MAX: open on
+ *                 that side).
+ *  list           *count = the number of qualifying blocks with n_fnt >= min_fnt, also when it exceeds max_records.  Exactly
+ *                 min(count, max_records) records are written: distinct such blocks in unspecified order — which ones, when they do
+ *                 not all fit, is unspecified too; entries beyond them are left as they were.  max_records == 0 with a NULL out only
+ *                 counts.  A NULL count with a non-NULL out is allowed (the caller then cannot tell how many were written).
+ *  grid           optional (NULL: none).  It needs a finite box, every side hi_k - lo_k + 1 <= 1024 and at most 2^24 cells in all;
+ *                 cell ((k_z - lo_z) * ny + (k_y - lo_y)) * nx + (k_x - lo_x), x fastest.  EVERY cell is written: 0 where there is no
+ *                 qualifying block, otherwise 1u << 31 | n_fnt << 20 | n_occupied << 10 | n_free (a count reaches 512, which ten
+ *                 bits hold).  The grid ignores min_fnt.
+ * GIE_ERR_INVALID: a NULL param; lo > hi on an axis; flags other than 0 or GIE_BLOCKS_DIST; min_fnt outside 0..512; max_records < 0;
+ * non-zero reserved; a NULL out with max_records > 0; a NULL count together with a NULL out and a NULL grid; a grid with a box that
+ * is open on a side, longer than 1024 blocks on a side or larger than 2^24 cells; a tiled mapper (its pool holds ghost blocks of
+ * other tiles: refused, as by every planner section); in the _dev form a d_out that is not 16-byte aligned.  Nothing is written then.
+ * The host form stages through the two scratch slots of the host forms and synchronises, like the display clouds.  The _dev form
+ * takes DEVICE buffers and is enqueued on the mapper's stream with no host wait and no read-back: d_count and d_grid are zeroed on
+ * the stream and written in place; at most two memsets and one launch, no grid barrier.  A call is legal wherever gie_query_global
+ * is: before the first gie_set_pose too (an empty pool: count 0, a grid of zeros) and between gie_fuse and gie_merge of one update.
+ * Map updates are not changed by it; a mapper that never calls it allocates and launches nothing (a _dev call with d_out but
+ * without d_count uses the display clouds' counter word).
+ * Cost: a key and 512 bytes per live block; GIE_BLOCKS_DIST 8 bytes more per FREE or FNT voxel; 32 bytes per record.
+ * gie_profile_read has no entry for it. */
+#define GIE_BLOCKS_DIST 1            /* flags: also reduce the distances */
+typedef struct gie_blocks_param {    /* 48 bytes */
+    int32_t lo[3], hi[3];   /* box of BLOCK coordinates (global voxel >> 3, arithmetic), both inclusive; INT32_MIN / INT32_MAX = open */
+    int32_t flags;          /* 0 or GIE_BLOCKS_DIST */
+    int32_t min_fnt;        /* 0..512: a RECORD is written only for a block with n_fnt >= min_fnt (the grid ignores it) */
+    int32_t max_records;    /* >= 0: capacity of `out` */
+    int32_t reserved[3];    /* 0 */
+} gie_blocks_param;
+typedef struct gie_block_summary {   /* 32 bytes */
+    int32_t  key[3];        /* block coordinate */
+    uint16_t n_free, n_occupied, n_fnt;   /* voxels of the block by type; UNKNOWN = 512 - their sum */
+    uint16_t fnt_voxel;     /* least in-block index (x&7)*64 + (y&7)*8 + (z&7) (gie_stream_changed's order) of an FNT voxel; 0xffff: none */
+    uint16_t free_voxel;    /* the same over FREE and FNT voxels; 0xffff: none */
+    uint16_t flags;         /* the call's flags */
+    int32_t  min_dist_sq;   /* GIE_BLOCKS_DIST: least dist_sq over the block's FREE / FNT voxels with 0 <= dist_sq < 900000; GIE_EMPTY_VALUE when there is none or the flag is off */
+    int32_t  reserved;      /* 0 */
+} gie_block_summary;
+int gie_blocks_summary(gie_mapper *h, const gie_blocks_param *p, gie_block_summary *out, int32_t *count, uint32_t *grid);
+int gie_blocks_summary_dev(gie_mapper *h, const gie_blocks_param *p, gie_block_summary *d_out, int32_t *d_count, uint32_t *d_grid);
+
 /* ---- ground costmap: the footprint of a height band of the local volume and its exact 2-D distance transform, for ground and
  * planar robots (the reference's ugv_height set-ups: cfg/ugv_laser3D_params.yaml, cfg/scan2D_params.yaml).  A body that occupies a
  * band of z needs a 2-D grid — which cells are blocked, how far each is from the nearest blocked one — and neither the 3-D EDT nor
