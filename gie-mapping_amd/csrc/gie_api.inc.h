@@ -138,6 +138,17 @@ struct gie_gcm_cache {
     uint64_t *planes = nullptr;           /* fields beyond the LDS budget: two bit planes per source, planes_n sources */
     int planes_n = 0;
 };
+/* the global block routes (gie_routes.inc.h): allocated at the first compute through be_alloc, grown when a later box is larger,
+ * kept with their box until the next compute */
+struct gie_routes_cache {
+    uint8_t *bytes = nullptr;             /* two planes of cap_cells bytes: the raw cell bytes and the final ones */
+    int32_t *f = nullptr;                 /* the field, cap_cells */
+    uint64_t *bits = nullptr;             /* five bit planes of cap_words words */
+    int32_t *info = nullptr;              /* gie_routes_info */
+    size_t cap_cells = 0, cap_words = 0;
+    int valid = 0;                        /* a compute has been enqueued */
+    int lo[3] = { 0, 0, 0 }, dim[3] = { 0, 0, 0 };   /* the box of that compute */
+};
 struct gie_mapper {
     gie_config cfg;
     gie_ctx c;
@@ -184,6 +195,7 @@ struct gie_mapper {
     gie_gcm_cache gcm;                    /* the ground cost matrix's scratch (HIP backend: gie_ground_costmat.inc.h) */
     uint64_t *gview_opq = nullptr;        /* ground view gain (HIP backend: gie_ground_view.inc.h): the opaque bit plane, allocated at the first call and rebuilt by every call */
     gie_costmat_cache costmat;            /* the cost matrix's scratch (HIP backend: gie_costmat.inc.h) */
+    gie_routes_cache routes;              /* the global block routes (HIP backend: gie_routes.inc.h) */
     int32_t *cloud_count = nullptr;       /* display clouds (HIP backend: gie_cloud.inc.h): the counter of a _dev call that passes none, allocated at the first such call */
 };
 

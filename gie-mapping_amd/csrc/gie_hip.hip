@@ -607,3 +607,4 @@ extern "C" int gie_debug_edt_hint(gie_mapper *m, int force, int32_t *info)
 #include "gie_ground_footprint.inc.h"
 #include "gie_ground_pose_nf1.inc.h"
 #include "gie_ground_sdf.inc.h"
+#include "gie_routes.inc.h"

@@ -134,6 +134,18 @@ class BlockSummary(C.Structure):
                 ("free_voxel", C.c_uint16), ("flags", C.c_uint16), ("min_dist_sq", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RoutesParam(C.Structure):
+    """gie_routes_param (include/gie.h): 48 bytes."""
+    _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("min_free", C.c_int32), ("min_open", C.c_int32), ("min_fnt", C.c_int32),
+                ("flags", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class RoutesInfo(C.Structure):
+    """gie_routes_info (include/gie.h): 32 bytes."""
+    _fields_ = [("n_nodes", C.c_int32), ("n_links", C.c_int32), ("n_frontier", C.c_int32), ("n_sources", C.c_int32), ("n_reached", C.c_int32),
+                ("max_steps", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class GroundParam(C.Structure):
     """gie_ground_param (include/gie.h): 32 bytes."""
     _fields_ = [("z_lo", C.c_int32), ("z_hi", C.c_int32), ("min_known", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
@@ -243,6 +255,7 @@ LOS_UNKNOWN_OPAQUE = 1
 CLOUD_TYPE = 0
 CLOUD_DIST = 1
 BLOCKS_DIST = 1
+ROUTES_FROM_FRONTIERS = 1
 GROUND_UNKNOWN_BLOCKS = 1
 GROUND_NF1_UNKNOWN_TRAVERSABLE = 1
 GROUND_NF1_FROM_FRONTIERS = 2
@@ -394,6 +407,15 @@ DEVICE_ONLY = {
     # global block summaries: counts, frontier blocks and a coarse grid out of the block pool (include/gie.h): device library only
     "blocks_summary": (C.c_int, [_H, C.POINTER(BlocksParam), C.c_void_p, C.c_void_p, C.c_void_p]),
     "blocks_summary_dev": (C.c_int, [_H, C.POINTER(BlocksParam), C.c_void_p, C.c_void_p, C.c_void_p]),
+    # global block routes: face links between blocks and a BFS field on the block grid (include/gie.h): device library only
+    "routes_compute": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(RoutesParam), C.c_void_p]),
+    "routes_compute_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.POINTER(RoutesParam), C.c_void_p]),
+    "read_routes": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
+    "read_routes_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
+    "routes_query": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p]),
+    "routes_query_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p]),
+    "routes_path": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "routes_path_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     # ground costmap of a height band of the local volume (include/gie.h): device library only
     "ground_compute": (C.c_int, [_H, C.POINTER(GroundParam), C.c_void_p]),
     "ground_compute_dev": (C.c_int, [_H, C.POINTER(GroundParam), C.c_void_p]),

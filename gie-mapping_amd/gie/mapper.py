@@ -13,8 +13,8 @@ import sys
 import numpy as np
 
 from . import _capi
-from ._capi import BLOCKS_DIST, CLOUD_DIST, CLOUD_TYPE, GROUND_POSE_HEADINGS, GROUND_POSE_MAX_SQ, GROUND_POSE_NF1_FROM_FRONTIERS, GROUND_POSE_NF1_REVERSE, GROUND_POSE_NF1_UNKNOWN_TRAVERSABLE, GROUND_FOOTPRINT_MARGIN, GROUND_FOOTPRINT_MAX_SQ, GROUND_FOOTPRINT_UNKNOWN_TRAVERSABLE, GROUND_LOS_UNKNOWN_TRAVERSABLE, GROUND_NF1_FROM_FRONTIERS, GROUND_NF1_UNKNOWN_TRAVERSABLE, GROUND_ROLLOUT_MAX_POSES, GROUND_ROLLOUT_NF1, GROUND_ROLLOUT_UNKNOWN_TRAVERSABLE, GROUND_UNKNOWN_BLOCKS, GROUND_VIEW_UNION, GROUND_VIEW_UNKNOWN_OPAQUE, LOS_UNKNOWN_OPAQUE, NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE, VOX_FNT, VOX_FREE, VOX_OCCUPIED, VOX_UNKNOWN
-from ._capi import BlocksParam, CamParam, CloudParam, Config, CostMapHdr, FrameStats, FrontierParam, GroundFootprintParam, GroundFrontierParam, GroundLosParam, GroundNf1Param, GroundParam, GroundPoseNf1Param, GroundRolloutParam, GroundSdfRolloutParam, GroundShortcutParam, GroundViewParam, LosParam, MultiScanParam, Nf1Param, ScanParam, ShortcutParam, ViewParam, Voxel
+from ._capi import BLOCKS_DIST, CLOUD_DIST, CLOUD_TYPE, GROUND_POSE_HEADINGS, GROUND_POSE_MAX_SQ, GROUND_POSE_NF1_FROM_FRONTIERS, GROUND_POSE_NF1_REVERSE, GROUND_POSE_NF1_UNKNOWN_TRAVERSABLE, GROUND_FOOTPRINT_MARGIN, GROUND_FOOTPRINT_MAX_SQ, GROUND_FOOTPRINT_UNKNOWN_TRAVERSABLE, GROUND_LOS_UNKNOWN_TRAVERSABLE, GROUND_NF1_FROM_FRONTIERS, GROUND_NF1_UNKNOWN_TRAVERSABLE, GROUND_ROLLOUT_MAX_POSES, GROUND_ROLLOUT_NF1, GROUND_ROLLOUT_UNKNOWN_TRAVERSABLE, GROUND_UNKNOWN_BLOCKS, GROUND_VIEW_UNION, GROUND_VIEW_UNKNOWN_OPAQUE, LOS_UNKNOWN_OPAQUE, NF1_FROM_FRONTIERS, NF1_UNKNOWN_TRAVERSABLE, ROUTES_FROM_FRONTIERS, VOX_FNT, VOX_FREE, VOX_OCCUPIED, VOX_UNKNOWN
+from ._capi import BlocksParam, CamParam, CloudParam, Config, CostMapHdr, FrameStats, FrontierParam, GroundFootprintParam, GroundFrontierParam, GroundLosParam, GroundNf1Param, GroundParam, GroundPoseNf1Param, GroundRolloutParam, GroundSdfRolloutParam, GroundShortcutParam, GroundViewParam, LosParam, MultiScanParam, Nf1Param, RoutesInfo, RoutesParam, ScanParam, ShortcutParam, ViewParam, Voxel
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG, "csrc", "libgie_hip.so")
@@ -38,6 +38,10 @@ CLOUD_NO_BAND = (-2 ** 31, 2 ** 31 - 1)
 # gie_block_summary (32 bytes)
 BLOCK_SUMMARY_DTYPE = np.dtype([("key", "<i4", (3,)), ("n_free", "<u2"), ("n_occupied", "<u2"), ("n_fnt", "<u2"), ("fnt_voxel", "<u2"), ("free_voxel", "<u2"),
                                 ("flags", "<u2"), ("min_dist_sq", "<i4"), ("reserved", "<i4")])
+# gie_routes_param (48 bytes), gie_routes_info (32 bytes)
+ROUTES_PARAM = np.dtype([("lo", "<i4", (3,)), ("hi", "<i4", (3,)), ("min_free", "<i4"), ("min_open", "<i4"), ("min_fnt", "<i4"), ("flags", "<i4"), ("reserved", "<i4", (2,))])
+ROUTES_INFO = np.dtype([("n_nodes", "<i4"), ("n_links", "<i4"), ("n_frontier", "<i4"), ("n_sources", "<i4"), ("n_reached", "<i4"), ("max_steps", "<i4"),
+                        ("reserved", "<i4", (2,))])
 # gie_ground_cell (16 bytes)
 GROUND_CELL_DTYPE = np.dtype([("dist_sq", "<i4"), ("coc", "<i4", (2,)), ("type", "i1"), ("inside", "u1"), ("pad", "u1", (2,))])
 GROUND_HIT_DTYPE = np.dtype([("first", "<i4"), ("len", "<i4"), ("hit", "<i4", (2,)), ("min_dist_sq", "<i4"), ("reserved", "<i4")])
@@ -840,6 +844,76 @@ class Mapper(MapperBase):
         DEVICE buffers (raw addresses; 0 = not wanted), on the mapper's stream without a host wait."""
         p = self.blocks_param(lo, hi, dist, min_fnt, max_records)
         self._chk(self._f["blocks_summary_dev"](self._h, C.byref(p), C.c_void_p(d_out or None), C.c_void_p(d_count or None), C.c_void_p(d_grid or None)))
+
+    # --- global block routes (include/gie.h) ----------------------------------------------------
+    def routes_param(self, lo, hi, min_free=1, min_open=1, min_fnt=1, from_frontiers=False):
+        """gie_routes_param: lo / hi = a finite box of BLOCK coordinates (global voxel >> 3), both inclusive."""
+        p = RoutesParam()
+        for k in range(3):
+            p.lo[k] = CLOUD_NO_BAND[0] if lo is None or lo[k] is None else int(lo[k])
+            p.hi[k] = CLOUD_NO_BAND[1] if hi is None or hi[k] is None else int(hi[k])
+        p.min_free, p.min_open, p.min_fnt, p.flags = int(min_free), int(min_open), int(min_fnt), ROUTES_FROM_FRONTIERS if from_frontiers else 0
+        return p
+
+    def routes_compute(self, lo, hi, goals=(), min_free=1, min_open=1, min_fnt=1, from_frontiers=False):
+        """Links and BFS field of the blocks of the box lo..hi from goal points (n x 3 metres, world frame) and / or the frontier
+        blocks; the result is kept until the next compute.  Returns the info record (ROUTES_INFO scalar; synchronises)."""
+        g = np.ascontiguousarray(np.asarray(goals, dtype=np.float32).reshape(-1, 3))
+        p = self.routes_param(lo, hi, min_free, min_open, min_fnt, from_frontiers)
+        info = np.zeros(1, ROUTES_INFO)
+        self._chk(self._f["routes_compute"](self._h, _ptr(g) if g.shape[0] else None, g.shape[0], C.byref(p), _ptr(info)))
+        self._routes_shape = tuple(int(p.hi[k]) - int(p.lo[k]) + 1 for k in (2, 1, 0))
+        return info[0]
+
+    def routes_compute_dev(self, d_goals, n, lo, hi, min_free=1, min_open=1, min_fnt=1, from_frontiers=False, d_info=0):
+        """The same on the mapper's stream without a host wait; goals (n x 3 float32) and the info record (32 bytes; 0 = not wanted)
+        in DEVICE buffers (raw addresses)."""
+        p = self.routes_param(lo, hi, min_free, min_open, min_fnt, from_frontiers)
+        self._chk(self._f["routes_compute_dev"](self._h, C.c_void_p(d_goals or None), int(n), C.byref(p), C.c_void_p(d_info or None)))
+        self._routes_shape = tuple(int(p.hi[k]) - int(p.lo[k]) + 1 for k in (2, 1, 0))
+
+    def routes_read(self):
+        """(steps int32 [nz][ny][nx], cell bytes uint8 [nz][ny][nx]) of the kept box (synchronises)."""
+        shape = getattr(self, "_routes_shape", None)
+        if shape is None:
+            raise RuntimeError("routes_read: no routes yet (routes_compute first)")
+        steps, cells = np.empty(shape, np.int32), np.empty(shape, np.uint8)
+        self._chk(self._f["read_routes"](self._h, _ptr(steps), _ptr(cells)))
+        return steps, cells
+
+    def routes_read_dev(self, d_steps, d_cells):
+        """The field (int32 per cell) and the cell bytes into DEVICE buffers (raw addresses; 0 = not wanted), on the mapper's stream."""
+        self._chk(self._f["read_routes_dev"](self._h, C.c_void_p(d_steps or None), C.c_void_p(d_cells or None)))
+
+    def routes_query(self, xyz):
+        """The kept field at the blocks of n points (n x 3 metres, world frame): int32 [n] steps, -1 outside the box, for a point
+        that is not finite, on a cell without a node and where no source is reachable (synchronises)."""
+        xyz = np.ascontiguousarray(np.asarray(xyz, dtype=np.float32).reshape(-1, 3))
+        out = np.zeros(xyz.shape[0], np.int32)
+        self._chk(self._f["routes_query"](self._h, _ptr(xyz) if len(xyz) else None, len(xyz), _ptr(out) if len(xyz) else None))
+        return out
+
+    def routes_query_dev(self, d_xyz, n, d_steps):
+        """n points (n x 3 float32) and their steps (n int32) in DEVICE buffers (raw addresses), on the mapper's stream."""
+        self._chk(self._f["routes_query_dev"](self._h, C.c_void_p(d_xyz or None), int(n), C.c_void_p(d_steps or None)))
+
+    def routes_path(self, starts, max_len, path=None):
+        """Descents from n start points (n x 3 metres): (path [n, max_len, 3] int32 BLOCK coordinates, len [n] int32 = steps + 1, 0
+        without a path).  Only the first min(len, max_len) blocks of a path are written: the rest is zero, or what the caller's
+        `path` held (synchronises)."""
+        xyz = np.ascontiguousarray(np.asarray(starts, dtype=np.float32).reshape(-1, 3))
+        n, max_len = xyz.shape[0], int(max_len)
+        if path is None:
+            path = np.zeros((n, max(max_len, 1), 3), np.int32)
+        elif path.dtype != np.int32 or path.shape != (n, max_len, 3) or not path.flags.c_contiguous:
+            raise ValueError("routes_path: path must be a contiguous (n, max_len, 3) int32 array")
+        ln = np.zeros(n, np.int32)
+        self._chk(self._f["routes_path"](self._h, _ptr(xyz) if n else None, n, max_len, _ptr(path) if n else None, _ptr(ln) if n else None))
+        return path, ln
+
+    def routes_path_dev(self, d_starts, n, max_len, d_path, d_len):
+        """n starts (n x 3 float32), keys (n x max_len x 3 int32) and lengths (n int32) in DEVICE buffers, on the mapper's stream."""
+        self._chk(self._f["routes_path_dev"](self._h, C.c_void_p(d_starts or None), int(n), int(max_len), C.c_void_p(d_path or None), C.c_void_p(d_len or None)))
 
     # --- ground costmap of a height band (include/gie.h) ---------------------------------------
     def ground_param(self, z_lo, z_hi, min_known=1, unknown_blocks=False):

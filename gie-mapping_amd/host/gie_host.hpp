@@ -67,6 +67,8 @@ struct Parameters {
     float ground_footprint[3] = { -1.f, -1.f, -1.f };   /* "ground/footprint": front, back, half width (metres) of the robot's rectangle around its reference
                                                           * point, three numbers ("0.7 0.3 0.3" or "[0.7, 0.3, 0.3]"); unset (the default) while one is negative */
     int explore_min_fnt = 1;             /* "explore/min_fnt": global_frontier_blocks() takes the blocks with at least this many FNT voxels (1..512) */
+    int explore_route_min_free = 1;      /* "explore/route_min_free": global_frontier_routes() takes a block as a node with at least this many passable voxels (1..512) */
+    int explore_route_min_open = 1;      /* "explore/route_min_open": ... and joins two blocks across a face with at least this many open voxel pairs (1..64) */
     bool profile_loc_rms = false, profile_glb_rms = false;
     std::string log_name = "GIE_log.csv";
     std::string data_case = "ugv_corridor";
@@ -127,6 +129,8 @@ struct Parameters {
         else if (k == "ground/min_known") ground_min_known = in();
         else if (k == "ground/robot_radius") ground_robot_radius = fl();
         else if (k == "explore/min_fnt") explore_min_fnt = in();
+        else if (k == "explore/route_min_free") explore_route_min_free = in();
+        else if (k == "explore/route_min_open") explore_route_min_open = in();
         else if (k == "ground/footprint") {
             std::string t = v;
             for (char &ch : t) if (ch == '[' || ch == ']' || ch == ',') ch = ' ';
@@ -395,6 +399,9 @@ struct DisplayClouds { std::vector<gie_cloud_point> loc_ogm, loc_edt, glb_ogm, g
 /* global_frontier_blocks(): a block of the global map that still holds frontier — the world position of its first FNT voxel, how many
  * FNT voxels it has, the least squared distance (voxels) from its free space to an obstacle (GIE_EMPTY_VALUE: none known) */
 struct FrontierBlockGoal { float pos[3]; int32_t key[3]; int32_t n_fnt, min_dist_sq; };
+/* global_frontier_routes(): the same with the number of block links of the shortest route from the robot's block (include/gie.h
+ * "global block routes"); -1: no route through mapped space */
+struct FrontierRouteGoal : FrontierBlockGoal { int32_t steps; };
 
 class VolumetricMapper {
 public:
@@ -1008,6 +1015,56 @@ public:
             FrontierBlockGoal g;
             for (int k = 0; k < 3; k++) { g.key[k] = r.key[k]; g.pos[k] = (float)(r.key[k] * 8 + v[k]) * w; }
             g.n_fnt = r.n_fnt; g.min_dist_sq = r.min_dist_sq;
+            goals.push_back(g);
+        }
+        return n;
+    }
+
+    /* The far exploration goals by ROUTE (include/gie.h "global block routes"): the goals of global_frontier_blocks(0, max_goals)
+     * (explore/min_fnt), then ONE gie_routes_compute with the robot's position as the only goal and ONE gie_routes_query at the goals'
+     * positions.  Nodes and links by explore/route_min_free and explore/route_min_open.  The box is the bounding box of the goals' keys
+     * and the robot's block, widened by one block; if that exceeds the stage's size limit (16384 words of 64 cells a plane) it is cut
+     * to the robot's block +- h on every axis, h halving from the longest reach of the box until it fits — goals beyond it are then
+     * unreachable by definition.  The goals come ordered by steps, ascending; the unreachable ones (steps -1) last; ties, and the
+     * unreachable among themselves, stay in global_frontier_blocks' straight-line order.  Returns its count of frontier blocks. */
+    int global_frontier_routes(int max_goals, std::vector<FrontierRouteGoal> &goals)
+    {
+        std::vector<FrontierBlockGoal> far;
+        const int n = global_frontier_blocks(0, max_goals, far);
+        const float w = cfg_.voxel_width;
+        gie_routes_param p = {};
+        int64_t rb[3], lo[3], hi[3];
+        for (int i = 0; i < 3; i++) {
+            rb[i] = (int64_t)((int32_t)std::floor(robot_pos_[i] / w + 0.5f) >> 3);      /* gie_pos2coord, in fp32; its block */
+            lo[i] = hi[i] = rb[i];
+            for (const FrontierBlockGoal &g : far) { lo[i] = std::min<int64_t>(lo[i], g.key[i]); hi[i] = std::max<int64_t>(hi[i], g.key[i]); }
+            lo[i] -= 1; hi[i] += 1;
+        }
+        auto words = [&]() { return ((hi[0] - lo[0] + 1 + 63) / 64) * (hi[1] - lo[1] + 1) * (hi[2] - lo[2] + 1); };
+        int64_t h = 0;
+        for (int i = 0; i < 3; i++) h = std::max(h, std::max(rb[i] - lo[i], hi[i] - rb[i]));
+        while (words() > 16384) {
+            h /= 2;
+            for (int i = 0; i < 3; i++) { lo[i] = std::max(lo[i], rb[i] - h); hi[i] = std::min(hi[i], rb[i] + h); }
+        }
+        for (int i = 0; i < 3; i++) { p.lo[i] = (int32_t)lo[i]; p.hi[i] = (int32_t)hi[i]; }
+        p.min_free = param.explore_route_min_free; p.min_open = param.explore_route_min_open; p.min_fnt = std::max(param.explore_min_fnt, 1);
+        chk(gie_routes_compute(m_, robot_pos_, 1, &p, nullptr));
+        std::vector<float> xyz(3 * far.size());
+        std::vector<int32_t> steps(far.size(), -1);
+        for (size_t i = 0; i < far.size(); i++) for (int k = 0; k < 3; k++) xyz[3 * i + k] = far[i].pos[k];
+        if (!far.empty()) chk(gie_routes_query(m_, xyz.data(), (int)far.size(), steps.data()));
+        std::vector<size_t> order(far.size());
+        for (size_t i = 0; i < order.size(); i++) order[i] = i;
+        std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+            const int64_t sa = steps[a] < 0 ? std::numeric_limits<int64_t>::max() : steps[a], sb = steps[b] < 0 ? std::numeric_limits<int64_t>::max() : steps[b];
+            return sa < sb;
+        });
+        goals.clear();
+        for (size_t i : order) {
+            FrontierRouteGoal g;
+            static_cast<FrontierBlockGoal &>(g) = far[i];
+            g.steps = steps[i];
             goals.push_back(g);
         }
         return n;

@@ -686,6 +686,80 @@ typedef struct gie_block_summary {   /* 32 bytes */
 int gie_blocks_summary(gie_mapper *h, const gie_blocks_param *p, gie_block_summary *out, int32_t *count, uint32_t *grid);
 int gie_blocks_summary_dev(gie_mapper *h, const gie_blocks_param *p, gie_block_summary *d_out, int32_t *d_count, uint32_t *d_grid);
 
+/* ---- global block routes: face links between the blocks of everything mapped so far and a BFS field on the block grid.  The block
+ * summaries above order far frontier by straight-line distance; this section says whether a block outside the local volume can be
+ * reached through mapped space, how many blocks the route has and through which blocks it goes: the global counterpart of
+ * gie_nf1_* and gie_ground_nf1_*.  No counterpart in the reference's code.
+ *
+ * Everything is an integer and exact.  r(g) = the record gie_query_global returns for global voxel g at the point of the mapper's
+ * stream where gie_routes_compute* is enqueued.  passable(g) iff r(g).vox_type is GIE_VOX_FREE or GIE_VOX_FNT.  Block k holds the
+ * voxels with g >> 3 == k (arithmetic shift on every axis: voxel -1 lies in block -1).  The call takes a finite box lo..hi of block
+ * coordinates; its cells are nx x ny x nz, cell ((k_z - lo_z) * ny + (k_y - lo_y)) * nx + (k_x - lo_x), x fastest, as in
+ * gie_blocks_summary's grid.  e_a = the unit step on axis a.
+ *  node(k)       k lies inside the box and at least min_free of its 512 voxels are passable.
+ *  pairs(k, a)   a in x, y, z: the number of the 64 voxel pairs (u, u + e_a) with u in block k at in-block coordinate 7 on axis a
+ *                (so u + e_a lies in block k + e_a at coordinate 0) and both passable.
+ *  link(k, a)    node(k), node(k + e_a) and pairs(k, a) >= min_open.  Links are undirected.  A link whose other end lies outside
+ *                the box does not exist.
+ *  frontier(k)   node(k) and the block has at least min_fnt FNT voxels.
+ *  sources       the nodes among: the block of each goal point (metres, world frame: gie_pos2coord per axis, then >> 3; a point
+ *                that is not finite or whose block lies outside the box is ignored, the mapping of gie_nf1_compute's goals) and,
+ *                with GIE_ROUTES_FROM_FRONTIERS, every frontier block.  A goal on a block that is no node is ignored.
+ *  steps(k)      int32: for a node joined to a source by a path of links, the number of links of the shortest such path (sources
+ *                0); -1 for every other cell.
+ *  cell byte     bit 0 node, bits 1 / 2 / 3 link(k, x / y / z), bit 4 frontier, bit 5 source; 0 for a cell without a node.
+ * THE GRAPH IS OPTIMISTIC BY CONSTRUCTION: a block is one node, so a wall that runs through the INSIDE of a block does not cut it —
+ * two faces of a block are joined whenever both have links, whether or not free space joins them inside.  That is the stated
+ * approximation of a coarse router; the local stages (gie_nf1_*, gie_los_*) resolve the rest once the robot is there.  A wall lying
+ * ON a block face (the voxels at coordinate 7 or those at coordinate 0 beyond it) is seen exactly.
+ *
+ *  gie_routes_compute*   builds cell bytes and field and keeps them, with their box, until the next compute.  n == 0 is valid; info
+ *                        may be NULL.  n_reached counts the cells with steps >= 0, max_steps is the largest value (-1 without a
+ *                        source).  n_links counts every link once.
+ *  gie_read_routes*      the int32 field and the byte plane of the kept box (nx * ny * nz entries each); either pointer may be NULL,
+ *                        not both.
+ *  gie_routes_query*     steps of the blocks of n points (3 floats each, the goals' mapping): -1 for a point that is not finite,
+ *                        outside the box, on a cell without a node or unreachable.  With the positions of
+ *                        gie_blocks_summary's records this reads the route length to every far frontier block in one call.
+ *  gie_routes_path*      one descent per start, in gie_nf1_path's form.  len = 0 when the start's block is outside the box (or the
+ *                        point not finite) or has steps < 0.  Otherwise the blocks k_0 .. k_s with s = steps(k_0): k_{i+1} is the
+ *                        first neighbour of k_i in the order -x +x -y +y -z +z that is joined to k_i by a link and has
+ *                        steps(k_i) - 1.  path_key holds max_len block coordinates (3 int32) per start; min(len, max_len) are
+ *                        written, entries beyond them are left as they were; len = s + 1 also when that exceeds max_len.
+ * Size limit: with W = ceil(nx / 64) a bit plane has W * ny * nz 64-bit words; at most 16384 words (1 048 576 cells at nx = 128:
+ * 128 x 128 x 64 blocks = 1024 x 1024 x 512 voxels).
+ * GIE_ERR_INVALID, with nothing written: a NULL param; lo > hi on an axis; a side that is open (INT32_MIN / INT32_MAX); min_free
+ * outside 1..512, min_open outside 1..64, min_fnt outside 1..512; non-zero reserved; unknown flags; n < 0; NULL points with n > 0; a
+ * box over the size limit; read / query / path before the first compute, with max_len < 1 or with NULL arrays and n > 0; a tiled
+ * mapper, for every call (its pool holds ghost blocks of other tiles).
+ * The calls are legal wherever gie_query_global is: before the first gie_set_pose (an empty pool: every cell 0, the field -1) and
+ * between gie_fuse and gie_merge of one update.  The stage writes nothing of the map; a mapper that never computes allocates and
+ * launches nothing; memory is allocated at the first compute and grown when a later box is larger.  The host forms stage through
+ * the scratch slots and synchronise; the _dev forms take DEVICE buffers and are enqueued on the mapper's stream with no host wait:
+ * two memsets and three or four launches per compute (the propagation is ONE workgroup: no grid barrier, no cooperative launch).
+ * Cost: a key and 512 bytes per live block inside the box plus 64 bytes of each of the three faces beyond it; 6 bytes per cell and
+ * 5 bits per cell of planes.  gie_profile_read has no entry for it. */
+#define GIE_ROUTES_FROM_FRONTIERS 1        /* flags: every frontier block is a source */
+typedef struct gie_routes_param {          /* 48 bytes */
+    int32_t lo[3], hi[3];                  /* finite box of BLOCK coordinates (global voxel >> 3, arithmetic), both inclusive */
+    int32_t min_free, min_open, min_fnt;   /* 1..512, 1..64, 1..512 */
+    int32_t flags;                         /* GIE_ROUTES_FROM_FRONTIERS */
+    int32_t reserved[2];                   /* 0 */
+} gie_routes_param;
+typedef struct gie_routes_info {           /* 32 bytes */
+    int32_t n_nodes, n_links, n_frontier, n_sources;
+    int32_t n_reached, max_steps;          /* n_reached counts steps >= 0; max_steps is the largest value, -1 without a source */
+    int32_t reserved[2];                   /* 0 */
+} gie_routes_info;
+int gie_routes_compute(gie_mapper *h, const float *goal_xyz, int n, const gie_routes_param *p, gie_routes_info *info);
+int gie_routes_compute_dev(gie_mapper *h, const float *d_goal_xyz, int n, const gie_routes_param *p, gie_routes_info *d_info);
+int gie_read_routes(gie_mapper *h, int32_t *steps, uint8_t *cells);
+int gie_read_routes_dev(gie_mapper *h, int32_t *d_steps, uint8_t *d_cells);
+int gie_routes_query(gie_mapper *h, const float *xyz, int n, int32_t *steps);
+int gie_routes_query_dev(gie_mapper *h, const float *d_xyz, int n, int32_t *d_steps);
+int gie_routes_path(gie_mapper *h, const float *start_xyz, int n, int max_len, int32_t *path_key, int32_t *len);
+int gie_routes_path_dev(gie_mapper *h, const float *d_start_xyz, int n, int max_len, int32_t *d_path_key, int32_t *d_len);
+
 /* ---- ground costmap: the footprint of a height band of the local volume and its exact 2-D distance transform, for ground and
  * planar robots (the reference's ugv_height set-ups: cfg/ugv_laser3D_params.yaml, cfg/scan2D_params.yaml).  A body that occupies a
  * band of z needs a 2-D grid — which cells are blocked, how far each is from the nearest blocked one — and neither the 3-D EDT nor
